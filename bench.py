@@ -24,13 +24,21 @@ north_star's collectives in the loop (flat 283 KB gradient all-reduce + 3-float 
 step, ppo2.py) and reports whole-job iterations/s and samples/s.
 
 Prints ONE JSON line (rank 0).  `value` = env-steps/s of the K timed steps issued the way --launch says (default: ONE persistent
-launch, irrl_env_step_rows_persistent_out) with EVERY step's ob / reward / done / extraInfo stored to its own row in HBM.  Extra
-objects: `roofline` (the binding one: FP32 VALU, dominant kernel HIP-event timed over the timed region on the stream it is launched
-on; `traffic` = its HBM bytes from the PMC passes), `roofline_hbm` (the HBM view: this path is latency/issue bound, not HBM bound,
-SURVEY 8d), `launch_modes` (the other ways of issuing the same steps, measured after the timed bracket), `cpu_baseline` (the f64 oracle
+launch, irrl_env_step_rows_persistent_out) with EVERY step's ob / reward / done / extraInfo stored to its own row in HBM; `ms_per_step` =
+wall milliseconds of one timed step.  Extra objects: `roofline` (the binding one: FP32 VALU, dominant kernel HIP-event timed over the timed
+region on the stream it is launched on; `traffic` = its HBM bytes from the PMC passes) and `roofline_hbm` (the HBM view: this path is
+latency/issue bound, not HBM bound).
+
+A plain run does only what `value` needs: set-up, pre-roll, warm-up, the K timed steps, the line.  `--full` adds everything else, all
+measured after the timed bracket: `launch_modes` (the other ways of issuing the same steps), `steady_state_check` (--check-steps),
+`per_step_call` / `per_step_call_compiled` (one step() call per step through ctypes / the pybind11 module), `cpu_baseline` (the f64 oracle
 with the reference's OpenMP-over-envs threading on the GPU box's host cores + its single-thread rate, bounded sample, rank 0 / N=1 only),
 `ppo` (second half of the metric: the LSTM policy of config 3; default precision of the update + `f32_level`: the same iteration with
-the update at the f32 level) and `ppo_mlp` (the same with config 2's MlpPolicy learner).
+the update at the f32 level) and `ppo_mlp` (the same with config 2's MlpPolicy learner).  Without --full these are null or absent.
+
+`--dump-outputs DIR` writes what the last timed step returned (rank 0's ob, reward, done, extraInfo) as DIR/<name>.npy in float32, at most
+DUMP_BYTES in all (beyond that a fixed, seeded sample of envs, whose ids go to DIR/env_index.npy).  The inputs depend on the arguments
+only (Philox action stream, seeded pool), so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -51,6 +59,8 @@ FP32_PEAK_TFLOPS = 157.3
 ACTION_SEED = 1
 MIN_PREROLL = 200
 HOT_STEPS = 300                 # untimed steps of the same workload right in front of a bracket's opening synchronize (see bracket())
+DUMP_BYTES = 64 << 20           # cap of --dump-outputs
+DUMP_SEED = 12345               # the env sample of --dump-outputs when the outputs exceed DUMP_BYTES
 
 
 def parse_args(argv=None):
@@ -63,8 +73,11 @@ def parse_args(argv=None):
     ap.add_argument("--cfg", default="bp5_imitation.yaml")
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE",
                     help="override one key of the env configuration (YAML scalar), e.g. --set Crutial=true; the bench line names it")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline sample budget (0 disables)")
-    ap.add_argument("--ppo-iters", type=int, default=5, help="timed PPO iterations of each learner leg, reported with min / median / max (0 disables)")
+    ap.add_argument("--full", action="store_true", help="also measure everything besides `value` (launch modes, check window, per-call rates, "
+                    "CPU baseline, PPO legs), after the timed bracket; a plain run does only the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy (float32)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline sample budget (0 disables; --full only)")
+    ap.add_argument("--ppo-iters", type=int, default=5, help="timed PPO iterations of each learner leg, reported with min / median / max (0 disables; --full only)")
     ap.add_argument("--ppo-steps", type=int, default=750, help="rollout length of the PPO leg (the metric's is 750)")
     ap.add_argument("--ppo-epochs", type=int, default=10, help="optimisation epochs of the PPO leg (the metric's is 10)")
     ap.add_argument("--launch", choices=("persistent", "rows", "graph", "python"), default="persistent",
@@ -74,11 +87,31 @@ def parse_args(argv=None):
                          "steps (irrl_env_step_rows_persistent_out: robots never interact, so nothing has to wait for the slowest wave of a step), "
                          "'rows' = K back-to-back launches from one irrl_env_step_rows_out call, 'graph' = one hipGraph of K step-kernel nodes, "
                          "'python' = one ctypes call per step.  The modes that were not timed are reported as extras (`launch_modes`).")
-    ap.add_argument("--no-mode-extras", action="store_true", help="skip the untimed extras that measure the other launch modes")
+    ap.add_argument("--no-mode-extras", action="store_true", help="skip the untimed extras that measure the other launch modes (--full only)")
     ap.add_argument("--no-graph", dest="launch", action="store_const", const="python", help="same as --launch python")
     ap.add_argument("--check-steps", type=int, default=2000, help="extra untimed-for-`value` window after the timed region that "
-                    "re-measures us/step over a longer run (0 disables); reported as `steady_state_check`")
-    return ap.parse_args(argv)
+                    "re-measures us/step over a longer run (0 disables; --full only); reported as `steady_state_check`")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(out_dir, arrays, cap=DUMP_BYTES, seed=DUMP_SEED):
+    """arrays: name -> numpy array whose first axis is the env.  Writes out_dir/<name>.npy in float32; when they exceed `cap` bytes
+    together, only a fixed, seeded sample of envs (the same for every array) is written, and its ids as out_dir/env_index.npy."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    n = min(len(v) for v in arrays.values())
+    per_env = sum(v[0].nbytes for v in arrays.values()) if n else 0
+    if per_env * n > cap:
+        keep = np.sort(np.random.RandomState(seed).choice(n, cap // (per_env + 8), replace=False))     # + 8 B of env_index per kept env
+        arrays = {k: v[keep] for k, v in arrays.items()}
+        arrays["env_index"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return sorted(arrays)
 
 
 def launched_by_torchrun():
@@ -233,9 +266,13 @@ def worker(args):
     loop_count = int(round(float(env_cfg["control_dt"]) / float(env_cfg["simulation_dt"])))
 
     # synthetic action stream resident in HBM: row s = actions of global step s for this rank's envs (global env id =
-    # rank * n + e).  Beyond 16384 steps the stream wraps (it would be 3 GB otherwise); the default run uses 5.5 k rows.
+    # rank * n + e).  Beyond 16384 steps the stream wraps (it would be 3 GB otherwise); a default plain run uses 4.5 k rows.
     preroll = max(MIN_PREROLL, args.preroll)
-    total = preroll + args.warmup + 8 * (args.steps + HOT_STEPS) + 50 + args.check_steps
+    # a plain run issues pre-roll + warm-up + the hot steps + K; --full also the extras' brackets and the check window.  Row s holds step s's
+    # actions whatever the table size, and a table below the cap holds every step the run issues: the timed steps see the same actions.
+    total = preroll + args.warmup + HOT_STEPS + args.steps
+    if args.full:
+        total = preroll + args.warmup + 8 * (args.steps + HOT_STEPS) + 50 + args.check_steps
     rows = min(total, 16384)
     lib = _lib.load()
     actions = torch.empty(rows, n, 12, device=dev)
@@ -370,10 +407,14 @@ def worker(args):
         raise SystemExit("bench.py: no toe was in contact during the timed region (free flight) -- not a valid measurement")
     if resets == 0 and n * world * args.steps >= 50000:
         raise SystemExit("bench.py: no episode ended inside the timed region of %d env-steps -- not the steady-state workload" % (n * world * args.steps))
+    if args.dump_outputs and rank == 0:
+        # what the last of the K timed steps returned, read before anything else steps the pool or rewrites the tables
+        dump_outputs(args.dump_outputs, {"ob": ob_rows[K - 1].cpu().numpy(), "reward": rew_rows[K - 1].cpu().numpy(),
+                                         "done": done_rows[K - 1].cpu().numpy(), "extra_info": extra_rows[K - 1].cpu().numpy()})
     # EXTRAS, untimed for `value`: the same K steps issued in the other ways (every step's outputs kept, as in the timed bracket), two
     # brackets each, the faster one reported; and the persistent launch that keeps only the last step's outputs (round 4's headline form)
     launch_modes = None
-    if not args.no_mode_extras and args.steps <= 20000:
+    if args.full and not args.no_mode_extras and args.steps <= 20000:
         launch_modes = {}
         for cand in ("persistent", "rows", "graph", "python"):
             t_c = min(bracket(cand) for _ in range(2))
@@ -384,7 +425,7 @@ def worker(args):
                                 "all outputs of every step kept except in persistent_last_step_outputs_only (irrl_env_step_rows_persistent: the form "
                                 "BENCH_r04 timed)" % args.steps)
     check = None
-    if args.check_steps > 0:
+    if args.full and args.check_steps > 0:
         # a longer window behind the timed region, in FIVE consecutive parts: mean and spread of us / step (the driver's --steps 20
         # bracket is 0.8 ms long; this says what the same kernel does over thousands of steps and how much that moves)
         torch.cuda.synchronize()
@@ -413,7 +454,7 @@ def worker(args):
     # the same K steps issued the way the reference's runner issues them: ONE FlexibleGymEnv.step() call (ctypes -> C-ABI) per
     # control step (RaisimGymVecEnv.py:31), wall clock around the loop -- reported beside `value`, never as `value`
     per_call = None
-    if world == 1:
+    if args.full and world == 1:
         run(HOT_STEPS)
         torch.cuda.synchronize()
         tc = time.perf_counter()
@@ -524,9 +565,9 @@ def worker(args):
             "library": lib.irrl_version().decode(), "pmc_note": pmc_note, "per_step_call": per_call, "per_step_call_compiled": per_call_native,
             "contact_solver": int(env_cfg.get("ContactSolver", 3)),
         }
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(env_cfg, args.cpu_seconds)
-    if args.ppo_iters > 0:
+    if args.full and args.ppo_iters > 0:
         # second half of BASELINE.json's metric ("PPO iters/sec"): the reference's training iteration (750-step rollout of
         # all envs with the 2x48 + 2x48 LSTM policy, GAE, 10 epochs of full-length BPTT, global reset) on every rank, gradients
         # and advantage moments all-reduced per optimizer step; reported beside the headline value, never mixed into it

@@ -11,7 +11,9 @@ class HipVecEnv(object):
     def __init__(self, env_cfg):
         env_cfg = dict(env_cfg)
         ref = env_cfg.pop("_ref_table", None)     # reference-trajectory table of a ManualTraj: False config (test plumbing)
-        text = yaml.safe_dump(env_cfg, default_flow_style=False)
+        # one line per key: the library's config reader takes "key: value" lines, and PyYAML would otherwise fold a long value
+        # (a RefTraj path with a space, under a long temporary directory) onto a second line
+        text = yaml.safe_dump(env_cfg, default_flow_style=False, width=float("inf"))
         self.impl = FlexibleGymEnv(pkg.__BLACKPANTHER_V55_RESOURCE_DIRECTORY__, text)
         if ref is not None:
             self.impl.set_ref(ref)

@@ -5,6 +5,7 @@ import shutil
 import sys
 
 import numpy as np
+import pytest
 
 from conftest import ROOT
 
@@ -99,6 +100,41 @@ def test_bench_gpus_n_launches_n_ranks_by_itself(monkeypatch):
     except SystemExit as e:
         assert e.code == 0
     assert len(calls) == 1
+
+
+def test_bench_arguments_full_dump_outputs_and_steps():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--steps", "7", "--warmup", "3"])
+    assert a.steps == 7 and a.warmup == 3 and not a.full and a.dump_outputs is None
+    b = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert b.full and b.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_bench_dump_outputs_writes_float32_within_the_cap(tmp_path):
+    """every array as <name>.npy in float32; above the cap a seeded sample of envs, the same one every time, and its ids"""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.RandomState(0)
+    arrays = {"ob": rng.randn(1000, 35).astype(np.float32), "reward": rng.randn(1000).astype(np.float32), "done": rng.rand(1000) < 0.1}
+    assert bench.dump_outputs(str(tmp_path / "all"), arrays) == ["done", "ob", "reward"]
+    for k, v in arrays.items():
+        got = np.load(str(tmp_path / "all" / (k + ".npy")))
+        assert got.dtype == np.float32 and np.array_equal(got, v.astype(np.float32))
+    cap = 20000
+    for d in ("s1", "s2"):
+        assert bench.dump_outputs(str(tmp_path / d), arrays, cap=cap) == ["done", "env_index", "ob", "reward"]
+    files = sorted(os.listdir(str(tmp_path / "s1")))
+    assert sum(np.load(str(tmp_path / "s1" / f)).nbytes for f in files) <= cap
+    idx = np.load(str(tmp_path / "s1" / "env_index.npy"))
+    assert idx.dtype == np.float64 and len(idx) > 0 and np.all(np.diff(idx) > 0)
+    for f in files:
+        x, y = np.load(str(tmp_path / "s1" / f)), np.load(str(tmp_path / "s2" / f))
+        assert np.array_equal(x, y)
+        if f != "env_index.npy":
+            assert np.array_equal(x, arrays[f[:-4]][idx.astype(int)].astype(np.float32))
 
 
 def test_baseline_config1_plumbing_runs_through_the_training_script_on_cpu():

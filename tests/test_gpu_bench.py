@@ -159,7 +159,7 @@ def _run_bench(extra, env_over):
 
 
 def test_bench_single_gpu_line_is_steady_state():
-    out = _run_bench(["--steps", "20", "--warmup", "5", "--ppo-iters", "0", "--cpu-seconds", "0", "--check-steps", "200"], {})
+    out = _run_bench(["--full", "--steps", "20", "--warmup", "5", "--ppo-iters", "0", "--cpu-seconds", "0", "--check-steps", "200"], {})
     assert out["n_gpus"] == 1 and out["steps"] == 20 and out["warmup"] == 5
     assert out["contact_fraction_in_timed_region"] > 0.1 and out["resets_in_timed_region"] > 0
     assert out["config"]["preroll"] >= 200
@@ -179,6 +179,48 @@ def test_bench_single_gpu_line_is_steady_state():
     assert all(lm[k]["env_steps_per_sec"] > 5e7 for k in ("persistent", "rows", "graph", "python"))
 
 
+def test_plain_bench_times_only_the_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """a plain run (no --full) measures `value` and nothing else; --dump-outputs writes what the last of the K timed steps returned:
+    the same bytes in two runs with the same arguments, and the same bits as the pool stepped here through the same action rows"""
+    import torch
+    import yaml
+    import high_speed_quadrupedal_locomotion_by_irrl_amd as pkg
+    from high_speed_quadrupedal_locomotion_by_irrl_amd import _lib
+    from high_speed_quadrupedal_locomotion_by_irrl_amd.flexible_robot import FlexibleGymEnv
+    n, K, warmup, preroll = 512, 30, 5, 200
+    args = ["--steps", str(K), "--warmup", str(warmup), "--preroll", str(preroll), "--envs", str(n)]
+    runs = [_run_bench(args + ["--dump-outputs", str(tmp_path / d)], {}) for d in ("a", "b")]
+    for out in runs:
+        assert out["steps"] == K and out["warmup"] == warmup and out["config"]["preroll"] == preroll
+        assert abs(out["value"] - n / (out["ms_per_step"] * 1e-3)) < 1e-9 * out["value"]
+        assert out["launch_modes"] is None and out["steady_state_check"] is None and out["per_step_call"] is None
+        assert out["per_step_call_compiled"] is None and "cpu_baseline" not in out and "ppo" not in out and "ppo_mlp" not in out
+    names = {"ob": (n, 35), "reward": (n,), "done": (n,), "extra_info": (n, 6)}
+    assert sorted(os.listdir(str(tmp_path / "a"))) == sorted(k + ".npy" for k in names)
+    got = {}
+    for name, shape in names.items():
+        a, b = np.load(str(tmp_path / "a" / (name + ".npy"))), np.load(str(tmp_path / "b" / (name + ".npy")))
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all()
+        assert np.array_equal(a, b), name
+        got[name] = a
+    # the bench's pool (same configuration, EnvIdOffset 0) through the same Philox rows: pre-roll + warm-up + the hot steps + K
+    with open(os.path.join(pkg.__BLACKPANTHER_V55_RESOURCE_DIRECTORY__, "bp5_imitation.yaml")) as f:
+        cfg = yaml.safe_load(f)["environment"]
+    cfg.update(num_envs=n, EnvIdOffset=0)
+    env = FlexibleGymEnv(pkg.__BLACKPANTHER_V55_RESOURCE_DIRECTORY__, yaml.safe_dump(cfg), device=0)
+    env.init()
+    steps = preroll + warmup + 300 + K
+    lib = _lib.load()
+    actions = torch.empty(steps, n, 12, device="cuda")
+    _lib.check(lib.irrl_bench_actions(1, 0, n, 0, steps, 0.3, C.c_void_p(actions.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    ob, rew = torch.zeros(n, 35, device="cuda"), torch.zeros(n, device="cuda")
+    done, extra = torch.zeros(n, dtype=torch.bool, device="cuda"), torch.zeros(n, 6, device="cuda")
+    env.step_rows(steps, actions, 0, ob, rew, done, extra)
+    torch.cuda.synchronize()
+    for name, t in zip(names, (ob, rew, done, extra)):
+        assert np.array_equal(got[name], t.float().cpu().numpy()), name
+
+
 def test_bench_every_launch_mode_gives_a_line():
     for mode in ("persistent", "rows", "graph", "python"):
         out = _run_bench(["--steps", "20", "--warmup", "5", "--ppo-iters", "0", "--cpu-seconds", "0", "--check-steps", "0", "--launch", mode, "--no-mode-extras"],
@@ -188,7 +230,7 @@ def test_bench_every_launch_mode_gives_a_line():
 
 
 def test_bench_gpus_2_runs_two_ranks_with_the_ppo_collectives():
-    out = _run_bench(["--gpus", "2", "--steps", "20", "--warmup", "5", "--envs", "512", "--cpu-seconds", "0", "--check-steps", "0",
+    out = _run_bench(["--full", "--gpus", "2", "--steps", "20", "--warmup", "5", "--envs", "512", "--cpu-seconds", "0", "--check-steps", "0",
                       "--ppo-iters", "1", "--ppo-steps", "32", "--ppo-epochs", "2"],
                      {"IRRL_BENCH_BACKEND": "gloo", "IRRL_BENCH_ONE_DEVICE": "1"})
     assert out["n_gpus"] == 2 and out["rccl_ranks_seen"] == 2 and out["config"]["global_envs"] == 1024

@@ -247,7 +247,7 @@ def test_bench_under_a_one_rank_launcher_uses_rccl():
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0",
                IRRL_BENCH_NATIVE="0", IRRL_BENCH_F32_LEVEL="0")
     env.pop("IRRL_BENCH_BACKEND", None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--envs", "512", "--cpu-seconds", "0",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "20", "--warmup", "5", "--envs", "512", "--cpu-seconds", "0",
                         "--check-steps", "0", "--no-mode-extras", "--ppo-iters", "1", "--ppo-steps", "32", "--ppo-epochs", "2"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]

@@ -308,9 +308,23 @@ def gen_actor_weights():
     print("wrote actor_bp5_155.npz", {k: v.shape for k, v in out.items()})
 
 
+def gen_checkpoint():
+    """The content of the trained bp5_155 checkpoint -- its hyper-parameters and all 19 parameter arrays -- without the tensorflow /
+    cloudpickle objects the pickle also holds: the tests rebuild a stable-baselines-layout checkpoint `(data, params)` from it."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    from high_speed_quadrupedal_locomotion_by_irrl_amd.checkpoint import read_checkpoint
+    data, params = read_checkpoint(os.path.join(REF, "pkl", "bp5_155.pkl"))
+    out = {"p%02d" % i: np.asarray(p) for i, p in enumerate(params)}
+    out["data"] = np.array(json.dumps(data, sort_keys=True))
+    np.savez_compressed(os.path.join(OUT, "bp5_155_checkpoint.npz"), **out)
+    print("wrote bp5_155_checkpoint.npz", len(params), "arrays")
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["task", "lstm", "lstm_syn", "ppo", "actor"]
+    which = sys.argv[1:] or ["task", "lstm", "lstm_syn", "ppo", "actor", "ckpt"]
+    if "ckpt" in which:
+        gen_checkpoint()
     if "actor" in which:
         gen_actor_weights()
     if "task" in which:

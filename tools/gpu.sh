@@ -49,30 +49,30 @@ while [ $# -gt 0 ]; do
     smoke) timeout 600 python __graft_entry__.py --smoke > $O/smoke.log 2>&1; echo "smoke rc=$?" >> $O/smoke.log ;;
     tests) timeout 2400 python -m pytest tests -m gpu -q -s ${TESTS_K:+-k "$TESTS_K"} > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.log ;;
     bench)
-      timeout 900 python bench.py > $O/bench.log 2>&1; echo "bench rc=$?" >> $O/bench.log
-      timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_driver_style.log 2>&1 ;;
+      timeout 900 python bench.py --full > $O/bench.log 2>&1; echo "bench rc=$?" >> $O/bench.log
+      timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_style.log 2>&1 ;;
     bench3)
       for c in bp5_imitation default_cfg bp5_terrain; do
-        timeout 600 python bench.py --cfg $c.yaml --cpu-seconds 0 --ppo-iters 0 --steps 2000 > $O/bench_$c.log 2>&1
+        timeout 600 python bench.py --full --cfg $c.yaml --cpu-seconds 0 --ppo-iters 0 --steps 2000 > $O/bench_$c.log 2>&1
       done ;;
     solvers)
       rm -f $O/solvers.log
       for s in 3 2 1 0 3 2; do
-        timeout 600 python bench.py --set ContactSolver=$s --cpu-seconds 0 --ppo-iters 0 --steps 2000 2>/dev/null | line "ContactSolver=$s" >> $O/solvers.log
+        timeout 600 python bench.py --full --set ContactSolver=$s --cpu-seconds 0 --ppo-iters 0 --steps 2000 2>/dev/null | line "ContactSolver=$s" >> $O/solvers.log
       done ;;
     sweep)
       rm -f $O/sweep.log
       for n in 1024 4096 6144 8192 16384 32768 131072; do
-        timeout 300 python bench.py --cpu-seconds 0 --ppo-iters 0 --steps 1000 --warmup 100 --check-steps 0 --envs $n --launch rows 2>/dev/null | line "envs=$n, one launch per step:" >> $O/sweep.log
-        timeout 300 python bench.py --cpu-seconds 0 --ppo-iters 0 --steps 1000 --warmup 100 --check-steps 0 --envs $n --launch persistent 2>/dev/null | line "envs=$n, ONE persistent launch:" >> $O/sweep.log
+        timeout 300 python bench.py --full --cpu-seconds 0 --ppo-iters 0 --steps 1000 --warmup 100 --check-steps 0 --envs $n --launch rows 2>/dev/null | line "envs=$n, one launch per step:" >> $O/sweep.log
+        timeout 300 python bench.py --full --cpu-seconds 0 --ppo-iters 0 --steps 1000 --warmup 100 --check-steps 0 --envs $n --launch persistent 2>/dev/null | line "envs=$n, ONE persistent launch:" >> $O/sweep.log
       done
       timeout 300 python tools/host_boundary_rate.py >> $O/sweep.log 2>&1 ;;
     gloo8)
       # BASELINE configs 4 / 5 at their real size WITHOUT the 8-GPU node: eight ranks x 4096 envs = the 32 768-env job, every rank on
       # this one MI355X, barrier / all-reduces over gloo (the RCCL / xGMI transport itself stays unmeasured); the PPO legs run the
       # per-optimizer-step collectives of SURVEY 8e.  The JSON line is copied to profiles/ by hand.
-      IRRL_BENCH_BACKEND=gloo IRRL_BENCH_ONE_DEVICE=1 OMP_NUM_THREADS=2 timeout 1500 python bench.py --gpus 8 --ppo-iters ${GLOO8_PPO_ITERS:-2} > $O/bench_gloo8.log 2>&1; echo "rc=$?" >> $O/bench_gloo8.log
-      IRRL_BENCH_BACKEND=gloo IRRL_BENCH_ONE_DEVICE=1 OMP_NUM_THREADS=2 timeout 900 python bench.py --gpus 8 --cfg bp5_terrain.yaml --ppo-iters 0 > $O/bench_gloo8_terrain.log 2>&1; echo "rc=$?" >> $O/bench_gloo8_terrain.log ;;
+      IRRL_BENCH_BACKEND=gloo IRRL_BENCH_ONE_DEVICE=1 OMP_NUM_THREADS=2 timeout 1500 python bench.py --full --gpus 8 --ppo-iters ${GLOO8_PPO_ITERS:-2} > $O/bench_gloo8.log 2>&1; echo "rc=$?" >> $O/bench_gloo8.log
+      IRRL_BENCH_BACKEND=gloo IRRL_BENCH_ONE_DEVICE=1 OMP_NUM_THREADS=2 timeout 900 python bench.py --full --gpus 8 --cfg bp5_terrain.yaml --ppo-iters 0 > $O/bench_gloo8_terrain.log 2>&1; echo "rc=$?" >> $O/bench_gloo8_terrain.log ;;
     prof)
       (cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -- python3 $R/bench.py --steps 20 --warmup 5 --cpu-seconds 0 --ppo-iters 0 --check-steps 0 > $O/rocprof_bench.log 2>&1) ;;
     profppo)
@@ -145,7 +145,7 @@ while [ $# -gt 0 ]; do
     variants)
       V=high_speed_quadrupedal_locomotion_by_irrl_amd/csrc/_variants; rm -f $O/variants.log
       for r in 1 2; do for f in $V/libirrl_env_*.so; do
-        IRRL_ENV_LIB=$PWD/$f timeout 300 python bench.py ${VARIANT_ARGS} --cpu-seconds 0 --ppo-iters 0 --steps 2000 2>/dev/null | line "$(basename $f .so)" >> $O/variants.log
+        IRRL_ENV_LIB=$PWD/$f timeout 300 python bench.py --full ${VARIANT_ARGS} --cpu-seconds 0 --ppo-iters 0 --steps 2000 2>/dev/null | line "$(basename $f .so)" >> $O/variants.log
       done; done
       if [ -n "$VARIANTS_PPO" ]; then for f in $V/libirrl_env_*.so; do
         for pol in ${VARIANTS_PPO}; do
