@@ -1,5 +1,5 @@
 // env_kernels.hip -- __global__ wrappers of the lane bodies in env_core.hpp (gfx950 only); compiled once per lane layout (build.py).
-// Launch shape of the lane kernels: 64-thread workgroups = one wave = 4 robots (16 lanes per robot, one DPP row each: pools <= 6144) or 16 robots
+// Launch shape of the lane kernels: 64-thread workgroups = one wave = 4 robots (16 lanes per robot, one DPP row each: pools of up to one wave per SIMD, 4096 robots on an MI355X) or 16 robots
 // (4 lanes per robot, one DPP quad each).  At N = 4096 the 16-lane layout is 1024 workgroups -> one wave on every SIMD of the 256 CUs; the kernels
 // keep the whole robot state in registers across the 8 substeps (no LDS; scratch only in the reset branch), so __launch_bounds__(256, 1) lets the
 // allocator use the full 512-register budget of a SIMD that hosts a single wave.  The rollout kernels (policy in the same launch) run 256-thread
@@ -27,6 +27,7 @@
 #if IRRL_LANES_PER_ROBOT == 16
 #include "policy_step.hpp"   // the LSTM policy's rollout step (device code shared with lstm_kernels.hip)
 #endif
+#include "env_kernels_decl.h"   // every kernel below is declared there: the launcher (irrl_env_abi.hip) sees the same signatures
 
 // This file is compiled three times (build.py): once per lane layout, kernel names suffixed _l16 / _l4, and the 4-lane layout once more for
 // TWO waves per SIMD (_l4w2, -DIRRL_L4_WAVES2: 256 registers per wave, ~130-220 of the step kernels' values in scratch).  Pools of more than
@@ -56,24 +57,25 @@ __device__ __forceinline__ int irrl_xcd_block() {
   const int q = nb >> 3, r = nb & 7;                // XCD x gets q workgroups, + 1 if x < r
   return x * q + (x < r ? x : r) + j;
 }
-// env_: robot of this lane; leg_: its leg; valid_: this lane owns the stores of (robot, leg) -- with 16 lanes per robot
-// that is sub-lane 0 of each quad.  Idle rows shadow the last robot with their stores masked.  BLK: the (renumbered) block index.
+// The lane context: which robot and leg a lane integrates.  env: the robot; rw: its index inside the wave; leg: the lane's leg; valid: this
+// lane owns the stores of (robot, leg) -- with 16 lanes per robot that is sub-lane 0 of each quad.  Idle rows (quads) shadow the last robot
+// with their stores masked.  `wave`: the wave's index in the pool (a kernel decides how its workgroups map to it), `lane`: 0 .. 63.
+struct LaneCtx { int env, rw, leg; bool valid; };
+__device__ __forceinline__ LaneCtx irrl_lane_ctx(const EnvParams &P, int wave, int lane) {
+  LaneCtx c;
 #if IRRL_LANES_PER_ROBOT == 16
-#define IRRL_LANE_PROLOGUE_B(BLK)                                                            \
-  const int lane_ = (int)(threadIdx.x & 63u);                                                \
-  const int wave_ = (int)((BLK) * (blockDim.x >> 6) + (threadIdx.x >> 6));                    \
-  int env_ = wave_ * 4 + (lane_ >> 4);                                                       \
-  const int leg_ = (lane_ >> 2) & 3;                                                         \
-  const bool valid_ = (env_ < P.n_envs) && ((lane_ & 3) == 0);                               \
-  if (env_ >= P.n_envs) env_ = P.n_envs - 1;
+  c.rw = lane >> 4; c.env = wave * 4 + c.rw; c.leg = (lane >> 2) & 3;
+  c.valid = (c.env < P.n_envs) && ((lane & 3) == 0);
 #else
-#define IRRL_LANE_PROLOGUE_B(BLK)                              \
-  const int lane_ = (int)(threadIdx.x & 63u);                  \
-  int env_ = (int)((BLK) * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 16 + (lane_ >> 2); \
-  const int leg_ = lane_ & 3;                                  \
-  const bool valid_ = env_ < P.n_envs;                         \
-  if (!valid_) env_ = P.n_envs - 1; /* idle quads shadow the last robot; their stores are masked */
+  c.rw = lane >> 2; c.env = wave * 16 + c.rw; c.leg = lane & 3;
+  c.valid = c.env < P.n_envs;
 #endif
+  if (c.env >= P.n_envs) c.env = P.n_envs - 1;
+  return c;
+}
+// `lc` of the stand-alone lane kernels (any workgroup size); BLK: the (renumbered) block index
+#define IRRL_LANE_PROLOGUE_B(BLK) \
+  const LaneCtx lc = irrl_lane_ctx(P, (int)((BLK) * (blockDim.x >> 6) + (threadIdx.x >> 6)), (int)(threadIdx.x & 63u));
 // P / S of a kernel body: the by-value arguments named in the kernarg segment (lanes_hip*.hpp: their fields are read where they are used,
 // with scalar loads, instead of all at the kernel's entry) -- or, A/B switch of tools/build_variants.py, the arguments themselves
 #ifndef IRRL_NO_PARAMS_KERNARG
@@ -103,6 +105,32 @@ __device__ __forceinline__ int irrl_xcd_block() {
 #define IRRL_ENV_BOUNDS __launch_bounds__(256, 1)
 #endif
 
+// the multi-step kernels' closing store of the lane context they carried in registers
+__device__ __forceinline__ void irrl_store_lane_back(const EnvParams &P, const EnvState &S, int env, int leg, bool valid, const irrl_plain::EnvLane &L) {
+  IRRL_SUB0_ONLY_BEGIN
+  irrl_plain::store_lane(IRRL_PARAMS_REFRESH(P), IRRL_PARAMS_REFRESH(S), env, leg, valid, L, P.randomize_per_episode != 0);
+  IRRL_SUB0_ONLY_END
+}
+
+#if IRRL_LANES_PER_ROBOT == 16
+// The persistent rollout kernels: what a step's PolicyStepArgs take from the launch's besides the fields themselves, read once in front of the step loop ...
+struct PolicyStepBase {
+  const float *states_first, *noise0;
+  long long row0, rng0;
+  size_t noise_stride;
+  __device__ __forceinline__ explicit PolicyStepBase(const PolicyStepArgs &a)
+      : states_first(a.states_in), noise0(a.noise), row0(a.row), rng0(a.rng_step), noise_stride((size_t)a.N * (size_t)a.act_dim) {}
+  // ... and step k's arguments: the launch's, re-read inside the step, with the row, RNG step, noise row and recurrent state of step k
+  __device__ __forceinline__ PolicyStepArgs at(const PolicyStepArgs &a, int k) const {
+    PolicyStepArgs ak = IRRL_PARAMS_REFRESH(a);
+    ak.row = row0 + k; ak.rng_step = rng0 + k;
+    ak.noise = noise0 ? noise0 + (size_t)k * noise_stride : nullptr;
+    ak.states_in = k == 0 ? states_first : a.states_out;
+    return ak;
+  }
+};
+#endif
+
 extern "C" {
 
 // The step kernel exists once per (Crutial, per-contact rule): the launcher picks by EnvParams::crutial / ::contact_rule.  Suffix
@@ -114,7 +142,7 @@ extern "C" {
   IRRL_K(NAME)(EnvParams P_, EnvState S_, const float *action, float *ob, float *reward, uint8_t *done, float *extra) {             \
     IRRL_BIND_ARGS                                                                                                                 \
     IRRL_LANE_PROLOGUE                                                                                                             \
-    NS::step_body<RULE>(P, S, env_, leg_, valid_, action, ob, reward, done, extra);                                                \
+    NS::step_body<RULE>(P, S, lc.env, lc.leg, lc.valid, action, ob, reward, done, extra);                                          \
   }
 IRRL_STEP_KERNEL(irrl_step_kernel_crutial, irrl, 0)
 IRRL_STEP_KERNEL(irrl_step_kernel_crutial_md, irrl, 1)
@@ -130,10 +158,10 @@ IRRL_K(irrl_step_kernel)(EnvParams P_, EnvState S_, const float *action, float *
 #ifdef IRRL_PROFILE_WAVES   /* diagnostic build (tools/wave_spread.py): extra[env][5] <- this wave's duration in 100 MHz ticks */
   const unsigned long long t0_ = wall_clock64();
 #endif
-  irrl_plain::step_body<IRRL_RULE_SHIPPED>(P, S, env_, leg_, valid_, action, ob, reward, done, extra);
+  irrl_plain::step_body<IRRL_RULE_SHIPPED>(P, S, lc.env, lc.leg, lc.valid, action, ob, reward, done, extra);
 #ifdef IRRL_PROFILE_WAVES
   const unsigned long long t1_ = wall_clock64();
-  if (valid_ && leg_ == 0) extra[env_ * 6 + 5] = (float)(t1_ - t0_);
+  if (lc.valid && lc.leg == 0) extra[lc.env * 6 + 5] = (float)(t1_ - t0_);
 #endif
 }
 
@@ -162,7 +190,7 @@ irrl_step_policy_kernel_l16(EnvParams P_, EnvState S_, const float *action, floa
     IRRL_LANE_PROLOGUE_IDENTITY
     // the env part keeps no LDS and, between its prologue and its epilogue, issues no global load (flat ground): the layer-0
     // policy weights travel L2 -> LDS underneath the eight substeps
-    irrl_plain::step_body<IRRL_RULE_SHIPPED>(P, S, env_, leg_, valid_, action, ob, reward, done, extra, [&]() { policy_prefetch_lds<48, 256>(a, lds_w); });
+    irrl_plain::step_body<IRRL_RULE_SHIPPED>(P, S, lc.env, lc.leg, lc.valid, action, ob, reward, done, extra, [&]() { policy_prefetch_lds<48, 256>(a, lds_w); });
   }
 #ifdef IRRL_PROFILE_POLICY
   const unsigned long long pt1_ = wall_clock64();
@@ -192,9 +220,7 @@ irrl_rollout_persistent_kernel_l16(EnvParams P_, EnvState S_, float *ob, float *
   __shared__ float head_w[48 * 17];
   __shared__ __attribute__((aligned(1024))) float lds_w[PolicyLdsImage<48>::FLOATS];   // 126 KiB: wh0 | wx0 of the actor and the critic stack
   policy_prefetch_lds<48, 256>(a, lds_w);
-  const float *states_first = a.states_in, *noise0 = a.noise;
-  const long long row0 = a.row, rng0 = a.rng_step;
-  const size_t noise_stride = (size_t)a.N * (size_t)a.act_dim;
+  const PolicyStepBase base(a);
   __syncthreads();   // the LDS image has landed
 #ifdef IRRL_PROFILE_PERSIST   /* diagnostic build (tools/persistent_phases.py): where a step goes, per wave, summed over the steps */
   unsigned long long ph_[4] = {0, 0, 0, 0}, pts_ = wall_clock64();
@@ -207,22 +233,14 @@ irrl_rollout_persistent_kernel_l16(EnvParams P_, EnvState S_, float *ob, float *
     // optimizer, the loop-invariant addresses of both parts -- hundreds of 64-bit values -- are hoisted and spilled)
     int tid = (int)threadIdx.x;
     asm volatile("" : "+v"(tid));
-    PolicyStepArgs ak = IRRL_PARAMS_REFRESH(a);
-    ak.row = row0 + k; ak.rng_step = rng0 + k;
-    ak.noise = noise0 ? noise0 + (size_t)k * noise_stride : nullptr;
-    ak.states_in = k == 0 ? states_first : a.states_out;
+    const PolicyStepArgs ak = base.at(a, k);
     policy_step_body<48, 9, 2, 256, true>(ak, (int)blockIdx.x * 16, hbuf, terms, head_w, lds_w, 0, 0, tid);
     IRRL_PP_STAMP(0);   // policy step
     __syncthreads();   // this workgroup's clipped actions (and the rollout rows) are stored and visible to its own loads
     IRRL_PP_STAMP(1);   // barrier behind the policy step
     {
-      const int lane_ = tid & 63;
-      const int wave_ = (int)blockIdx.x * 4 + (tid >> 6);
-      int env_ = wave_ * 4 + (lane_ >> 4);
-      const int leg_ = (lane_ >> 2) & 3;
-      const bool valid_ = (env_ < P.n_envs) && ((lane_ & 3) == 0);
-      if (env_ >= P.n_envs) env_ = P.n_envs - 1;
-      irrl_plain::step_body<IRRL_RULE_SHIPPED>(IRRL_PARAMS_REFRESH(P), IRRL_PARAMS_REFRESH(S), env_, leg_, valid_, (const float *)ak.clipped, ob, reward, done, extra);
+      const LaneCtx lc = irrl_lane_ctx(P, (int)blockIdx.x * 4 + (tid >> 6), tid & 63);
+      irrl_plain::step_body<IRRL_RULE_SHIPPED>(IRRL_PARAMS_REFRESH(P), IRRL_PARAMS_REFRESH(S), lc.env, lc.leg, lc.valid, (const float *)ak.clipped, ob, reward, done, extra);
     }
     IRRL_PP_STAMP(2);   // env step of this wave's four robots
     __syncthreads();   // obs / dones / reward of step k are stored and visible: the next policy step reads them
@@ -255,11 +273,10 @@ irrl_rollout_persistent_actor_kernel_l16(EnvParams P_, EnvState S_, float *ob, f
   __shared__ __attribute__((aligned(1024))) float lds_w[PolicyLdsImage<48>::FLOATS];   // wh0 | wx0 | wh1 | wx1 of the ACTOR stack
   policy_prefetch_lds_actor<48, 256>(a, lds_w);
   for (int i = (int)threadIdx.x; i < 48 * a.act_dim; i += 256) head_w[i] = a.pi_w[i];
-  const float *states_first = a.states_in, *noise0 = a.noise;
-  const long long row0 = a.row, rng0 = a.rng_step;
-  const size_t noise_stride = (size_t)a.N * (size_t)a.act_dim;
+  const PolicyStepBase base(a);
   // the env part's lane context stays in registers across the steps (irrl_steps_persistent_kernel below): with one virtual wave per wave the
-  // policy part leaves room for it (379 registers, no scratch beyond the reset branch's)
+  // policy part leaves room for it (379 registers, no scratch beyond the reset branch's).  (irrl_lane_ctx() written out: called here, it costs
+  // this kernel a different register assignment from its first instructions on -- 212 of 17 981 lines -- and the kernel is held to its ISA.)
   const int lane0_ = (int)(threadIdx.x & 63u);
   int env0_ = ((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 4 + (lane0_ >> 4);
   const int leg0_ = (lane0_ >> 2) & 3;
@@ -273,10 +290,7 @@ irrl_rollout_persistent_actor_kernel_l16(EnvParams P_, EnvState S_, float *ob, f
   for (int k = 0; k < steps; k++) {
     int tid = (int)threadIdx.x;
     asm volatile("" : "+v"(tid));     // (see irrl_rollout_persistent_kernel_l16: keeps the per-lane addresses inside the loop)
-    PolicyStepArgs ak = IRRL_PARAMS_REFRESH(a);
-    ak.row = row0 + k; ak.rng_step = rng0 + k;
-    ak.noise = noise0 ? noise0 + (size_t)k * noise_stride : nullptr;
-    ak.states_in = k == 0 ? states_first : a.states_out;
+    const PolicyStepArgs ak = base.at(a, k);
     policy_step_body<48, 9, 1, 256, true, true>(ak, (int)blockIdx.x * 16, hbuf, terms, head_w, lds_w, 0, 0, tid);
     __syncthreads();   // this workgroup's clipped actions (and the rollout rows) are stored and visible to its own loads
     {
@@ -292,11 +306,7 @@ irrl_rollout_persistent_actor_kernel_l16(EnvParams P_, EnvState S_, float *ob, f
     __syncthreads();   // obs / dones / reward of step k are stored and visible: the next policy step reads them
   }
 #ifndef IRRL_ACTOR_NO_CARRY
-  if (steps > 0) {
-    IRRL_SUB0_ONLY_BEGIN
-    irrl_plain::store_lane(IRRL_PARAMS_REFRESH(P), IRRL_PARAMS_REFRESH(S), env0_, leg0_, valid0_, L, P.randomize_per_episode != 0);
-    IRRL_SUB0_ONLY_END
-  }
+  if (steps > 0) irrl_store_lane_back(P, S, env0_, leg0_, valid0_, L);
 #endif
 }
 #endif
@@ -320,6 +330,8 @@ irrl_rollout_persistent_actor_wave_kernel_l16(EnvParams P_, EnvState S_, float *
   __shared__ __attribute__((aligned(16))) float lds_w[LstmWaveImage<HID>::FLOATS];      // the ACTOR's operands, [gate column][K] (policy_step.hpp)
   lstm_wave_image_stage<HID, 256>(a, lds_w);
   for (int i = (int)threadIdx.x; i < HID * a.act_dim; i += 256) head_w[i] = a.pi_w[i];
+  // (PolicyStepBase and irrl_lane_ctx() written out, here and in the step loop: with either of them this kernel gets another schedule and
+  // register assignment -- same instruction count, thousands of lines moved -- and the kernel is held to its ISA)
   const float *noise0 = a.noise;
   const long long row0 = a.row, rng0 = a.rng_step;
   const size_t noise_stride = (size_t)a.N * (size_t)a.act_dim;
@@ -387,9 +399,7 @@ irrl_rollout_persistent_actor_wave_kernel_l16(EnvParams P_, EnvState S_, float *
     PS_WAVE_SYNC();    // observations / done flags / rewards of step k are in the scratch
   }
   if (steps > 0) {
-    IRRL_SUB0_ONLY_BEGIN
-    irrl_plain::store_lane(IRRL_PARAMS_REFRESH(P), IRRL_PARAMS_REFRESH(S), env0_, leg0_, valid0_, L, P.randomize_per_episode != 0);
-    IRRL_SUB0_ONLY_END
+    irrl_store_lane_back(P, S, env0_, leg0_, valid0_, L);
     if (pok_) {      // the actor's LSTM state behind the last step (the critic's half is the caller's: ppo2.Runner._critic_pass)
 #pragma unroll
       for (int G = 0; G < NG; G++) {
@@ -414,69 +424,58 @@ __global__ void IRRL_ENV_BOUNDS
 irrl_rollout_persistent_mlp_kernel_l16(EnvParams P_, EnvState S_, float *ob, float *reward, uint8_t *done, float *extra, PolicyStepArgs a_, int steps) {
   IRRL_BIND_ARGS
   IRRL_BIND_POLICY_ARGS(a, a_)
-  __shared__ __attribute__((aligned(16))) float wsl[4][MlpWaveLds<64>::FLOATS];      // per wave: its four robots' scratch (policy_step.hpp)
+  typedef MlpWaveLds<64> LAY;
+  __shared__ __attribute__((aligned(16))) float wsl[4][LAY::FLOATS];      // per wave: its four robots' scratch (policy_step.hpp)
   __shared__ float head_w[64 * 17];
   __shared__ __attribute__((aligned(16))) float wl[MlpLdsImage<64>::FLOATS];
   mlp_policy_stage_lds<64>(a, wl, head_w, (int)threadIdx.x, 256);
-  const float *noise0 = a.noise;
-  const long long row0 = a.row, rng0 = a.rng_step;
-  const size_t noise_stride = (size_t)a.N * (size_t)a.act_dim;
+  const PolicyStepBase base(a);
   // the env part's lane context stays in registers across the steps (round 5; irrl_steps_persistent_kernel below): this policy's step needs
   // few registers (its weights and activations live in LDS), so the context survives it without spilling
   const int lane0_ = (int)(threadIdx.x & 63u);
   const int wave_ = (int)(threadIdx.x >> 6);
   const int e4_ = ((int)blockIdx.x * 4 + wave_) * 4;            // the wave's first robot
-  const int rl_ = lane0_ >> 4;                                   // this lane's robot inside the wave
-  int env0_ = e4_ + rl_;
-  const int leg0_ = (lane0_ >> 2) & 3;
-  const bool valid0_ = (env0_ < P.n_envs) && ((lane0_ & 3) == 0);
-  if (env0_ >= P.n_envs) env0_ = P.n_envs - 1;
+  const LaneCtx lc = irrl_lane_ctx(P, (int)blockIdx.x * 4 + wave_, lane0_);
   irrl_plain::EnvLane L;
-  irrl_plain::load_lane(P, S, env0_, leg0_, L, true);
+  irrl_plain::load_lane(P, S, lc.env, lc.leg, L, true);
   // Round 5: the policy of a wave's four robots is that wave's own work (mlp_policy_wave_body): no workgroup barrier in the step loop, no wait
   // for the slowest of the four env waves in every step -- and what a wave hands from its env step to its policy step and back (observations,
   // reward, done flag; clipped actions) goes through its LDS scratch next to the stores to memory, so no load inside the loop waits for a store.
   float *ws = wsl[wave_];
   {   // the state of things in front of step 0, from memory: observations, done flags, the last reward
     const int n = ((a.N - e4_ < 4) ? a.N - e4_ : 4);
-    for (int i = lane0_; i < 4 * 35; i += 64) ws[MlpWaveLds<64>::X + i] = (i < n * 35) ? a.obs[(size_t)e4_ * 35 + i] : 0.0f;
+    for (int i = lane0_; i < 4 * 35; i += 64) ws[LAY::X + i] = (i < n * 35) ? a.obs[(size_t)e4_ * 35 + i] : 0.0f;
     if (lane0_ < 4) {
       const int e = (e4_ + lane0_ < a.N) ? e4_ + lane0_ : a.N - 1;
-      ws[MlpWaveLds<64>::DON + lane0_] = a.dones[e] ? 1.0f : 0.0f;
-      ws[MlpWaveLds<64>::REW + lane0_] = a.prev_reward ? a.prev_reward[e] : 0.0f;
+      ws[LAY::DON + lane0_] = a.dones[e] ? 1.0f : 0.0f;
+      ws[LAY::REW + lane0_] = a.prev_reward ? a.prev_reward[e] : 0.0f;
     }
   }
   __syncthreads();
   for (int k = 0; k < steps; k++) {
     int lane = lane0_;
     asm volatile("" : "+v"(lane));     // (see irrl_rollout_persistent_kernel_l16: keeps the per-lane addresses inside the loop)
-    PolicyStepArgs ak = IRRL_PARAMS_REFRESH(a);
-    ak.row = row0 + k; ak.rng_step = rng0 + k;
-    ak.noise = noise0 ? noise0 + (size_t)k * noise_stride : nullptr;
+    const PolicyStepArgs ak = base.at(a, k);
     mlp_policy_wave_body<64, true, true>(ak, e4_, ws, wl, head_w, lane);
     PS_WAVE_SYNC();    // this wave's clipped actions are in its scratch
     {
-      int env_ = env0_;
+      int env_ = lc.env;
       asm volatile("" : "+v"(env_));
       if (k > 0) irrl_plain::lane_carry(L);
       irrl_plain::ActionRegs act;
 #pragma unroll
-      for (int j = 0; j < 3; j++) act.a[j] = ws[MlpWaveLds<64>::ACT + rl_ * 12 + leg0_ * 3 + j];
+      for (int j = 0; j < 3; j++) act.a[j] = ws[LAY::ACT + lc.rw * 12 + lc.leg * 3 + j];
       irrl_plain::step_compute<IRRL_RULE_SHIPPED, irrl_plain::NoStepHook>(
-          IRRL_PARAMS_REFRESH(P), L, env_, leg0_, valid0_, act, ob, reward, done, extra, irrl_plain::NoStepHook(),
+          IRRL_PARAMS_REFRESH(P), L, env_, lc.leg, lc.valid, act, ob, reward, done, extra, irrl_plain::NoStepHook(),
           [&](const irrl_plain::EnvLane &Lf, float rew, bool dn) {
             // (inside the epilogue's sub-lane-0 region) the scaled observation row, the reward and the done flag once more, into the scratch
-            irrl_plain::observe_write(P, rl_, leg0_, valid0_, Lf, ws + MlpWaveLds<64>::X);
-            if (valid0_ && leg0_ == 0) { ws[MlpWaveLds<64>::REW + rl_] = rew; ws[MlpWaveLds<64>::DON + rl_] = dn ? 1.0f : 0.0f; }
+            irrl_plain::observe_write(P, lc.rw, lc.leg, lc.valid, Lf, ws + LAY::X);
+            if (lc.valid && lc.leg == 0) { ws[LAY::REW + lc.rw] = rew; ws[LAY::DON + lc.rw] = dn ? 1.0f : 0.0f; }
           });
     }
     PS_WAVE_SYNC();    // observations / done flags / rewards of step k are in the scratch: the wave's next policy step reads them
   }
-  if (steps > 0) {
-    IRRL_SUB0_ONLY_BEGIN
-    irrl_plain::store_lane(IRRL_PARAMS_REFRESH(P), IRRL_PARAMS_REFRESH(S), env0_, leg0_, valid0_, L, P.randomize_per_episode != 0);
-    IRRL_SUB0_ONLY_END
-  }
+  if (steps > 0) irrl_store_lane_back(P, S, lc.env, lc.leg, lc.valid, L);
 }
 #endif
 
@@ -499,46 +498,31 @@ __device__ __forceinline__ void irrl_steps_persistent_body(const EnvParams &P_, 
   // out_rows != 0: the outputs are [count, N, .] tables and step k fills row k -- the trajectory `count` step() calls of the reference
   // would have returned (VEC:268-278, RaisimGymVecEnv.py:26-52); 0: [N, .] arrays every step overwrites (the last step's survive)
   const size_t orow = out_rows ? (size_t)P.n_envs : (size_t)0;
-  const int lane0_ = (int)(threadIdx.x & 63u);
-#if IRRL_LANES_PER_ROBOT == 16
-  int env0_ = (blk * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6)) * 4 + (lane0_ >> 4);
-  const int leg0_ = (lane0_ >> 2) & 3;
-  const bool valid0_ = (env0_ < P.n_envs) && ((lane0_ & 3) == 0);
-  if (env0_ >= P.n_envs) env0_ = P.n_envs - 1;
-#else
-  int env0_ = (blk * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6)) * 16 + (lane0_ >> 2);
-  const int leg0_ = lane0_ & 3;
-  const bool valid0_ = env0_ < P.n_envs;
-  if (!valid0_) env0_ = P.n_envs - 1;
-#endif
+  const LaneCtx lc = irrl_lane_ctx(P, blk * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6), (int)(threadIdx.x & 63u));
   irrl_plain::EnvLane L;
-  irrl_plain::load_lane(P, S, env0_, leg0_, L, true);
+  irrl_plain::load_lane(P, S, lc.env, lc.leg, L, true);
   // the action row of step k + 1 is requested while step k runs (three words per lane): a step does not start behind that round trip either
   irrl_plain::ActionRegs act_next;
   {
-    const float *a0 = action_rows + row * (size_t)(first_row % n_rows) + (size_t)env0_ * 12 + leg0_ * 3;
+    const float *a0 = action_rows + row * (size_t)(first_row % n_rows) + (size_t)lc.env * 12 + lc.leg * 3;
     act_next.a[0] = a0[0]; act_next.a[1] = a0[1]; act_next.a[2] = a0[2];
   }
   for (int k = 0; k < count; k++) {
     // the lane's robot made opaque once per iteration: the per-lane addresses of the action row and of the output rows are then computed
     // inside the loop (hoisted, they are dozens of 64-bit values that spill)
-    int env_ = env0_;
+    int env_ = lc.env;
     asm volatile("" : "+v"(env_));
     if (k > 0) irrl_plain::lane_carry(L);
     const irrl_plain::ActionRegs act = act_next;
     {
       const int kn = (k + 1 < count) ? k + 1 : k;      // (behind the last step: that step's own row once more)
-      const float *an = action_rows + row * (size_t)((first_row + kn) % n_rows) + (size_t)env_ * 12 + leg0_ * 3;
+      const float *an = action_rows + row * (size_t)((first_row + kn) % n_rows) + (size_t)env_ * 12 + lc.leg * 3;
       act_next.a[0] = an[0]; act_next.a[1] = an[1]; act_next.a[2] = an[2];
     }
     irrl_plain::step_compute<RULE, irrl_plain::NoStepHook, irrl_plain::NoStepTail, irrl_plain::ActionRegs>(
-        IRRL_PARAMS_REFRESH(P), L, env_, leg0_, valid0_, act, ob + orow * 35 * (size_t)k, reward + orow * (size_t)k, done + orow * (size_t)k, extra + orow * 6 * (size_t)k);
+        IRRL_PARAMS_REFRESH(P), L, env_, lc.leg, lc.valid, act, ob + orow * 35 * (size_t)k, reward + orow * (size_t)k, done + orow * (size_t)k, extra + orow * 6 * (size_t)k);
   }
-  if (count > 0) {
-    IRRL_SUB0_ONLY_BEGIN
-    irrl_plain::store_lane(IRRL_PARAMS_REFRESH(P), IRRL_PARAMS_REFRESH(S), env0_, leg0_, valid0_, L, P.randomize_per_episode != 0);
-    IRRL_SUB0_ONLY_END
-  }
+  if (count > 0) irrl_store_lane_back(P, S, lc.env, lc.leg, lc.valid, L);
 }
 extern "C" {
 // the multi-step kernel once with the run-time terrain test (rough ground) and once with flat ground compiled in (the launcher picks)
@@ -556,25 +540,25 @@ IRRL_K(irrl_steps_persistent_kernel_flat)(EnvParams P_, EnvState S_, const float
 __global__ void IRRL_ENV_BOUNDS IRRL_K(irrl_init_kernel)(EnvParams P_, EnvState S_) {
   IRRL_BIND_ARGS
   IRRL_LANE_PROLOGUE
-  irrl::init_body(P, S, env_, leg_, valid_);
+  irrl::init_body(P, S, lc.env, lc.leg, lc.valid);
 }
 
 __global__ void IRRL_ENV_BOUNDS IRRL_K(irrl_reset_kernel)(EnvParams P_, EnvState S_, float *ob) {
   IRRL_BIND_ARGS
   IRRL_LANE_PROLOGUE
-  irrl::reset_body(P, S, env_, leg_, valid_, ob);
+  irrl::reset_body(P, S, lc.env, lc.leg, lc.valid, ob);
 }
 
 __global__ void IRRL_ENV_BOUNDS IRRL_K(irrl_observe_kernel)(EnvParams P_, EnvState S_, float *ob) {
   IRRL_BIND_ARGS
   IRRL_LANE_PROLOGUE
-  irrl::observe_body(P, S, env_, leg_, valid_, ob);
+  irrl::observe_body(P, S, lc.env, lc.leg, lc.valid, ob);
 }
 
 __global__ void IRRL_ENV_BOUNDS IRRL_K(irrl_probe_kernel)(EnvParams P_, EnvState S_, float *minv, float *nonlin) {
   IRRL_BIND_ARGS
   IRRL_LANE_PROLOGUE
-  irrl::dynamics_probe_body(P, S, env_, leg_, valid_, minv, nonlin);
+  irrl::dynamics_probe_body(P, S, lc.env, lc.leg, lc.valid, minv, nonlin);
 }
 
 #if IRRL_LANES_PER_ROBOT == 16

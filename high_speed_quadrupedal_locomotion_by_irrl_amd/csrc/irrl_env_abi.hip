@@ -13,33 +13,7 @@
 #include "mlp_bf16_pc.hpp"
 #include "ppo_optim.hpp"
 
-// The env kernels are compiled in two lane layouts from the same source (csrc/env_kernels.hip, see build.py):
-//   _l16  16 lanes per robot (lanes_hip16.hpp): 4 robots per wave -- fills all 1024 SIMDs at 4096 robots, shortest step
-//   _l4    4 lanes per robot (lanes_hip.hpp):  16 robots per wave -- 2.3x fewer instructions per robot, the better
-//          throughput once the pool is large enough to occupy the chip on its own
-//   _l4w2  the same, compiled for two waves per SIMD (256 registers each): pools with more 4-lane waves than SIMDs (> 16 384 robots)
-#define IRRL_DECLARE_KERNELS(sfx)                                                                                            \
-  extern "C" __global__ void irrl_step_kernel##sfx(EnvParams, EnvState, const float *, float *, float *, uint8_t *, float *);   \
-  extern "C" __global__ void irrl_step_kernel_dir##sfx(EnvParams, EnvState, const float *, float *, float *, uint8_t *, float *); \
-  extern "C" __global__ void irrl_step_kernel_md##sfx(EnvParams, EnvState, const float *, float *, float *, uint8_t *, float *); \
-  extern "C" __global__ void irrl_step_kernel_crutial##sfx(EnvParams, EnvState, const float *, float *, float *, uint8_t *, float *); \
-  extern "C" __global__ void irrl_step_kernel_crutial_md##sfx(EnvParams, EnvState, const float *, float *, float *, uint8_t *, float *); \
-  extern "C" __global__ void irrl_steps_persistent_kernel##sfx(EnvParams, EnvState, const float *, int, int, int, float *, float *, uint8_t *, float *, int); \
-  extern "C" __global__ void irrl_steps_persistent_kernel_flat##sfx(EnvParams, EnvState, const float *, int, int, int, float *, float *, uint8_t *, float *, int); \
-  extern "C" __global__ void irrl_step_kernel_flat##sfx(EnvParams, EnvState, const float *, float *, float *, uint8_t *, float *);   \
-  extern "C" __global__ void irrl_init_kernel##sfx(EnvParams, EnvState);                                                       \
-  extern "C" __global__ void irrl_reset_kernel##sfx(EnvParams, EnvState, float *);                                             \
-  extern "C" __global__ void irrl_observe_kernel##sfx(EnvParams, EnvState, float *);                                           \
-  extern "C" __global__ void irrl_probe_kernel##sfx(EnvParams, EnvState, float *, float *);
-IRRL_DECLARE_KERNELS(_l16)
-IRRL_DECLARE_KERNELS(_l4)
-IRRL_DECLARE_KERNELS(_l4w2)
-extern "C" __global__ void irrl_terminal_kernel(EnvParams, EnvState, uint8_t *);
-extern "C" __global__ void irrl_step_policy_kernel_l16(EnvParams, EnvState, const float *, float *, float *, uint8_t *, float *, PolicyStepArgs);
-extern "C" __global__ void irrl_rollout_persistent_kernel_l16(EnvParams, EnvState, float *, float *, uint8_t *, float *, PolicyStepArgs, int);
-extern "C" __global__ void irrl_rollout_persistent_actor_kernel_l16(EnvParams, EnvState, float *, float *, uint8_t *, float *, PolicyStepArgs, int);
-extern "C" __global__ void irrl_rollout_persistent_actor_wave_kernel_l16(EnvParams, EnvState, float *, float *, uint8_t *, float *, PolicyStepArgs, int);
-extern "C" __global__ void irrl_rollout_persistent_mlp_kernel_l16(EnvParams, EnvState, float *, float *, uint8_t *, float *, PolicyStepArgs, int);
+#include "env_kernels_decl.h"   // the env kernels (csrc/env_kernels.hip), declared once for their definitions and for the launches below
 
 #include "irrl_config.hpp"
 #include "irrl_state_pool.hpp"
@@ -122,11 +96,14 @@ static int pick_waves2(int n_envs, int device) {
   if (e) { int v = atoi(e); if (v == 1 || v == 2) return v == 2; }
   return (n_envs + 15) / 16 > device_simds(device);
 }
-#define IRRL_LAUNCH(h, name, grid, ...)                                                                                   \
-  do {                                                                                                                    \
-    if ((h)->lanes == 16) hipLaunchKernelGGL(name##_l16, grid, quad_block(), 0, (h)->stream, __VA_ARGS__);                 \
-    else if ((h)->waves2) hipLaunchKernelGGL(name##_l4w2, grid, quad_block(), 0, (h)->stream, __VA_ARGS__);                \
-    else hipLaunchKernelGGL(name##_l4, grid, quad_block(), 0, (h)->stream, __VA_ARGS__);                                   \
+// the pool's lane layout as an index: _l16, _l4, _l4w2 (the order of IRRL_PER_LAYOUT)
+static inline int layout_index(const irrl_env *h) { return h->lanes == 16 ? 0 : h->waves2 ? 2 : 1; }
+#define IRRL_PER_LAYOUT(name) { name##_l16, name##_l4, name##_l4w2 }
+// a lane kernel that exists once per layout (init / reset / observe / probe)
+#define IRRL_LAUNCH(h, name, grid, ...)                                                                               \
+  do {                                                                                                                \
+    static const decltype(&name##_l16) k_[3] = IRRL_PER_LAYOUT(name);                                                  \
+    hipLaunchKernelGGL(k_[layout_index(h)], grid, quad_block(), 0, (h)->stream, __VA_ARGS__);                         \
   } while (0)
 
 // the step kernel: one instantiation per (Crutial, per-contact rule) -- env_kernels.hip -- and, for the default pool kind (no meteorite, published
@@ -146,18 +123,51 @@ static inline bool shipped_solver(const irrl_env *h) {
   return h->P.contact_jacobi != 0 && h->P.contact_exit != 0 && h->P.contact_tol > 0.0f && h->P.contact_iters == IRRL_SHIPPED_SWEEP_CAP &&
          h->P.loop_count == IRRL_SHIPPED_SUBSTEPS;
 }
-#define IRRL_LAUNCH_STEP(h, grid, ...)                                                                                      \
-  do {                                                                                                                    \
-    if ((h)->P.crutial) {                                                                                                   \
-      if ((h)->P.contact_rule) IRRL_LAUNCH(h, irrl_step_kernel_crutial_md, grid, __VA_ARGS__);                               \
-      else IRRL_LAUNCH(h, irrl_step_kernel_crutial, grid, __VA_ARGS__);                                                      \
-    } else if ((h)->P.contact_rule) {                                                                                       \
-      if (shipped_solver(h) && flat_kernels(h)) IRRL_LAUNCH(h, irrl_step_kernel_flat, grid, __VA_ARGS__);                   \
-      else if (shipped_solver(h)) IRRL_LAUNCH(h, irrl_step_kernel, grid, __VA_ARGS__);                                      \
-      else IRRL_LAUNCH(h, irrl_step_kernel_md, grid, __VA_ARGS__);                                                          \
-    }                                                                                                                       \
-    else IRRL_LAUNCH(h, irrl_step_kernel_dir, grid, __VA_ARGS__);                                                            \
-  } while (0)
+// WHICH STEP KERNEL A POOL RUNS: the one place that decides it (read per launch: the setters change loop_count)
+enum StepVariant { SV_CRUTIAL, SV_CRUTIAL_MD, SV_DIR, SV_MD, SV_SHIPPED, SV_SHIPPED_FLAT, SV_COUNT };
+static StepVariant step_variant(const irrl_env *h) {
+  if (h->P.crutial) return h->P.contact_rule ? SV_CRUTIAL_MD : SV_CRUTIAL;
+  if (!h->P.contact_rule) return SV_DIR;
+  if (!shipped_solver(h)) return SV_MD;
+  return flat_kernels(h) ? SV_SHIPPED_FLAT : SV_SHIPPED;
+}
+// the multi-step kernel and the rollout kernels (env step + policy in one launch; 16-lane layout only) exist for the shipped variants alone
+static inline bool persistent_kernels(const irrl_env *h) { const StepVariant v = step_variant(h); return v == SV_SHIPPED || v == SV_SHIPPED_FLAT; }
+static inline bool rollout_kernels(const irrl_env *h) { return h->lanes == 16 && persistent_kernels(h); }
+
+typedef void (*step_kernel_t)(IRRL_STEP_KERNEL_ARGS);
+typedef void (*steps_kernel_t)(IRRL_STEPS_KERNEL_ARGS);
+typedef void (*rollout_kernel_t)(IRRL_ROLLOUT_KERNEL_ARGS);
+static const step_kernel_t kStepKernels[SV_COUNT][3] = {   // [StepVariant][layout]
+    IRRL_PER_LAYOUT(irrl_step_kernel_crutial), IRRL_PER_LAYOUT(irrl_step_kernel_crutial_md), IRRL_PER_LAYOUT(irrl_step_kernel_dir),
+    IRRL_PER_LAYOUT(irrl_step_kernel_md), IRRL_PER_LAYOUT(irrl_step_kernel), IRRL_PER_LAYOUT(irrl_step_kernel_flat)};
+static const steps_kernel_t kStepsKernels[2][3] = {IRRL_PER_LAYOUT(irrl_steps_persistent_kernel), IRRL_PER_LAYOUT(irrl_steps_persistent_kernel_flat)};   // [flat][layout]
+// one env.step of the first P.n_envs robots of the pool (P: h->P, or a copy with fewer robots)
+static void launch_step(irrl_env *h, const EnvParams &P, const float *action, float *ob, float *reward, uint8_t *done, float *extra) {
+  hipLaunchKernelGGL(kStepKernels[step_variant(h)][layout_index(h)], lane_grid(h, P.n_envs), quad_block(), 0, h->stream, P, h->S, action, ob, reward, done, extra);
+}
+// a rollout kernel: 256-thread workgroups of 16 robots
+static void launch_rollout(irrl_env *h, rollout_kernel_t k, float *obs, float *env_reward, uint8_t *dones, float *env_extra, const PolicyStepArgs &a, int steps) {
+  hipLaunchKernelGGL(k, dim3((h->P.n_envs + 15) / 16), dim3(256), 0, h->stream, h->P, h->S, obs, env_reward, dones, env_extra, a, steps);
+}
+// the policy's arguments of one rollout step (lstm: 12 weight arrays and the recurrent state; mlp: 8 and none)
+static PolicyStepArgs policy_step_args(int n, int ob_dim, int act_dim, float *obs, uint8_t *dones, const float *states_in, float *states_out,
+                                       const float *const *w, int n_w, const float *pi_w, const float *pi_b, const float *vf_w, const float *vf_b,
+                                       const float *logstd, const float *noise, int rng_on, unsigned rng_seed, long long rng_step, const long long *rng_base,
+                                       int env_id_offset, float *action, float *clipped, float *value, float *neglogp, long long row, float *mb_obs,
+                                       float *mb_actions, float *mb_values, float *mb_neglogp, uint8_t *mb_dones, float *mb_rewards, float *env_reward) {
+  PolicyStepArgs a;
+  a.obs = obs; a.dones = dones; a.states_in = states_in; a.states_out = states_out;
+  for (int i = 0; i < 12; i++) a.w[i] = i < n_w ? w[i] : nullptr;
+  a.pi_w = pi_w; a.pi_b = pi_b; a.vf_w = vf_w; a.vf_b = vf_b; a.logstd = logstd; a.noise = noise;
+  a.action = action; a.clipped = clipped; a.value = value; a.neglogp = neglogp;
+  a.row = row; a.rng_base = rng_base;
+  a.mb_obs = mb_obs; a.mb_actions = mb_actions; a.mb_values = mb_values; a.mb_neglogp = mb_neglogp; a.mb_dones = mb_dones;
+  a.mb_rewards = mb_rewards; a.prev_reward = mb_rewards ? env_reward : nullptr;
+  a.rng_step = rng_step; a.rng_seed = rng_seed; a.rng_on = rng_on; a.env_id_offset = (unsigned)env_id_offset;
+  a.N = n; a.ob_dim = ob_dim; a.act_dim = act_dim;
+  return a;
+}
 
 extern "C" {
 
@@ -300,24 +310,28 @@ static int need_init(irrl_env *h) {
 int irrl_env_step(irrl_env *h, const float *action, float *ob, float *reward, uint8_t *done, float *extra) {
   if (need_init(h)) return 1;
   if (use_device(h)) return 1;
-  IRRL_LAUNCH_STEP(h, lane_grid(h, h->P.n_envs), h->P, h->S, action, ob, reward, done, extra);
+  launch_step(h, h->P, action, ob, reward, done, extra);
   HIP_TRY(hipGetLastError());
   return 0;
 }
 
 // `count` steps from an action table, one launch per step.  out_rows != 0: ob / reward / done / extra are [count, N, .] tables and step k
 // fills row k (what `count` step() calls of the reference return, VEC:268-278 / RaisimGymVecEnv.py:26-52); 0: [N, .] arrays, overwritten
-static int step_rows_impl(irrl_env *h, int count, const float *action_rows, int n_rows, int first_row, float *ob, float *reward,
-                          uint8_t *done, float *extra, int out_rows, const char *who) {
+static int step_rows_check(irrl_env *h, int count, const float *action_rows, int n_rows, int first_row, float *ob, float *reward, uint8_t *done, float *extra,
+                           const char *who) {
   if (need_init(h)) return 1;
   if (count < 0 || n_rows <= 0 || first_row < 0) { g_err = std::string(who) + ": count >= 0, n_rows > 0, first_row >= 0"; return 1; }
   if (!action_rows || !ob || !reward || !done || !extra) { g_err = std::string(who) + ": NULL argument"; return 1; }
+  return 0;
+}
+static int step_rows_impl(irrl_env *h, int count, const float *action_rows, int n_rows, int first_row, float *ob, float *reward,
+                          uint8_t *done, float *extra, int out_rows, const char *who) {
+  if (step_rows_check(h, count, action_rows, n_rows, first_row, ob, reward, done, extra, who)) return 1;
   if (use_device(h)) return 1;
   const size_t row = (size_t)h->P.n_envs * 12, orow = out_rows ? (size_t)h->P.n_envs : (size_t)0;
   for (int k = 0; k < count; k++) {
     const float *action = action_rows + row * (size_t)((first_row + k) % n_rows);
-    IRRL_LAUNCH_STEP(h, lane_grid(h, h->P.n_envs), h->P, h->S, action, ob + orow * 35 * (size_t)k, reward + orow * (size_t)k, done + orow * (size_t)k,
-                     extra + orow * 6 * (size_t)k);
+    launch_step(h, h->P, action, ob + orow * 35 * (size_t)k, reward + orow * (size_t)k, done + orow * (size_t)k, extra + orow * 6 * (size_t)k);
   }
   HIP_TRY(hipGetLastError());
   return 0;
@@ -326,15 +340,12 @@ static int step_rows_impl(irrl_env *h, int count, const float *action_rows, int 
 // grid-wide boundary between steps); pools the kernel is not instantiated for (meteorite, first contact rule) take the launch-per-step path
 static int step_rows_persistent_impl(irrl_env *h, int count, const float *action_rows, int n_rows, int first_row, float *ob, float *reward,
                                      uint8_t *done, float *extra, int out_rows, const char *who) {
-  if (need_init(h)) return 1;
-  if (count < 0 || n_rows <= 0 || first_row < 0) { g_err = std::string(who) + ": count >= 0, n_rows > 0, first_row >= 0"; return 1; }
-  if (!action_rows || !ob || !reward || !done || !extra) { g_err = std::string(who) + ": NULL argument"; return 1; }
-  if (h->P.crutial || !h->P.contact_rule || !shipped_solver(h)) return step_rows_impl(h, count, action_rows, n_rows, first_row, ob, reward, done, extra, out_rows, who);
+  if (step_rows_check(h, count, action_rows, n_rows, first_row, ob, reward, done, extra, who)) return 1;
+  if (!persistent_kernels(h)) return step_rows_impl(h, count, action_rows, n_rows, first_row, ob, reward, done, extra, out_rows, who);
   if (use_device(h)) return 1;
-  if (count > 0) {
-    if (flat_kernels(h)) IRRL_LAUNCH(h, irrl_steps_persistent_kernel_flat, lane_grid(h, h->P.n_envs), h->P, h->S, action_rows, n_rows, first_row, count, ob, reward, done, extra, out_rows);
-    else IRRL_LAUNCH(h, irrl_steps_persistent_kernel, lane_grid(h, h->P.n_envs), h->P, h->S, action_rows, n_rows, first_row, count, ob, reward, done, extra, out_rows);
-  }
+  if (count > 0)
+    hipLaunchKernelGGL(kStepsKernels[flat_kernels(h)][layout_index(h)], lane_grid(h, h->P.n_envs), quad_block(), 0, h->stream, h->P, h->S, action_rows, n_rows,
+                       first_row, count, ob, reward, done, extra, out_rows);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -358,7 +369,7 @@ int irrl_env_step_rows_persistent_out(irrl_env *h, int count, const float *actio
 
 // which `fuse` modes of irrl_lstm_rollout exist for THIS pool and network: 1 = the mode runs as described, 0 = it does not (fuse 1 / 2 then fall
 // back to two launches per step inside the call; fuse 3 is refused -- its caller must evaluate the critic itself, so it has to know beforehand)
-static bool rollout_one_tile(const irrl_env *h, int hid) { return h->lanes == 16 && !h->P.crutial && h->P.contact_rule && shipped_solver(h) && hid == 48; }
+static bool rollout_one_tile(const irrl_env *h, int hid) { return rollout_kernels(h) && hid == 48; }
 int irrl_lstm_rollout_supports(irrl_env *h, int hid, int fuse) {
   if (!h) { g_err = "irrl_lstm_rollout_supports: NULL handle"; return -1; }
   if (fuse == 0) return 1;
@@ -385,6 +396,12 @@ int irrl_lstm_rollout(irrl_env *h, int steps, int hid, int ob_dim, int act_dim, 
                                  logstd, noise_at(k), rng_on, rng_seed, rng_step + k, rng_base, env_id_offset, action, clipped, value, neglogp, row + k, mb_obs,
                                  mb_actions, mb_values, mb_neglogp, mb_dones, mb_rewards, env_reward, hip_stream);
   };
+  // ... and its arguments for a kernel that runs it behind the env step (`first`: the recurrent state still comes from states_in)
+  auto policy_args = [&](int k, bool first) {
+    return policy_step_args(n, ob_dim, act_dim, obs, dones, first ? states_in : states_out, states_out, lstm_w, 12, pi_w, pi_b, vf_w, vf_b, logstd, noise_at(k), rng_on,
+                            rng_seed, rng_step + k, rng_base, env_id_offset, action, clipped, value, neglogp, row + k, mb_obs, mb_actions, mb_values, mb_neglogp,
+                            mb_dones, mb_rewards, env_reward);
+  };
   // fuse != 0: one launch per step, env.step k together with the policy step k + 1 (16-lane layout = one MFMA M-tile per four env
   // waves, the reference's 48-unit network, pools without the meteorite).  Bit-identical to the two-launch sequence, and measured
   // SLOWER on MI355X (62.9 against 58.2 us per step at 4096 envs): kept as an option, not the default.
@@ -402,25 +419,11 @@ int irrl_lstm_rollout(irrl_env *h, int steps, int hid, int ob_dim, int act_dim, 
     for (int i = 0; i < 12; i++)
       if (!lstm_w[i]) { g_err = "irrl_lstm_rollout: the LSTM weight table has a NULL entry"; return 1; }
     if (!mb_rewards) { g_err = "irrl_lstm_rollout: the persistent path writes the reward rows (mb_rewards is mandatory)"; return 1; }
-    PolicyStepArgs a;
-    a.obs = obs; a.dones = dones; a.states_in = states_in; a.states_out = states_out;
-    for (int i = 0; i < 12; i++) a.w[i] = lstm_w[i];
-    a.pi_w = pi_w; a.pi_b = pi_b; a.vf_w = vf_w; a.vf_b = vf_b; a.logstd = logstd; a.noise = noise;
-    a.action = action; a.clipped = clipped; a.value = value; a.neglogp = neglogp;
-    a.row = row; a.rng_base = rng_base;
-    a.mb_obs = mb_obs; a.mb_actions = mb_actions; a.mb_values = mb_values; a.mb_neglogp = mb_neglogp; a.mb_dones = mb_dones;
-    a.mb_rewards = mb_rewards; a.prev_reward = mb_rewards ? env_reward : nullptr;
-    a.rng_step = rng_step; a.rng_seed = rng_seed; a.rng_on = rng_on; a.env_id_offset = (unsigned)env_id_offset;
-    a.N = n; a.ob_dim = ob_dim; a.act_dim = act_dim;
-    if (fuse == 3) {
-      // the actor as each wave's own work (round 5, second half); IRRL_ACTOR_WAVES=0: the workgroup-wide actor step (same buffers, bit for bit)
-      const char *aw = getenv("IRRL_ACTOR_WAVES");
-      if (aw && aw[0] == '0')
-        hipLaunchKernelGGL(irrl_rollout_persistent_actor_kernel_l16, dim3((n + 15) / 16), dim3(256), 0, h->stream, h->P, h->S, obs, env_reward, dones, env_extra, a, steps);
-      else
-        hipLaunchKernelGGL(irrl_rollout_persistent_actor_wave_kernel_l16, dim3((n + 15) / 16), dim3(256), 0, h->stream, h->P, h->S, obs, env_reward, dones, env_extra, a, steps);
-    } else
-      hipLaunchKernelGGL(irrl_rollout_persistent_kernel_l16, dim3((n + 15) / 16), dim3(256), 0, h->stream, h->P, h->S, obs, env_reward, dones, env_extra, a, steps);
+    // fuse == 3: the actor as each wave's own work (round 5, second half); IRRL_ACTOR_WAVES=0: the workgroup-wide actor step (same buffers, bit for bit)
+    const char *aw = getenv("IRRL_ACTOR_WAVES");
+    const rollout_kernel_t k = fuse != 3 ? irrl_rollout_persistent_kernel_l16
+                               : (aw && aw[0] == '0') ? irrl_rollout_persistent_actor_kernel_l16 : irrl_rollout_persistent_actor_wave_kernel_l16;
+    launch_rollout(h, k, obs, env_reward, dones, env_extra, policy_args(0, true), steps);
     HIP_TRY(hipGetLastError());
     return 0;
   }
@@ -429,20 +432,10 @@ int irrl_lstm_rollout(irrl_env *h, int steps, int hid, int ob_dim, int act_dim, 
   if (steps > 0 && policy(0) != 0) { g_err = "irrl_lstm_rollout: policy step refused its arguments"; return 1; }
   for (int k = 0; k < steps; k++) {
     if (fused && k + 1 < steps) {
-      PolicyStepArgs a;
-      a.obs = obs; a.dones = dones; a.states_in = states_out; a.states_out = states_out;
-      for (int i = 0; i < 12; i++) a.w[i] = lstm_w[i];
-      a.pi_w = pi_w; a.pi_b = pi_b; a.vf_w = vf_w; a.vf_b = vf_b; a.logstd = logstd; a.noise = noise_at(k + 1);
-      a.action = action; a.clipped = clipped; a.value = value; a.neglogp = neglogp;
-      a.row = row + k + 1; a.rng_base = rng_base;
-      a.mb_obs = mb_obs; a.mb_actions = mb_actions; a.mb_values = mb_values; a.mb_neglogp = mb_neglogp; a.mb_dones = mb_dones;
-      a.mb_rewards = mb_rewards; a.prev_reward = mb_rewards ? env_reward : nullptr;
-      a.rng_step = rng_step + k + 1; a.rng_seed = rng_seed; a.rng_on = rng_on; a.env_id_offset = (unsigned)env_id_offset;
-      a.N = n; a.ob_dim = ob_dim; a.act_dim = act_dim;
       hipLaunchKernelGGL(irrl_step_policy_kernel_l16, dim3((n + 15) / 16), dim3(256), 0, h->stream, h->P, h->S, (const float *)clipped, obs,
-                         env_reward, dones, env_extra, a);
+                         env_reward, dones, env_extra, policy_args(k + 1, false));
     } else {
-      IRRL_LAUNCH_STEP(h, lane_grid(h, n), h->P, h->S, (const float *)clipped, obs, env_reward, dones, env_extra);
+      launch_step(h, h->P, (const float *)clipped, obs, env_reward, dones, env_extra);
       if (k + 1 < steps && policy(k + 1) != 0) { g_err = "irrl_lstm_rollout: policy step refused its arguments"; return 1; }
     }
   }
@@ -470,20 +463,12 @@ int irrl_mlp_rollout(irrl_env *h, int steps, int hid, int ob_dim, int act_dim, f
   h->stream = (hipStream_t)hip_stream;
   const int n = h->P.n_envs;
   auto noise_at = [&](int k) { return noise ? noise + (size_t)k * (size_t)n * (size_t)act_dim : nullptr; };
-  const bool one_tile = h->lanes == 16 && !h->P.crutial && h->P.contact_rule && shipped_solver(h);
-  if (fuse == 2 && one_tile && steps > 0) {
+  if (fuse == 2 && rollout_kernels(h) && steps > 0) {
     if (!mb_rewards) { g_err = "irrl_mlp_rollout: the persistent path writes the reward rows (mb_rewards is mandatory)"; return 1; }
-    PolicyStepArgs a;
-    a.obs = obs; a.dones = dones; a.states_in = nullptr; a.states_out = nullptr;
-    for (int i = 0; i < 12; i++) a.w[i] = i < 8 ? mlp_w[i] : nullptr;
-    a.pi_w = pi_w; a.pi_b = pi_b; a.vf_w = vf_w; a.vf_b = vf_b; a.logstd = logstd; a.noise = noise;
-    a.action = action; a.clipped = clipped; a.value = value; a.neglogp = neglogp;
-    a.row = row; a.rng_base = rng_base;
-    a.mb_obs = mb_obs; a.mb_actions = mb_actions; a.mb_values = mb_values; a.mb_neglogp = mb_neglogp; a.mb_dones = mb_dones;
-    a.mb_rewards = mb_rewards; a.prev_reward = env_reward;
-    a.rng_step = rng_step; a.rng_seed = rng_seed; a.rng_on = rng_on; a.env_id_offset = (unsigned)env_id_offset;
-    a.N = n; a.ob_dim = ob_dim; a.act_dim = act_dim;
-    hipLaunchKernelGGL(irrl_rollout_persistent_mlp_kernel_l16, dim3((n + 15) / 16), dim3(256), 0, h->stream, h->P, h->S, obs, env_reward, dones, env_extra, a, steps);
+    launch_rollout(h, irrl_rollout_persistent_mlp_kernel_l16, obs, env_reward, dones, env_extra,
+                   policy_step_args(n, ob_dim, act_dim, obs, dones, nullptr, nullptr, mlp_w, 8, pi_w, pi_b, vf_w, vf_b, logstd, noise, rng_on, rng_seed, rng_step, rng_base,
+                                    env_id_offset, action, clipped, value, neglogp, row, mb_obs, mb_actions, mb_values, mb_neglogp, mb_dones, mb_rewards, env_reward),
+                   steps);
     HIP_TRY(hipGetLastError());
     return 0;
   }
@@ -491,7 +476,7 @@ int irrl_mlp_rollout(irrl_env *h, int steps, int hid, int ob_dim, int act_dim, f
     if (irrl_mlp_policy_step(hid, ob_dim, act_dim, n, obs, dones, mlp_w, pi_w, pi_b, vf_w, vf_b, logstd, noise_at(k), rng_on, rng_seed, rng_step + k, rng_base,
                              env_id_offset, action, clipped, value, neglogp, row + k, mb_obs, mb_actions, mb_values, mb_neglogp, mb_dones, mb_rewards, env_reward,
                              hip_stream) != 0) { g_err = "irrl_mlp_rollout: policy step refused its arguments"; return 1; }
-    IRRL_LAUNCH_STEP(h, lane_grid(h, n), h->P, h->S, (const float *)clipped, obs, env_reward, dones, env_extra);
+    launch_step(h, h->P, (const float *)clipped, obs, env_reward, dones, env_extra);
   }
   HIP_TRY(hipGetLastError());
   return 0;
@@ -518,7 +503,7 @@ static int step_host_impl(irrl_env *h, int n_step, const float *action, float *o
   HIP_TRY(hipMemcpyAsync(h->d_action, pa, n * 12 * 4, hipMemcpyHostToDevice, h->stream));
   EnvParams P = h->P;
   P.n_envs = n_step;
-  IRRL_LAUNCH_STEP(h, lane_grid(h, n_step), P, h->S, (const float *)h->d_action, h->d_ob, h->d_reward, h->d_done, h->d_extra);
+  launch_step(h, P, (const float *)h->d_action, h->d_ob, h->d_reward, h->d_done, h->d_extra);
   HIP_TRY(hipGetLastError());
   if (n_step == h->P.n_envs) {
     // device outputs and their pinned staging are laid out alike (ob | reward | extra | done): one copy
@@ -901,6 +886,16 @@ int irrl_ppo_heads_loss(size_t M, int act_dim, int hid, const float *h_pi, const
 }
 
 // ---- MlpPolicy: gradients of one PPO2 minibatch, one launch per network (kernel: csrc/mlp_update.hpp) ----
+// the samples as five arrays (rec NULL) or as packed records (the five arrays NULL)
+static MlpUpdateArgs mlp_update_args(size_t n, const int64_t *idx, const float *obs, const float *actions, const float *returns, const float *old_values,
+                                     const float *old_neglogp, const float *rec, const float *w1, const float *b1, const float *w2, const float *b2,
+                                     const float *w3, const float *b3, const float *logstd, const float *adv_stats, float cliprange, float vf_coef, float *partials) {
+  MlpUpdateArgs a;
+  a.n = n; a.idx = idx; a.obs = obs; a.actions = actions; a.returns = returns; a.old_values = old_values; a.old_neglogp = old_neglogp; a.rec = rec;
+  a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.w3 = w3; a.b3 = b3; a.logstd = logstd; a.adv_stats = adv_stats;
+  a.cliprange = cliprange; a.vf_coef = vf_coef; a.inv_n = 1.0f / (float)n; a.partials = partials;
+  return a;
+}
 int irrl_mlp_ppo_grads(int kind, size_t n, const int64_t *idx, int ob_dim, int hid, int act_dim, const float *obs, const float *actions,
                        const float *returns, const float *old_values, const float *old_neglogp, const float *w1, const float *b1, const float *w2,
                        const float *b2, const float *w3, const float *b3, const float *logstd, const float *adv_stats, float cliprange, float vf_coef,
@@ -908,10 +903,7 @@ int irrl_mlp_ppo_grads(int kind, size_t n, const int64_t *idx, int ob_dim, int h
   if (n == 0 || n_blocks <= 0) { g_err = "irrl_mlp_ppo_grads: empty batch"; return 1; }
   if (ob_dim != IRRL_MLP_OB || hid != IRRL_MLP_H || act_dim != 12) { g_err = "irrl_mlp_ppo_grads: built for 35 observations, [64, 64] hidden units and 12 actions"; return 1; }
   if (kind != 0 && kind != 1) { g_err = "irrl_mlp_ppo_grads: kind is 0 (policy network) or 1 (value network)"; return 1; }
-  MlpUpdateArgs a;
-  a.n = n; a.idx = idx; a.obs = obs; a.actions = actions; a.returns = returns; a.old_values = old_values; a.old_neglogp = old_neglogp; a.rec = nullptr;
-  a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.w3 = w3; a.b3 = b3; a.logstd = logstd; a.adv_stats = adv_stats;
-  a.cliprange = cliprange; a.vf_coef = vf_coef; a.inv_n = 1.0f / (float)n; a.partials = partials;
+  const MlpUpdateArgs a = mlp_update_args(n, idx, obs, actions, returns, old_values, old_neglogp, nullptr, w1, b1, w2, b2, w3, b3, logstd, adv_stats, cliprange, vf_coef, partials);
   if (kind == 0) hipLaunchKernelGGL(irrl_mlp_ppo_kernel<0>, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)hip_stream, a);
   else hipLaunchKernelGGL(irrl_mlp_ppo_kernel<1>, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)hip_stream, a);
   HIP_TRY(hipGetLastError());
@@ -929,39 +921,22 @@ static int mlp_bf16_launch(const char *who, int kind, bool use_rec, size_t n, in
   int dev_ = 0;
   if (hipGetDevice(&dev_) != hipSuccess || dev_ < 0 || dev_ >= IRRL_MAX_DEVICES) { g_err = std::string(who) + ": no current device"; return 1; }
   int &allowed = allowed_on.v[dev_];
+  // [pairs][use_rec][kind]; pairs: producer / consumer wave pairs (mlp_bf16_pc.hpp, 512 threads), else one wave per SIMD (mlp_bf16.hpp, 256 threads)
+  typedef void (*mlp_kernel_t)(const MlpUpdateArgs);
+  static const mlp_kernel_t ks[2][2][2] = {{{irrl_mlp_ppo_bf16_kernel<0, false>, irrl_mlp_ppo_bf16_kernel<1, false>}, {irrl_mlp_ppo_bf16_kernel<0, true>, irrl_mlp_ppo_bf16_kernel<1, true>}},
+                                           {{irrl_mlp_ppo_bf16_pc_kernel<0, false>, irrl_mlp_ppo_bf16_pc_kernel<1, false>}, {irrl_mlp_ppo_bf16_pc_kernel<0, true>, irrl_mlp_ppo_bf16_pc_kernel<1, true>}}};
+  const int lds_bytes[2] = {(int)mlp_bf16_lds_bytes(), (int)mlp_bf16_pc_lds_bytes()};
   if (allowed < 0) {   // the weight planes and the waves' images exceed the 64 KB a kernel gets without asking (gfx950 has 160 KB per CU)
-    const void *ks[4] = {(const void *)irrl_mlp_ppo_bf16_kernel<0, false>, (const void *)irrl_mlp_ppo_bf16_kernel<1, false>,
-                         (const void *)irrl_mlp_ppo_bf16_kernel<0, true>, (const void *)irrl_mlp_ppo_bf16_kernel<1, true>};
-    const void *kp[4] = {(const void *)irrl_mlp_ppo_bf16_pc_kernel<0, false>, (const void *)irrl_mlp_ppo_bf16_pc_kernel<1, false>,
-                         (const void *)irrl_mlp_ppo_bf16_pc_kernel<0, true>, (const void *)irrl_mlp_ppo_bf16_pc_kernel<1, true>};
     allowed = 0;
-    for (int i = 0; i < 4; i++) {
-      if (hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, mlp_bf16_lds_bytes()) != hipSuccess) allowed = 1;
-      if (hipFuncSetAttribute(kp[i], hipFuncAttributeMaxDynamicSharedMemorySize, mlp_bf16_pc_lds_bytes()) != hipSuccess) allowed = 1;
-    }
+    for (int i = 0; i < 8; i++)
+      if (hipFuncSetAttribute((const void *)ks[i >> 2][(i >> 1) & 1][i & 1], hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes[i >> 2]) != hipSuccess) allowed = 1;
   }
   if (allowed != 0) { g_err = std::string(who) + ": the device refused the kernel's LDS size"; return 1; }
   // IRRL_MLP_WAVES=4: the one-wave-per-SIMD kernel of mlp_bf16.hpp; default: producer / consumer wave pairs (mlp_bf16_pc.hpp) -- same partial rows, bit for bit
   // (read per call: the parity test runs both kernels in one process)
   const char *waves_env = getenv("IRRL_MLP_WAVES");
   const bool pairs = !(waves_env && waves_env[0] == '4');
-  const dim3 grid((unsigned)n_blocks), block(pairs ? 512 : 256);
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (pairs) {
-    if (use_rec) {
-      if (kind == 0) hipLaunchKernelGGL((irrl_mlp_ppo_bf16_pc_kernel<0, true>), grid, block, mlp_bf16_pc_lds_bytes(), st, a);
-      else hipLaunchKernelGGL((irrl_mlp_ppo_bf16_pc_kernel<1, true>), grid, block, mlp_bf16_pc_lds_bytes(), st, a);
-    } else {
-      if (kind == 0) hipLaunchKernelGGL((irrl_mlp_ppo_bf16_pc_kernel<0, false>), grid, block, mlp_bf16_pc_lds_bytes(), st, a);
-      else hipLaunchKernelGGL((irrl_mlp_ppo_bf16_pc_kernel<1, false>), grid, block, mlp_bf16_pc_lds_bytes(), st, a);
-    }
-  } else if (use_rec) {
-    if (kind == 0) hipLaunchKernelGGL((irrl_mlp_ppo_bf16_kernel<0, true>), grid, block, mlp_bf16_lds_bytes(), st, a);
-    else hipLaunchKernelGGL((irrl_mlp_ppo_bf16_kernel<1, true>), grid, block, mlp_bf16_lds_bytes(), st, a);
-  } else {
-    if (kind == 0) hipLaunchKernelGGL((irrl_mlp_ppo_bf16_kernel<0, false>), grid, block, mlp_bf16_lds_bytes(), st, a);
-    else hipLaunchKernelGGL((irrl_mlp_ppo_bf16_kernel<1, false>), grid, block, mlp_bf16_lds_bytes(), st, a);
-  }
+  hipLaunchKernelGGL(ks[pairs][use_rec][kind], dim3((unsigned)n_blocks), dim3(pairs ? 512 : 256), lds_bytes[pairs], (hipStream_t)hip_stream, a);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -971,10 +946,7 @@ int irrl_mlp_ppo_grads_bf16(int kind, size_t n, const int64_t *idx, int ob_dim, 
                             const float *b2, const float *w3, const float *b3, const float *logstd, const float *adv_stats, float cliprange, float vf_coef,
                             float *partials, int n_blocks, void *hip_stream) {
   if (ob_dim != IRRL_MLP_OB || hid != IRRL_MLP_H || act_dim != 12) { g_err = "irrl_mlp_ppo_grads_bf16: built for 35 observations, [64, 64] hidden units and 12 actions"; return 1; }
-  MlpUpdateArgs a;
-  a.n = n; a.idx = idx; a.obs = obs; a.actions = actions; a.returns = returns; a.old_values = old_values; a.old_neglogp = old_neglogp; a.rec = nullptr;
-  a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.w3 = w3; a.b3 = b3; a.logstd = logstd; a.adv_stats = adv_stats;
-  a.cliprange = cliprange; a.vf_coef = vf_coef; a.inv_n = 1.0f / (float)n; a.partials = partials;
+  const MlpUpdateArgs a = mlp_update_args(n, idx, obs, actions, returns, old_values, old_neglogp, nullptr, w1, b1, w2, b2, w3, b3, logstd, adv_stats, cliprange, vf_coef, partials);
   return mlp_bf16_launch("irrl_mlp_ppo_grads_bf16", kind, false, n, n_blocks, a, hip_stream);
 }
 
@@ -995,31 +967,28 @@ int irrl_mlp_ppo_grads_bf16_rec(int kind, size_t n, const int64_t *idx, const fl
                                 const float *b2, const float *w3, const float *b3, const float *logstd, const float *adv_stats, float cliprange,
                                 float vf_coef, float *partials, int n_blocks, void *hip_stream) {
   if (!rec || ((uintptr_t)rec & 255u)) { g_err = "irrl_mlp_ppo_grads_bf16_rec: rec is NULL or not 256-byte aligned"; return 1; }
-  MlpUpdateArgs a;
-  a.n = n; a.idx = idx; a.obs = nullptr; a.actions = nullptr; a.returns = nullptr; a.old_values = nullptr; a.old_neglogp = nullptr; a.rec = rec;
-  a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.w3 = w3; a.b3 = b3; a.logstd = logstd; a.adv_stats = adv_stats;
-  a.cliprange = cliprange; a.vf_coef = vf_coef; a.inv_n = 1.0f / (float)n; a.partials = partials;
+  const MlpUpdateArgs a = mlp_update_args(n, idx, nullptr, nullptr, nullptr, nullptr, nullptr, rec, w1, b1, w2, b2, w3, b3, logstd, adv_stats, cliprange, vf_coef, partials);
   return mlp_bf16_launch("irrl_mlp_ppo_grads_bf16_rec", kind, true, n, n_blocks, a, hip_stream);
 }
 
 // sums[3] = (sum a, sum a^2, n) of a = returns[r] - old_values[r] over the minibatch's rows, in double; scratch: [2 * n_blocks] doubles;
 // stats (may be NULL): (mean, population std) of a as floats, what the loss kernels take as adv_stats when there is one rank
-int irrl_adv_moments(size_t n, const int64_t *idx, const float *returns, const float *old_values, double *scratch, int n_blocks, double *sums,
-                     float *stats, void *hip_stream) {
-  if (n == 0 || n_blocks <= 0) { g_err = "irrl_adv_moments: empty batch"; return 1; }
-  hipLaunchKernelGGL(irrl_adv_moments_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)hip_stream, idx, n, returns, old_values, scratch, (size_t)1);
+static int adv_moments_launch(size_t n, const int64_t *idx, const float *ret, const float *val, size_t stride, double *scratch, int n_blocks, double *sums, float *stats,
+                              void *hip_stream) {
+  hipLaunchKernelGGL(irrl_adv_moments_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)hip_stream, idx, n, ret, val, scratch, stride);
   hipLaunchKernelGGL(irrl_adv_moments_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)hip_stream, scratch, n_blocks, n, sums, stats);
   HIP_TRY(hipGetLastError());
   return 0;
 }
+int irrl_adv_moments(size_t n, const int64_t *idx, const float *returns, const float *old_values, double *scratch, int n_blocks, double *sums,
+                     float *stats, void *hip_stream) {
+  if (n == 0 || n_blocks <= 0) { g_err = "irrl_adv_moments: empty batch"; return 1; }
+  return adv_moments_launch(n, idx, returns, old_values, 1, scratch, n_blocks, sums, stats, hip_stream);
+}
 // the same moments with the advantages read out of the packed records (word 51 = return - old value, formed in f32 by the pack kernel)
 int irrl_adv_moments_rec(size_t n, const int64_t *idx, const float *rec, double *scratch, int n_blocks, double *sums, float *stats, void *hip_stream) {
   if (n == 0 || n_blocks <= 0 || !rec) { g_err = "irrl_adv_moments_rec: empty batch"; return 1; }
-  hipLaunchKernelGGL(irrl_adv_moments_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)hip_stream, idx, n, rec + 51, (const float *)nullptr, scratch,
-                     (size_t)IRRL_MLP_REC);
-  hipLaunchKernelGGL(irrl_adv_moments_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)hip_stream, scratch, n_blocks, n, sums, stats);
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return adv_moments_launch(n, idx, rec + 51, nullptr, IRRL_MLP_REC, scratch, n_blocks, sums, stats, hip_stream);
 }
 
 // ---- the tail of an optimizer step on flat buffers (kernels: csrc/ppo_optim.hpp; ppo2.py:182-197 clip_by_global_norm + Adam) ----

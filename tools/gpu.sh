@@ -160,7 +160,7 @@ while [ $# -gt 0 ]; do
         IRRL_ENV_LIB=$PWD/$f timeout 300 python tools/ppo_bench.py --policy lstm --envs 4096 --iters 4 --precision $prec 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$(basename $f .so) $prec rollout', round(d['rollout_s']*1e3,2), 'ms update', round(d['update_s']*1e3,2), 'ms', round(d['ppo_iters_per_sec'],3), 'it/s')" >> $O/ablstm.log
       done; done; done ;;
     abrecomp)
-      # same-box A/B of the PPO-LSTM update at bf16x3: the backward kernel recomputes the gates (IRRL_LSTM_RECOMPUTE=1, default) / loads stored ones (0)
+      # same-box A/B of the PPO-LSTM update at bf16x3: the backward kernel recomputes the gates (IRRL_LSTM_RECOMPUTE=1, opt-in) / loads stored ones (0, the default)
       rm -f $O/abrecomp.log
       for r in 1 2 3; do for rc in 1 0; do
         IRRL_LSTM_RECOMPUTE=$rc timeout 300 python tools/ppo_bench.py --policy lstm --envs 4096 --iters 4 --precision bf16x3 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('IRRL_LSTM_RECOMPUTE=$rc rollout', round(d['rollout_s']*1e3,2), 'ms update', round(d['update_s']*1e3,2), 'ms', round(d['ppo_iters_per_sec'],3), 'it/s')" >> $O/abrecomp.log
