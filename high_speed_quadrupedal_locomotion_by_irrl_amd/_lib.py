@@ -26,6 +26,10 @@ SIGNATURES = {
     "irrl_env_action_dim": (C.c_int, [vp]),
     "irrl_env_extra_dim": (C.c_int, [vp]),
     "irrl_env_extra_name": (C.c_char_p, [vp, C.c_int]),
+    "irrl_kernel_variant_for": (C.c_char_p, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int]),
+    "irrl_env_kernel_variant": (C.c_char_p, [vp]),
+    "irrl_env_kernel_name": (C.c_char_p, [vp, C.c_int]),
+    "irrl_env_persistent_supported": (C.c_int, [vp]),
     "irrl_env_step": (C.c_int, [vp, vp, vp, vp, vp, vp]),
     "irrl_env_step_host": (C.c_int, [vp, fp, fp, fp, u8, fp]),
     "irrl_env_step_rows": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
@@ -88,6 +92,7 @@ SIGNATURES = {
     "irrl_lstm_policy_step": (C.c_int, [C.c_int] * 4 + [vp] * 11 + [C.c_int, C.c_uint, C.c_longlong, vp, C.c_int] + [vp] * 4 + [C.c_longlong] + [vp] * 8),
     "irrl_mlp_rollout": (C.c_int, [vp] + [C.c_int] * 4 + [vp] * 9 + [C.c_int, C.c_uint, C.c_longlong, vp, C.c_int] + [vp] * 4 + [C.c_longlong] + [vp] * 8 + [C.c_int, vp]),
     "irrl_lstm_rollout_supports": (C.c_int, [vp, C.c_int, C.c_int]),
+    "irrl_mlp_rollout_supports": (C.c_int, [vp, C.c_int, C.c_int]),
     "irrl_lstm_rollout": (C.c_int, [vp] + [C.c_int] * 4 + [vp] * 11 + [C.c_int, C.c_uint, C.c_longlong, vp, C.c_int] + [vp] * 4 + [C.c_longlong] + [vp] * 8 + [C.c_int, vp]),
 }
 

@@ -181,8 +181,10 @@ def build(force=False, verbose=False, extra_flags=()):
     objdir = os.path.join(_HERE, "csrc", "_obj")
     os.makedirs(objdir, exist_ok=True)
     # the env kernels in both lane layouts (same source, different lane-primitive header; the 4-lane layout once more for two waves per
-    # SIMD) through the ISA pass, then the C-ABI + LSTM kernels through the plain driver
+    # SIMD; the 16-lane layout once more for the run-time-solver twins of the rollout kernels alone) through the ISA pass, then the C-ABI +
+    # LSTM kernels through the plain driver
     units = [("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=16"] + ENV_FLAGS, "env_kernels_l16.o"),
+             ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=16", "-DIRRL_ROLLOUT_RT_UNIT"] + ENV_FLAGS, "env_kernels_l16rt.o"),
              ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=4"] + ENV_FLAGS, "env_kernels_l4.o"),
              ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=4", "-DIRRL_L4_WAVES2"] + ENV_FLAGS_W2, "env_kernels_l4w2.o"),
              ("irrl_env_abi.hip", ['-DIRRL_SRC_HASH="%s"' % want], "irrl_env_abi.o")]
@@ -196,7 +198,7 @@ def build(force=False, verbose=False, extra_flags=()):
             if verbose:
                 print(" ".join(cmd))
             subprocess.check_call(cmd)
-    with ThreadPoolExecutor(4) as ex:
+    with ThreadPoolExecutor(len(units)) as ex:
         list(ex.map(one, units))
     link = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC"] + [os.path.join(objdir, u[2]) for u in units] + ["-o", LIB]
     if verbose:

@@ -24,6 +24,8 @@ struct PolicyStepArgs;   // policy_step.hpp
   extern "C" __global__ void irrl_step_kernel_flat##sfx(IRRL_STEP_KERNEL_ARGS);            \
   extern "C" __global__ void irrl_steps_persistent_kernel##sfx(IRRL_STEPS_KERNEL_ARGS);    \
   extern "C" __global__ void irrl_steps_persistent_kernel_flat##sfx(IRRL_STEPS_KERNEL_ARGS); \
+  extern "C" __global__ void irrl_steps_persistent_kernel_rt##sfx(IRRL_STEPS_KERNEL_ARGS); \
+  extern "C" __global__ void irrl_steps_persistent_kernel_dir##sfx(IRRL_STEPS_KERNEL_ARGS); \
   extern "C" __global__ void irrl_init_kernel##sfx(EnvParams, EnvState);                   \
   extern "C" __global__ void irrl_reset_kernel##sfx(EnvParams, EnvState, float *);         \
   extern "C" __global__ void irrl_observe_kernel##sfx(EnvParams, EnvState, float *);       \
@@ -33,8 +35,14 @@ IRRL_DECLARE_KERNELS(_l4)
 IRRL_DECLARE_KERNELS(_l4w2)
 #undef IRRL_DECLARE_KERNELS
 extern "C" __global__ void irrl_terminal_kernel(EnvParams, EnvState, uint8_t *);
-extern "C" __global__ void irrl_step_policy_kernel_l16(IRRL_STEP_KERNEL_ARGS, PolicyStepArgs);
-extern "C" __global__ void irrl_rollout_persistent_kernel_l16(IRRL_ROLLOUT_KERNEL_ARGS);
-extern "C" __global__ void irrl_rollout_persistent_actor_kernel_l16(IRRL_ROLLOUT_KERNEL_ARGS);
-extern "C" __global__ void irrl_rollout_persistent_actor_wave_kernel_l16(IRRL_ROLLOUT_KERNEL_ARGS);
-extern "C" __global__ void irrl_rollout_persistent_mlp_kernel_l16(IRRL_ROLLOUT_KERNEL_ARGS);
+// the kernels with the policy in the same launch (16-lane layout; csrc/env_rollout_kernels.hpp): sfx _l16 = the shipped solver settings compiled in,
+// _rt_l16 = read from EnvParams
+#define IRRL_DECLARE_ROLLOUT_KERNELS(sfx)                                                                      \
+  extern "C" __global__ void irrl_step_policy_kernel##sfx(IRRL_STEP_KERNEL_ARGS, PolicyStepArgs);              \
+  extern "C" __global__ void irrl_rollout_persistent_kernel##sfx(IRRL_ROLLOUT_KERNEL_ARGS);                    \
+  extern "C" __global__ void irrl_rollout_persistent_actor_kernel##sfx(IRRL_ROLLOUT_KERNEL_ARGS);              \
+  extern "C" __global__ void irrl_rollout_persistent_actor_wave_kernel##sfx(IRRL_ROLLOUT_KERNEL_ARGS);         \
+  extern "C" __global__ void irrl_rollout_persistent_mlp_kernel##sfx(IRRL_ROLLOUT_KERNEL_ARGS);
+IRRL_DECLARE_ROLLOUT_KERNELS(_l16)
+IRRL_DECLARE_ROLLOUT_KERNELS(_rt_l16)
+#undef IRRL_DECLARE_ROLLOUT_KERNELS

@@ -196,6 +196,7 @@ class VecEnv {
   }
   int lanes_per_robot() const { return irrl_env_lanes_per_robot(h_); }
   int waves_per_simd() const { return irrl_env_waves_per_simd(h_); }
+  int persistent_supported() const { return irrl_env_persistent_supported(h_); }
   size_t handle() const { return reinterpret_cast<size_t>(h_); }
 
  private:
@@ -244,5 +245,6 @@ PYBIND11_MODULE(_flexible_robot, m) {
       .def("set_state", &VecEnv::set_state, nc("state"))
       .def_property_readonly("lanes_per_robot", &VecEnv::lanes_per_robot)
       .def_property_readonly("waves_per_simd", &VecEnv::waves_per_simd)
+      .def_property_readonly("persistent_supported", &VecEnv::persistent_supported)
       .def_property_readonly("handle", &VecEnv::handle);
 }

@@ -108,9 +108,9 @@ static inline int layout_index(const irrl_env *h) { return h->lanes == 16 ? 0 : 
 
 // the step kernel: one instantiation per (Crutial, per-contact rule) -- env_kernels.hip -- and, for the default pool kind (no meteorite, published
 // rule), one with the shipped solver settings compiled in (simultaneous sweeps + predicted exit + a tolerance above zero + at most six sweeps + eight substeps per control step: env_core.hpp IRRL_SOLVER_FIXED) next to the
-// one that reads them from EnvParams; the multi-step and rollout kernels exist for the former only (the launchers fall back)
-// flat ground compiled in (env_core.hpp IRRL_FLAT_GROUND): the step kernel and the multi-step kernel exist in that form too.  (Not in the
-// instrumented build of tools/wave_spread.py, whose per-wave clock sits in irrl_step_kernel.)
+// one that reads them from EnvParams, and one more with flat ground compiled in as well (env_core.hpp IRRL_FLAT_GROUND).  The multi-step kernel
+// exists for every variant without the meteorite, the rollout kernels (16-lane layout) for the published rule without it; Crutial pools fall back.
+// (The flat form is not used in the instrumented build of tools/wave_spread.py, whose per-wave clock sits in irrl_step_kernel.)
 static inline bool flat_kernels(const irrl_env *h) {
 #ifdef IRRL_PROFILE_WAVES
   (void)h;
@@ -119,32 +119,62 @@ static inline bool flat_kernels(const irrl_env *h) {
   return !h->P.terrain;
 #endif
 }
-static inline bool shipped_solver(const irrl_env *h) {
-  return h->P.contact_jacobi != 0 && h->P.contact_exit != 0 && h->P.contact_tol > 0.0f && h->P.contact_iters == IRRL_SHIPPED_SWEEP_CAP &&
-         h->P.loop_count == IRRL_SHIPPED_SUBSTEPS;
-}
-// WHICH STEP KERNEL A POOL RUNS: the one place that decides it (read per launch: the setters change loop_count)
+// WHICH STEP KERNEL A POOL RUNS: the one place that decides it, a function of the settings alone (host only: irrl_kernel_variant_for exports it, so
+// the table is testable without a device).  contact_solver: the YAML key's value (bit 1 simultaneous sweeps, bit 0 the published per-contact rule);
+// contact_exit / contact_tol / contact_iters: ContactExit / ContactTolerance / ContactIterations as irrl_config.hpp resolves them; substeps:
+// control_dt / simulation_dt.  SV_COUNT: contact_solver out of range.
 enum StepVariant { SV_CRUTIAL, SV_CRUTIAL_MD, SV_DIR, SV_MD, SV_SHIPPED, SV_SHIPPED_FLAT, SV_COUNT };
-static StepVariant step_variant(const irrl_env *h) {
-  if (h->P.crutial) return h->P.contact_rule ? SV_CRUTIAL_MD : SV_CRUTIAL;
-  if (!h->P.contact_rule) return SV_DIR;
-  if (!shipped_solver(h)) return SV_MD;
-  return flat_kernels(h) ? SV_SHIPPED_FLAT : SV_SHIPPED;
+static const char *const kVariantNames[SV_COUNT + 1] = {"crutial", "crutial_md", "dir", "md", "shipped", "shipped_flat", ""};
+static StepVariant variant_for(int crutial, int contact_solver, int contact_exit, double contact_tol, int contact_iters, int substeps, int terrain) {
+  if (contact_solver < 0 || contact_solver > 3) return SV_COUNT;
+  const bool rule = (contact_solver & 1) != 0, jacobi = (contact_solver & 2) != 0;
+  if (crutial) return rule ? SV_CRUTIAL_MD : SV_CRUTIAL;
+  if (!rule) return SV_DIR;
+  const bool shipped = jacobi && contact_exit != 0 && (float)contact_tol > 0.0f && contact_iters == IRRL_SHIPPED_SWEEP_CAP && substeps == IRRL_SHIPPED_SUBSTEPS;
+  if (!shipped) return SV_MD;
+  return terrain ? SV_SHIPPED : SV_SHIPPED_FLAT;
 }
-// the multi-step kernel and the rollout kernels (env step + policy in one launch; 16-lane layout only) exist for the shipped variants alone
-static inline bool persistent_kernels(const irrl_env *h) { const StepVariant v = step_variant(h); return v == SV_SHIPPED || v == SV_SHIPPED_FLAT; }
-static inline bool rollout_kernels(const irrl_env *h) { return h->lanes == 16 && persistent_kernels(h); }
+// ... of a pool (read per launch: the setters change loop_count)
+static StepVariant step_variant(const irrl_env *h) {
+  return variant_for(h->P.crutial, (h->P.contact_jacobi ? 2 : 0) | (h->P.contact_rule ? 1 : 0), h->P.contact_exit, (double)h->P.contact_tol, h->P.contact_iters,
+                     h->P.loop_count, flat_kernels(h) ? 0 : 1);
+}
 
 typedef void (*step_kernel_t)(IRRL_STEP_KERNEL_ARGS);
+typedef void (*step_policy_kernel_t)(IRRL_STEP_KERNEL_ARGS, PolicyStepArgs);
 typedef void (*steps_kernel_t)(IRRL_STEPS_KERNEL_ARGS);
 typedef void (*rollout_kernel_t)(IRRL_ROLLOUT_KERNEL_ARGS);
-static const step_kernel_t kStepKernels[SV_COUNT][3] = {   // [StepVariant][layout]
-    IRRL_PER_LAYOUT(irrl_step_kernel_crutial), IRRL_PER_LAYOUT(irrl_step_kernel_crutial_md), IRRL_PER_LAYOUT(irrl_step_kernel_dir),
-    IRRL_PER_LAYOUT(irrl_step_kernel_md), IRRL_PER_LAYOUT(irrl_step_kernel), IRRL_PER_LAYOUT(irrl_step_kernel_flat)};
-static const steps_kernel_t kStepsKernels[2][3] = {IRRL_PER_LAYOUT(irrl_steps_persistent_kernel), IRRL_PER_LAYOUT(irrl_steps_persistent_kernel_flat)};   // [flat][layout]
+// a kernel with its name (irrl_env_kernel_name reports what a pool launches)
+#define IRRL_NAMED(k) { k, #k }
+#define IRRL_PER_LAYOUT_NAMED(name) { IRRL_NAMED(name##_l16), IRRL_NAMED(name##_l4), IRRL_NAMED(name##_l4w2) }
+struct StepKernel { step_kernel_t fn; const char *name; };
+struct StepsKernel { steps_kernel_t fn; const char *name; };
+static const StepKernel kStepKernels[SV_COUNT][3] = {   // [StepVariant][layout]
+    IRRL_PER_LAYOUT_NAMED(irrl_step_kernel_crutial), IRRL_PER_LAYOUT_NAMED(irrl_step_kernel_crutial_md), IRRL_PER_LAYOUT_NAMED(irrl_step_kernel_dir),
+    IRRL_PER_LAYOUT_NAMED(irrl_step_kernel_md), IRRL_PER_LAYOUT_NAMED(irrl_step_kernel), IRRL_PER_LAYOUT_NAMED(irrl_step_kernel_flat)};
+// the multi-step kernel per variant; fn == nullptr: the variant has none (the meteorite) and the multi-step entry points launch once per step
+#define IRRL_NO_STEPS_KERNEL { {nullptr, ""}, {nullptr, ""}, {nullptr, ""} }
+static const StepsKernel kStepsKernels[SV_COUNT][3] = {   // [StepVariant][layout]
+    IRRL_NO_STEPS_KERNEL, IRRL_NO_STEPS_KERNEL, IRRL_PER_LAYOUT_NAMED(irrl_steps_persistent_kernel_dir), IRRL_PER_LAYOUT_NAMED(irrl_steps_persistent_kernel_rt),
+    IRRL_PER_LAYOUT_NAMED(irrl_steps_persistent_kernel), IRRL_PER_LAYOUT_NAMED(irrl_steps_persistent_kernel_flat)};
+// the kernels that run the policy in the same launch (16-lane layout only): the twin with the shipped solver settings compiled in, or the one that
+// reads them from EnvParams -- picked by variant HERE and nowhere else.  [0]: SV_SHIPPED / SV_SHIPPED_FLAT, [1]: SV_MD; no other variant has them.
+struct RolloutKernels { step_policy_kernel_t step_policy; rollout_kernel_t full, actor, actor_wave, mlp; };
+static const RolloutKernels kRolloutKernels[2] = {
+    {irrl_step_policy_kernel_l16, irrl_rollout_persistent_kernel_l16, irrl_rollout_persistent_actor_kernel_l16, irrl_rollout_persistent_actor_wave_kernel_l16,
+     irrl_rollout_persistent_mlp_kernel_l16},
+    {irrl_step_policy_kernel_rt_l16, irrl_rollout_persistent_kernel_rt_l16, irrl_rollout_persistent_actor_kernel_rt_l16,
+     irrl_rollout_persistent_actor_wave_kernel_rt_l16, irrl_rollout_persistent_mlp_kernel_rt_l16}};
+static inline bool persistent_kernels(const irrl_env *h) { return kStepsKernels[step_variant(h)][layout_index(h)].fn != nullptr; }
+static inline const RolloutKernels *rollout_kernel_set(const irrl_env *h) {
+  if (h->lanes != 16) return nullptr;
+  const StepVariant v = step_variant(h);
+  return (v == SV_SHIPPED || v == SV_SHIPPED_FLAT) ? &kRolloutKernels[0] : v == SV_MD ? &kRolloutKernels[1] : nullptr;
+}
+static inline bool rollout_kernels(const irrl_env *h) { return rollout_kernel_set(h) != nullptr; }
 // one env.step of the first P.n_envs robots of the pool (P: h->P, or a copy with fewer robots)
 static void launch_step(irrl_env *h, const EnvParams &P, const float *action, float *ob, float *reward, uint8_t *done, float *extra) {
-  hipLaunchKernelGGL(kStepKernels[step_variant(h)][layout_index(h)], lane_grid(h, P.n_envs), quad_block(), 0, h->stream, P, h->S, action, ob, reward, done, extra);
+  hipLaunchKernelGGL(kStepKernels[step_variant(h)][layout_index(h)].fn, lane_grid(h, P.n_envs), quad_block(), 0, h->stream, P, h->S, action, ob, reward, done, extra);
 }
 // a rollout kernel: 256-thread workgroups of 16 robots
 static void launch_rollout(irrl_env *h, rollout_kernel_t k, float *obs, float *env_reward, uint8_t *dones, float *env_extra, const PolicyStepArgs &a, int steps) {
@@ -286,6 +316,21 @@ int irrl_env_init(irrl_env *h) {
 }
 
 int irrl_env_num_envs(const irrl_env *h) { return h->P.n_envs; }
+// which kernels a configuration selects / a pool runs right now (nothing is launched)
+const char *irrl_kernel_variant_for(int crutial, int contact_solver, int contact_exit, double contact_tol, int contact_iters, int substeps, int terrain) {
+  return kVariantNames[variant_for(crutial, contact_solver, contact_exit, contact_tol, contact_iters, substeps, terrain)];
+}
+const char *irrl_env_kernel_variant(const irrl_env *h) { return h ? kVariantNames[step_variant(h)] : ""; }
+const char *irrl_env_kernel_name(const irrl_env *h, int path) {
+  if (!h || path < 0 || path > 1) return "";
+  const StepVariant v = step_variant(h);
+  const int l = layout_index(h);
+  return (path == 1 && kStepsKernels[v][l].fn) ? kStepsKernels[v][l].name : kStepKernels[v][l].name;
+}
+int irrl_env_persistent_supported(const irrl_env *h) {
+  if (!h) { g_err = "irrl_env_persistent_supported: NULL handle"; return -1; }
+  return persistent_kernels(h) ? 1 : 0;
+}
 int irrl_env_lanes_per_robot(const irrl_env *h) { return h->lanes; }
 int irrl_env_waves_per_simd(const irrl_env *h) { return h->waves2 ? 2 : 1; }
 int irrl_env_ob_dim(const irrl_env *) { return IRRL_OB_DIM; }
@@ -337,14 +382,14 @@ static int step_rows_impl(irrl_env *h, int count, const float *action_rows, int 
   return 0;
 }
 // the same `count` steps as ONE launch (env_kernels.hip irrl_steps_persistent_kernel: a wave walks its robots through all of them, no
-// grid-wide boundary between steps); pools the kernel is not instantiated for (meteorite, first contact rule) take the launch-per-step path
+// grid-wide boundary between steps); pools the kernel is not instantiated for (the meteorite) take the launch-per-step path
 static int step_rows_persistent_impl(irrl_env *h, int count, const float *action_rows, int n_rows, int first_row, float *ob, float *reward,
                                      uint8_t *done, float *extra, int out_rows, const char *who) {
   if (step_rows_check(h, count, action_rows, n_rows, first_row, ob, reward, done, extra, who)) return 1;
   if (!persistent_kernels(h)) return step_rows_impl(h, count, action_rows, n_rows, first_row, ob, reward, done, extra, out_rows, who);
   if (use_device(h)) return 1;
   if (count > 0)
-    hipLaunchKernelGGL(kStepsKernels[flat_kernels(h)][layout_index(h)], lane_grid(h, h->P.n_envs), quad_block(), 0, h->stream, h->P, h->S, action_rows, n_rows,
+    hipLaunchKernelGGL(kStepsKernels[step_variant(h)][layout_index(h)].fn, lane_grid(h, h->P.n_envs), quad_block(), 0, h->stream, h->P, h->S, action_rows, n_rows,
                        first_row, count, ob, reward, done, extra, out_rows);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -403,7 +448,7 @@ int irrl_lstm_rollout(irrl_env *h, int steps, int hid, int ob_dim, int act_dim, 
                             mb_dones, mb_rewards, env_reward);
   };
   // fuse != 0: one launch per step, env.step k together with the policy step k + 1 (16-lane layout = one MFMA M-tile per four env
-  // waves, the reference's 48-unit network, pools without the meteorite).  Bit-identical to the two-launch sequence, and measured
+  // waves, the reference's 48-unit network, pools without the meteorite under the published contact rule, whatever their solver settings).  Bit-identical to the two-launch sequence, and measured
   // SLOWER on MI355X (62.9 against 58.2 us per step at 4096 envs): kept as an option, not the default.
   const bool one_tile = rollout_one_tile(h, hid);   // what the combined kernels are instantiated for
   // fuse == 2: THE WHOLE ROLLOUT AS ONE PERSISTENT LAUNCH (irrl_rollout_persistent_kernel_l16): a workgroup loops over all steps for its
@@ -421,8 +466,8 @@ int irrl_lstm_rollout(irrl_env *h, int steps, int hid, int ob_dim, int act_dim, 
     if (!mb_rewards) { g_err = "irrl_lstm_rollout: the persistent path writes the reward rows (mb_rewards is mandatory)"; return 1; }
     // fuse == 3: the actor as each wave's own work (round 5, second half); IRRL_ACTOR_WAVES=0: the workgroup-wide actor step (same buffers, bit for bit)
     const char *aw = getenv("IRRL_ACTOR_WAVES");
-    const rollout_kernel_t k = fuse != 3 ? irrl_rollout_persistent_kernel_l16
-                               : (aw && aw[0] == '0') ? irrl_rollout_persistent_actor_kernel_l16 : irrl_rollout_persistent_actor_wave_kernel_l16;
+    const RolloutKernels *rk = rollout_kernel_set(h);
+    const rollout_kernel_t k = fuse != 3 ? rk->full : (aw && aw[0] == '0') ? rk->actor : rk->actor_wave;
     launch_rollout(h, k, obs, env_reward, dones, env_extra, policy_args(0, true), steps);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -432,7 +477,7 @@ int irrl_lstm_rollout(irrl_env *h, int steps, int hid, int ob_dim, int act_dim, 
   if (steps > 0 && policy(0) != 0) { g_err = "irrl_lstm_rollout: policy step refused its arguments"; return 1; }
   for (int k = 0; k < steps; k++) {
     if (fused && k + 1 < steps) {
-      hipLaunchKernelGGL(irrl_step_policy_kernel_l16, dim3((n + 15) / 16), dim3(256), 0, h->stream, h->P, h->S, (const float *)clipped, obs,
+      hipLaunchKernelGGL(rollout_kernel_set(h)->step_policy, dim3((n + 15) / 16), dim3(256), 0, h->stream, h->P, h->S, (const float *)clipped, obs,
                          env_reward, dones, env_extra, policy_args(k + 1, false));
     } else {
       launch_step(h, h->P, (const float *)clipped, obs, env_reward, dones, env_extra);
@@ -443,9 +488,17 @@ int irrl_lstm_rollout(irrl_env *h, int steps, int hid, int ob_dim, int act_dim, 
   return 0;
 }
 
+// irrl_mlp_rollout_supports: which `fuse` modes exist for this pool (the twin of irrl_lstm_rollout_supports; fuse 2 falls back inside the call)
+int irrl_mlp_rollout_supports(irrl_env *h, int hid, int fuse) {
+  if (!h) { g_err = "irrl_mlp_rollout_supports: NULL handle"; return -1; }
+  if (hid != 64) return 0;
+  if (fuse == 0) return 1;
+  if (fuse != 2) return 0;
+  return rollout_kernels(h) ? 1 : 0;
+}
 // The MlpPolicy twin of irrl_lstm_rollout (no recurrent state).  fuse == 2 (and a pool the combined kernel is instantiated for: 16 lanes
 // per robot, no meteorite, published contact rule, 64 hidden units, 35 observations): the whole rollout as ONE persistent launch
-// (irrl_rollout_persistent_mlp_kernel_l16); otherwise 2 x steps launches back to back.  Bit-identical buffers either way.
+// (irrl_rollout_persistent_mlp_kernel[_rt]_l16); otherwise 2 x steps launches back to back.  Bit-identical buffers either way.
 int irrl_mlp_rollout(irrl_env *h, int steps, int hid, int ob_dim, int act_dim, float *obs, uint8_t *dones, const float *const *mlp_w, const float *pi_w,
                      const float *pi_b, const float *vf_w, const float *vf_b, const float *logstd, const float *noise, int rng_on, unsigned rng_seed,
                      long long rng_step, const long long *rng_base, int env_id_offset, float *action, float *clipped, float *value, float *neglogp,
@@ -465,7 +518,7 @@ int irrl_mlp_rollout(irrl_env *h, int steps, int hid, int ob_dim, int act_dim, f
   auto noise_at = [&](int k) { return noise ? noise + (size_t)k * (size_t)n * (size_t)act_dim : nullptr; };
   if (fuse == 2 && rollout_kernels(h) && steps > 0) {
     if (!mb_rewards) { g_err = "irrl_mlp_rollout: the persistent path writes the reward rows (mb_rewards is mandatory)"; return 1; }
-    launch_rollout(h, irrl_rollout_persistent_mlp_kernel_l16, obs, env_reward, dones, env_extra,
+    launch_rollout(h, rollout_kernel_set(h)->mlp, obs, env_reward, dones, env_extra,
                    policy_step_args(n, ob_dim, act_dim, obs, dones, nullptr, nullptr, mlp_w, 8, pi_w, pi_b, vf_w, vf_b, logstd, noise, rng_on, rng_seed, rng_step, rng_base,
                                     env_id_offset, action, clipped, value, neglogp, row, mb_obs, mb_actions, mb_values, mb_neglogp, mb_dones, mb_rewards, env_reward),
                    steps);

@@ -86,6 +86,21 @@ class FlexibleGymEnv(object):
     def waves_per_simd(self):
         return self._lib.irrl_env_waves_per_simd(self._h)
 
+    # which kernels this pool runs RIGHT NOW (read per call: the time-step setters change the answer)
+    @property
+    def kernel_variant(self):
+        """"crutial", "crutial_md", "dir", "md", "shipped" or "shipped_flat": the step-kernel variant the pool's settings select"""
+        return self._lib.irrl_env_kernel_variant(self._h).decode()
+
+    @property
+    def persistent_supported(self):
+        """1: step_rows(..., persistent=True) runs as ONE launch; 0: it falls back to one launch per step"""
+        return self._lib.irrl_env_persistent_supported(self._h)
+
+    def kernel_name(self, path):
+        """name of the kernel behind step() (path 0) or step_rows(..., persistent=True) (path 1), layout suffix included"""
+        return self._lib.irrl_env_kernel_name(self._h, int(path)).decode()
+
     # -- raisim_gym.cpp:17-46 --
     def init(self):
         _lib.check(self._lib.irrl_env_init(self._h))

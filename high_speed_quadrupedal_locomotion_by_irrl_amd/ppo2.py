@@ -566,9 +566,11 @@ class Runner(object):
         self.states[:, off:].copy_(torch.cat(new_v, 1))
 
     def _actor_only_supported(self):
-        """irrl_lstm_rollout_supports(pool, hid, fuse = 3), asked once per runner: the persistent actor-only kernel exists for 16 lanes per
-        robot, 48 hidden units, Crutial off and the published contact rule; MlpPolicy has no critic stack to take off the path."""
-        if not hasattr(self, "_actor_only_ok"):
+        """irrl_lstm_rollout_supports(pool, hid, fuse = 3): the persistent actor-only kernel exists for 16 lanes per robot, 48 hidden units,
+        Crutial off and the published contact rule; MlpPolicy has no critic stack to take off the path.  The answer is kept per
+        `params_epoch` of the pool (as `_maybe_capture` keeps its graph): the time-step setters change which kernels a pool runs."""
+        epoch = getattr(getattr(self.env, "wrapper", None), "params_epoch", 0)
+        if getattr(self, "_actor_only_epoch", None) != epoch:
             pol = self.model.policy
             ok = False
             if hasattr(pol, "lstm_v") and hasattr(getattr(self.env, "wrapper", None), "_h"):
@@ -577,8 +579,42 @@ class Runner(object):
                 if rc < 0:
                     _lib.check(1)
                 ok = rc == 1
-            self._actor_only_ok = ok
+            self._actor_only_ok, self._actor_only_epoch = ok, epoch
         return self._actor_only_ok
+
+    def _note_rollout_fallback(self, mode):
+        """One line, once per runner, at the first run() that asks for a persistent rollout the pool has no kernel for: the rollout about to
+        run is two launches per step.  Asked through the C-ABI per run() until then (nothing is launched); names the pool's kernel variant and
+        why it has no such kernel."""
+        if getattr(self, "_fallback_noted", False):
+            return                                       # (set where the line is printed: a run() that did not ask for a persistent rollout uses nothing up)
+        raw = getattr(self.env, "wrapper", None)
+        if not hasattr(raw, "_h") or not hasattr(raw, "kernel_variant"):
+            return
+        from . import _lib
+        pol, lib = self.model.policy, _lib.load()
+        if hasattr(pol, "lstm_v"):
+            if mode < 2:
+                return                                   # two launches per step (or the fused-step experiment) were asked for
+            ok = lib.irrl_lstm_rollout_supports(raw._h, int(pol.n_lstm[0]), 2) == 1
+        else:
+            from . import lstm_fused
+            if lstm_fused.MLP_ROLLOUT != "persistent":
+                return                                   # two launches per step were asked for (IRRL_MLP_ROLLOUT=direct)
+            ok = lib.irrl_mlp_rollout_supports(raw._h, 64, 2) == 1
+        if ok:
+            return
+        variant = raw.kernel_variant
+        if variant.startswith("crutial"):
+            why = "Crutial pools have no persistent rollout kernel"
+        elif variant == "dir":
+            why = "ContactSolver 0 / 2 (the first per-contact rule) has no persistent rollout kernel"
+        elif raw.lanes_per_robot != 16:
+            why = "the persistent rollout kernels exist for the 16-lane layout only (this pool: %d lanes per robot)" % raw.lanes_per_robot
+        else:
+            why = "no persistent rollout kernel is built for this policy's size"
+        self._fallback_noted = True
+        print("[PPO2] rollout runs as two launches per step: kernel variant '%s', %s" % (variant, why), flush=True)
 
     def _fused_step(self, t):
         """Rollout step t as two launches: the whole policy step (sample, clip, buffer rows incl. the previous reward) and
@@ -699,6 +735,7 @@ class Runner(object):
                 mode = self.rollout_one_launch_per_step
                 if mode == 3 and not self._actor_only_supported():
                     mode = 2      # the actor-only kernel is not instantiated for this pool / network (asked through the C-ABI, nothing was launched)
+                self._note_rollout_fallback(mode)
                 pol.fused_rollout(*args, noise_all=self.noise_all, fused=mode)
                 if mode == 3:
                     self._critic_pass(mb_states)

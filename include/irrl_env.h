@@ -59,6 +59,24 @@ int irrl_env_lanes_per_robot(const irrl_env *h);
 /* resident waves per SIMD the pool's kernels are compiled for: 1 (the whole register file of a SIMD for one wave), or 2 for 4-lane pools
  * with more waves than the device has SIMDs (> 16 384 envs on an MI355X); build-defined, overridable with IRRL_L4_WAVES=1|2 */
 int irrl_env_waves_per_simd(const irrl_env *h);
+/* WHICH KERNELS A CONFIGURATION SELECTS.  The step kernel exists in six variants and the settings alone decide which one a pool runs:
+ *   "crutial" / "crutial_md"  Crutial: True (the meteorite), first / published per-contact rule
+ *   "dir"                     ContactSolver 0 or 2: the build's first per-contact rule
+ *   "md"                      the published rule (ContactSolver 1 or 3) with the solver settings read at run time
+ *   "shipped" / "shipped_flat"  the published rule with the shipped settings compiled in -- ContactSolver 3, ContactExit 1, ContactTolerance > 0,
+ *                             ContactIterations 6, eight substeps per control step -- on rough / flat ground
+ * irrl_kernel_variant_for is a function of the settings alone (host only, no device needed): contact_solver / contact_exit / contact_tol /
+ * contact_iters are the Contact* keys as resolved by the parser (absent keys: 3 / 1 / 0.0 / 6 -- so a config WITHOUT ContactTolerance is "md"),
+ * substeps = control_dt / simulation_dt, terrain = Terrain.  "" for a contact_solver outside 0..3.  The strings are stable. */
+const char *irrl_kernel_variant_for(int crutial, int contact_solver, int contact_exit, double contact_tol, int contact_iters, int substeps, int terrain);
+/* the pool's variant right now (read per call: irrl_env_set_control_dt / irrl_env_set_simulation_dt change the substep count) */
+const char *irrl_env_kernel_variant(const irrl_env *h);
+/* name of the kernel that irrl_env_step (path 0) or irrl_env_step_rows_persistent[_out] (path 1) launches for this pool right now, lane-layout
+ * suffix included (e.g. "irrl_steps_persistent_kernel_rt_l16"); where path 1 falls back to one launch per step, the step kernel's name.
+ * "" for any other path. */
+const char *irrl_env_kernel_name(const irrl_env *h, int path);
+/* 1: irrl_env_step_rows_persistent[_out] run as ONE launch for this pool, 0: they fall back to one launch per step (Crutial pools), -1: NULL handle */
+int irrl_env_persistent_supported(const irrl_env *h);
 int irrl_env_ob_dim(const irrl_env *h);
 int irrl_env_action_dim(const irrl_env *h);
 int irrl_env_extra_dim(const irrl_env *h);
@@ -74,8 +92,9 @@ int irrl_env_step_host(irrl_env *h, const float *action, float *ob, float *rewar
 int irrl_env_step_rows(irrl_env *h, int count, const float *action_rows, int n_rows, int first_row, float *ob, float *reward,
                        uint8_t *done, float *extra);
 /* the same `count` steps as ONE launch: a wave walks its own robots through all of them (robots never interact, VEC:273), so there is no
- * grid-wide boundary between steps and no launch per step.  States and outputs bit-identical to irrl_env_step_rows (which it falls back
- * to for pools with the meteorite or the build's first contact rule). */
+ * grid-wide boundary between steps and no launch per step.  States and outputs bit-identical to irrl_env_step_rows.  Every pool WITHOUT the
+ * meteorite gets the single launch, whatever its contact rule, solver settings or substep count (kernel variants "dir", "md", "shipped",
+ * "shipped_flat"; all three lane layouts); Crutial pools fall back to irrl_env_step_rows.  irrl_env_persistent_supported tells which. */
 int irrl_env_step_rows_persistent(irrl_env *h, int count, const float *action_rows, int n_rows, int first_row, float *ob, float *reward,
                                   uint8_t *done, float *extra);
 /* the two calls above WITH EVERY STEP'S OUTPUTS KEPT: ob_rows [count, N, 35], reward_rows [count, N], done_rows [count, N] u8,
@@ -329,7 +348,10 @@ int irrl_lstm_policy_step(int hid, int ob_dim, int act_dim, int N, const float *
  * history only and nothing in the rollout needs it before GAE, so the per-step part runs the actor stack alone (all of its operands resident in LDS) and
  * writes everything EXCEPT `value` / `mb_values` and the critic's half of `states`, which the caller obtains for the whole rollout afterwards with the
  * sequence kernels over the recorded observations (ppo2.Runner does); actor-side buffers bit-identical to the other modes; an error where the persistent
- * kernel is not instantiated. */
+ * kernel is not instantiated.
+ * WHICH POOLS GET THE SINGLE LAUNCH (fuse 1 / 2 / 3): 16 lanes per robot, hid 48, kernel variant "md", "shipped" or "shipped_flat" -- the published
+ * contact rule without the meteorite, with the shipped solver settings or any others (a config without the Contact* keys, ContactSolver 1, another
+ * sweep cap, a control step of other than eight substeps).  Crutial pools, ContactSolver 0 / 2 and 4-lane pools run two launches per step. */
 int irrl_lstm_rollout(irrl_env *env, int steps, int hid, int ob_dim, int act_dim, float *obs, uint8_t *dones, const float *states_in,
                       float *states_out, const float *const *lstm_w, const float *pi_w, const float *pi_b, const float *vf_w,
                       const float *vf_b, const float *logstd, const float *noise, int rng_on, unsigned rng_seed, long long rng_step,
@@ -353,7 +375,8 @@ int irrl_mlp_policy_step(int hid, int ob_dim, int act_dim, int N, const float *o
 
 /* `steps` consecutive rollout steps of MlpPolicy (policy step t, then env.step on its clipped action) from ONE call -- the MlpPolicy twin of
  * irrl_lstm_rollout (no recurrent state; mlp_w as in irrl_mlp_policy_step; ob 35, act 12, hid 64).  fuse == 2 and a pool the combined
- * kernel exists for (16 lanes per robot, Crutial off, published contact rule): the whole rollout as ONE persistent launch -- a workgroup
+ * kernel exists for (16 lanes per robot, kernel variant "md", "shipped" or "shipped_flat": Crutial off, published contact rule, any solver
+ * settings and substep count): the whole rollout as ONE persistent launch -- a workgroup
  * keeps its 16 robots and the policy's weights (in LDS) for all `steps`, no grid-wide boundary between steps; otherwise 2 x steps launches
  * back to back.  Bit-identical buffers either way (what ppo2.Runner records as a hipGraph of 2 x steps nodes otherwise). */
 int irrl_mlp_rollout(irrl_env *env, int steps, int hid, int ob_dim, int act_dim, float *obs, uint8_t *dones, const float *const *mlp_w, const float *pi_w,
@@ -361,6 +384,11 @@ int irrl_mlp_rollout(irrl_env *env, int steps, int hid, int ob_dim, int act_dim,
                      long long rng_step, const long long *rng_base, int env_id_offset, float *action, float *clipped, float *value, float *neglogp,
                      long long row, float *mb_obs, float *mb_actions, float *mb_values, float *mb_neglogp, uint8_t *mb_dones, float *mb_rewards,
                      float *env_reward, float *env_extra, int fuse, void *hip_stream);
+
+/* which `fuse` modes of irrl_mlp_rollout exist for THIS pool and a network of `hid` units: 1 = the mode runs as described (fuse 0 always; fuse 2 where
+ * the persistent kernel exists), 0 = it does not (fuse 2 then runs as 2 x steps launches inside the call; hid != 64 is refused by irrl_mlp_rollout),
+ * -1 = bad handle.  The twin of irrl_lstm_rollout_supports. */
+int irrl_mlp_rollout_supports(irrl_env *env, int hid, int fuse);
 
 #ifdef __cplusplus
 }

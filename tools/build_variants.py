@@ -24,7 +24,8 @@ for spec in sys.argv[1:]:
             del env_flags[i:i + 2]
     B_ENV = env_flags
     common = list(B.COMMON_FLAGS) + flags
-    for src, fl, obj in (("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=16"] + B_ENV, "l16"), ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=4"] + B_ENV, "l4"),
+    for src, fl, obj in (("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=16"] + B_ENV, "l16"),
+                         ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=16", "-DIRRL_ROLLOUT_RT_UNIT"] + B_ENV, "l16rt"), ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=4"] + B_ENV, "l4"),
                          ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=4", "-DIRRL_L4_WAVES2"] + (B_ENV if swapped else list(B.ENV_FLAGS_W2)), "l4w2"),
                          ("irrl_env_abi.hip", [], "abi")):
         o = os.path.join(out, f"{name}_{obj}.o")
