@@ -129,6 +129,33 @@ def last_error():
     return load().irrl_last_error().decode("utf-8", "replace")
 
 
+# Two ways an entry point reports a failure (written down here once):
+#   * csrc/irrl_env_abi.hip -- every irrl_env_*, irrl_lstm_rollout / irrl_mlp_rollout and their *_supports queries (< 0), irrl_gae, irrl_ppo_loss,
+#     irrl_ppo_heads_loss, irrl_mlp_ppo_grads*, irrl_mlp_pack_records, irrl_adv_moments*, irrl_clip_adam, irrl_sum_rows_scatter,
+#     irrl_random_permutation, irrl_bench_actions, irrl_calib_copy_dword -- SETS the text of irrl_last_error(): `check(rc)`;
+#   * csrc/lstm_kernels.hip -- irrl_lstm_seq_forward[_x|_bf16], irrl_lstm_seq_backward[_x|_bf16], irrl_lstm_policy_step, irrl_mlp_policy_step,
+#     irrl_sum_rows -- returns non-zero and nothing else (irrl_last_error() would be some earlier call's text): `check_rc(rc, name, **dims)`.
 def check(rc):
     if rc != 0:
         raise RuntimeError("irrl_env: " + last_error())
+
+
+def check_rc(rc, name, **dims):
+    if rc != 0:
+        raise RuntimeError("%s failed (rc=%d%s)" % (name, rc, "".join(", %s=%s" % kv for kv in dims.items())))
+
+
+# argument marshalling: the one place where tensors and streams turn into C pointers
+def ptr(t):
+    """address of a tensor's first element; None stays None (the C side sees NULL: an optional argument)"""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream_ptr(device):
+    """torch's current stream on `device`: every launch of the library is ordered on it (and recorded by a graph capture)"""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def contig(t):
+    return t if t.is_contiguous() else t.contiguous()

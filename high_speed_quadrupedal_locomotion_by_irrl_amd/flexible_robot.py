@@ -36,10 +36,9 @@ def _np_bool(a, shape, name):
 
 
 def _dev_ptr(t, shape, dtypes, name):
-    import torch
     if tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.dtype not in dtypes:
         raise TypeError("%s must be a contiguous CUDA tensor of shape %s and dtype in %s" % (name, tuple(shape), dtypes))
-    return C.c_void_p(t.data_ptr())
+    return _lib.ptr(t)
 
 
 class FlexibleGymEnv(object):
@@ -71,8 +70,7 @@ class FlexibleGymEnv(object):
 
     # -- helpers --
     def _sync_stream(self):
-        import torch
-        self._lib.irrl_env_set_stream(self._h, C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream))
+        self._lib.irrl_env_set_stream(self._h, _lib.stream_ptr(self._device))
 
     @property
     def device_index(self):

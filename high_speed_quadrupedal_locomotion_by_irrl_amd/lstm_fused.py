@@ -14,6 +14,7 @@ import weakref
 import torch
 
 from . import _lib
+from ._lib import check_rc, ptr, stream_ptr
 
 _PERM_CACHE = {}
 FUSE_WEIGHT_GRADIENTS = True   # backward: dx / dwx / dwh / db inside the sequence kernel
@@ -57,10 +58,6 @@ def _perm(hid, device):
         inv[perm] = torch.arange(4 * hid, device=device)
         _PERM_CACHE[key] = (perm, inv)
     return _PERM_CACHE[key]
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
 
 
 _WCACHE = {}
@@ -160,21 +157,23 @@ class _LstmSeqFn(torch.autograd.Function):
         cseq = None if infer else torch.empty(T, Np, hid, device=x.device, dtype=torch.float32)
         hseq = torch.empty(T, Np, hid, device=x.device, dtype=torch.float32)
         state_out = torch.empty(Np, 2 * hid, device=x.device, dtype=torch.float32)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        stream = stream_ptr(x.device)
         ctx.nsplit = nsplit
         if nsplit:
-            rc = lib.irrl_lstm_seq_forward_bf16(nsplit, hid, T, Np, n_in, _ptr(x_k), _ptr(wx_p), _ptr(b_p), _ptr(wh_p), _ptr(masks_k), _ptr(state0_k),
-                                                None if gates is None else _ptr(gates), None if infer else _ptr(cseq), _ptr(hseq), _ptr(state_out), stream)
+            name = "irrl_lstm_seq_forward_bf16"
+            rc = lib.irrl_lstm_seq_forward_bf16(nsplit, hid, T, Np, n_in, ptr(x_k), ptr(wx_p), ptr(b_p), ptr(wh_p), ptr(masks_k), ptr(state0_k),
+                                                ptr(gates), ptr(cseq), ptr(hseq), ptr(state_out), stream)
         elif n_in <= 48 and FUSE_INPUT_PROJECTION:
             # x wx + b inside the sequence kernel: no [T*N, 4H] zx round trip through HBM
-            rc = lib.irrl_lstm_seq_forward_x(hid, T, Np, n_in, _ptr(x_k), _ptr(wx_p), _ptr(b_p), _ptr(wh_p), _ptr(masks_k), _ptr(state0_k),
-                                             _ptr(gates), _ptr(cseq), _ptr(hseq), _ptr(state_out), stream)
+            name = "irrl_lstm_seq_forward_x"
+            rc = lib.irrl_lstm_seq_forward_x(hid, T, Np, n_in, ptr(x_k), ptr(wx_p), ptr(b_p), ptr(wh_p), ptr(masks_k), ptr(state0_k),
+                                             ptr(gates), ptr(cseq), ptr(hseq), ptr(state_out), stream)
         else:
             zx = torch.addmm(b_p, x_k.reshape(T * Np, n_in), wx_p)             # [T*Np, 4H] in [unit][gate] order
-            rc = lib.irrl_lstm_seq_forward(hid, T, Np, _ptr(zx), _ptr(wh_p), _ptr(masks_k), _ptr(state0_k), _ptr(gates), _ptr(cseq),
-                                           _ptr(hseq), _ptr(state_out), stream)
-        if rc != 0:
-            raise RuntimeError("irrl_lstm_seq_forward failed (rc=%d, hid=%d, T=%d, N=%d)" % (rc, hid, T, Np))
+            name = "irrl_lstm_seq_forward"
+            rc = lib.irrl_lstm_seq_forward(hid, T, Np, ptr(zx), ptr(wh_p), ptr(masks_k), ptr(state0_k), ptr(gates), ptr(cseq),
+                                           ptr(hseq), ptr(state_out), stream)
+        check_rc(rc, name, hid=hid, T=T, N=Np, n_in=n_in)
         if not infer:
             ctx.save_for_backward(x_k, wx_p, wh_p, gates, cseq, hseq, masks_k, state0_k, b_p)
         ctx.dims = (T, N, Np, n_in, hid)
@@ -193,7 +192,7 @@ class _LstmSeqFn(torch.autograd.Function):
         dh_seq = dh_seq.contiguous()
         if Np != N:
             dh_seq = torch.cat([dh_seq, dh_seq.new_zeros(T, Np - N, hid)], 1)
-        stream = C.c_void_p(torch.cuda.current_stream(x_k.device).cuda_stream)
+        stream = stream_ptr(x_k.device)
         if n_in <= 48 and FUSE_WEIGHT_GRADIENTS:
             # one launch: recurrence + dx + per-workgroup dwx / dwh / db partials (no dz tensor, no tall GEMMs)
             nb = Np // 16
@@ -203,31 +202,28 @@ class _LstmSeqFn(torch.autograd.Function):
             dwh_part = torch.empty(nb, hid, 4 * hid, device=dev, dtype=torch.float32)
             db_part = torch.empty(nb * 4, 4 * hid, device=dev, dtype=torch.float32)
             if getattr(ctx, "nsplit", 0):
-                rc = lib.irrl_lstm_seq_backward_bf16(ctx.nsplit, hid, T, Np, n_in, _ptr(gates) if gates is not None else None, _ptr(cseq), _ptr(hseq), _ptr(x_k),
-                                                     _ptr(masks_k), _ptr(state0_k), _ptr(dh_seq), _ptr(wh_p), _ptr(wx_p), _ptr(b_p),
-                                                     _ptr(dx_k) if dx_k is not None else None,
-                                                     _ptr(dwx_part), _ptr(dwh_part), _ptr(db_part), stream)
+                name = "irrl_lstm_seq_backward_bf16"
+                rc = lib.irrl_lstm_seq_backward_bf16(ctx.nsplit, hid, T, Np, n_in, ptr(gates), ptr(cseq), ptr(hseq), ptr(x_k),
+                                                     ptr(masks_k), ptr(state0_k), ptr(dh_seq), ptr(wh_p), ptr(wx_p), ptr(b_p),
+                                                     ptr(dx_k), ptr(dwx_part), ptr(dwh_part), ptr(db_part), stream)
             else:
-                rc = lib.irrl_lstm_seq_backward_x(hid, T, Np, n_in, _ptr(gates), _ptr(cseq), _ptr(hseq), _ptr(x_k), _ptr(masks_k), _ptr(state0_k),
-                                                  _ptr(dh_seq), _ptr(wh_p), _ptr(wx_p), _ptr(dx_k) if dx_k is not None else None,
-                                                  _ptr(dwx_part), _ptr(dwh_part), _ptr(db_part), stream)
-            if rc != 0:
-                raise RuntimeError("irrl_lstm_seq_backward_x failed (rc=%d)" % rc)
+                name = "irrl_lstm_seq_backward_x"
+                rc = lib.irrl_lstm_seq_backward_x(hid, T, Np, n_in, ptr(gates), ptr(cseq), ptr(hseq), ptr(x_k), ptr(masks_k), ptr(state0_k),
+                                                  ptr(dh_seq), ptr(wh_p), ptr(wx_p), ptr(dx_k), ptr(dwx_part), ptr(dwh_part), ptr(db_part), stream)
+            check_rc(rc, name, hid=hid, T=T, N=Np, n_in=n_in)
             # workgroup rows added in one fixed order, gate columns back in the reference's order (the library's reduction over the
             # outer dimension of a [256, 9216] matrix takes 250 us; irrl_sum_rows 10)
             dwx = torch.empty(n_in, 4 * hid, device=dev, dtype=torch.float32)
             dwh = torch.empty(hid, 4 * hid, device=dev, dtype=torch.float32)
             db = torch.empty(4 * hid, device=dev, dtype=torch.float32)
             for part, rows, out in ((dwx_part, nb, dwx), (dwh_part, nb, dwh), (db_part, nb * 4, db)):
-                if lib.irrl_sum_rows(_ptr(part), rows, out.numel(), hid, _ptr(out), stream) != 0:
-                    raise RuntimeError("irrl_sum_rows failed")
+                check_rc(lib.irrl_sum_rows(ptr(part), rows, out.numel(), hid, ptr(out), stream), "irrl_sum_rows", rows=rows, cols=out.numel(), hid=hid)
             dx = dx_k[:, :N] if dx_k is not None else None
             return dx, dwx, dwh, db, None, None, None, None
         dz = torch.empty(T, Np, hid, 4, device=x_k.device, dtype=torch.float32)
-        rc = lib.irrl_lstm_seq_backward(hid, T, Np, _ptr(gates), _ptr(cseq), _ptr(masks_k), _ptr(state0_k), _ptr(dh_seq), _ptr(wh_p),
-                                        _ptr(dz), stream)
-        if rc != 0:
-            raise RuntimeError("irrl_lstm_seq_backward failed (rc=%d)" % rc)
+        rc = lib.irrl_lstm_seq_backward(hid, T, Np, ptr(gates), ptr(cseq), ptr(masks_k), ptr(state0_k), ptr(dh_seq), ptr(wh_p),
+                                        ptr(dz), stream)
+        check_rc(rc, "irrl_lstm_seq_backward", hid=hid, T=T, N=Np)
         dzf = dz.reshape(T * Np, 4 * hid)
         keep = (1.0 - masks_k).unsqueeze(-1)
         hprev = torch.cat([state0_k[:, hid:].unsqueeze(0), hseq[:-1]], 0) * keep     # h_{t-1} as it entered step t
@@ -251,6 +247,72 @@ def supported(x, hid):
 
 
 # ---- the whole policy step of a rollout in one launch (csrc/lstm_kernels.hip: lstm_policy_step_kernel) ----
+# The four wrappers below feed the four entry points of the C-ABI (step / rollout x LSTM / MLP) from the same pieces.
+def _lstm_weight_table(policy, dev):
+    """the 12 [unit][gate]-permuted arrays of the two stacks (actor layers, then critic layers: wx, wh, b each)"""
+    perm = _perm(policy.n_lstm[0], dev)[0]
+    ptrs = []
+    for l in list(policy.lstm_pi) + list(policy.lstm_v):
+        ptrs += [t.data_ptr() for t in _permuted_weights(l.wx, l.wh, l.b, perm)]
+    return (C.c_void_p * 12)(*ptrs)
+
+
+def _mlp_weight_table(policy):
+    """the 8 arrays of MlpPolicy's two [64, 64] stacks (actor w, b per layer, then critic)"""
+    ws = [t for fc in (policy.pi_fc, policy.vf_fc) for l in (fc[0], fc[1]) for t in (l.w, l.b)]
+    assert all(t.is_contiguous() for t in ws)
+    return (C.c_void_p * 8)(*[t.data_ptr() for t in ws])
+
+
+def _head_ptrs(policy):
+    return [ptr(policy.pi.w), ptr(policy.pi.b), ptr(policy.vf.w), ptr(policy.vf.b), ptr(policy.logstd)]
+
+
+def _sampling_args(noise, rng):
+    """-> (noise pointer, rng_on, seed, step, base pointer, env0).  Given `noise` switches the kernel RNG off whatever `rng` says; else
+    rng = (seed, step[, base[, env0]]): seed masked to 32 bits, base an int64 device scalar or None, env0 the global id of env 0
+    (multi-GPU shards); neither: deterministic."""
+    if noise is not None or rng is None:
+        return ptr(noise), 0, 0, 0, None, 0
+    return (None, 1, int(rng[0]) & 0xFFFFFFFF, int(rng[1]), ptr(rng[2]) if len(rng) > 2 else None, int(rng[3]) if len(rng) > 3 else 0)
+
+
+def _outputs(out, N, act, dev):
+    """(action, clipped, value, neglogp): the caller's preallocated quadruple, or a fresh one"""
+    if out is None:
+        out = (torch.empty(N, act, device=dev), torch.empty(N, act, device=dev), torch.empty(N, device=dev), torch.empty(N, device=dev))
+    return out
+
+
+_ROW_BUFFERS = ("mb_obs", "mb_actions", "mb_values", "mb_neglogpacs", "mb_dones")
+
+
+def _required_ptrs(rollout, keys):
+    missing = [k for k in keys if rollout.get(k) is None]
+    if missing:
+        raise KeyError("rollout lacks %s" % ", ".join(missing))
+    return [ptr(rollout[k]) for k in keys]
+
+
+def _step_buffer_ptrs(rollout):
+    """-> (row, 7 pointers) of the step form: no dict = row -1 and no buffer; mb_rewards / prev_reward are optional"""
+    if rollout is None:
+        return -1, [None] * 7
+    return int(rollout["row"]), _required_ptrs(rollout, _ROW_BUFFERS) + [ptr(rollout.get("mb_rewards")), ptr(rollout.get("prev_reward"))]
+
+
+def _rollout_buffer_ptrs(rollout, env_reward, env_extra):
+    """-> (row, 8 pointers) of the rollout form: all six buffers are mandatory, then the env's reward and extra-info rows"""
+    return int(rollout["row"]), _required_ptrs(rollout, _ROW_BUFFERS + ("mb_rewards",)) + [ptr(env_reward), ptr(env_extra)]
+
+
+def _check_rollout_args(N, act, steps, dones, env_reward, env_extra, noise_all, *inplace):
+    assert all(t.is_contiguous() for t in inplace) and dones.is_contiguous() and dones.element_size() == 1
+    assert env_reward.is_contiguous() and env_extra.is_contiguous() and tuple(env_extra.shape) == (N, 6)
+    if noise_all is not None:
+        assert noise_all.is_contiguous() and tuple(noise_all.shape[1:]) == (N, act) and noise_all.shape[0] >= steps
+
+
 def policy_step_supported(policy, obs):
     n = policy.n_lstm
     return (obs.is_cuda and obs.dtype == torch.float32 and len(n) == 2 and n[0] == n[1] and n[0] in (32, 48, 64)
@@ -268,41 +330,19 @@ def policy_step(policy, obs, states, dones, noise=None, rng=None, states_out=Non
     N, ob_dim = obs.shape
     hid, act = policy.n_lstm[0], policy.act_dim
     dev = obs.device
-    perm = _perm(hid, dev)[0]
-    ptrs = []
-    for l in list(policy.lstm_pi) + list(policy.lstm_v):
-        wx_p, wh_p, b_p = _permuted_weights(l.wx, l.wh, l.b, perm)
-        ptrs += [wx_p.data_ptr(), wh_p.data_ptr(), b_p.data_ptr()]
-    warr = (C.c_void_p * 12)(*ptrs)
+    warr = _lstm_weight_table(policy, dev)
     obs = obs.contiguous()
     states = states.contiguous()
     if states_out is None:
         states_out = torch.empty_like(states)
     assert states_out.is_contiguous() and dones.is_contiguous() and dones.element_size() == 1
-    if out is None:
-        out = (torch.empty(N, act, device=dev), torch.empty(N, act, device=dev), torch.empty(N, device=dev), torch.empty(N, device=dev))
-    action, clipped, value, neglogp = out
+    action, clipped, value, neglogp = _outputs(out, N, act, dev)
     if noise is not None:
         noise = noise.contiguous()
-    rng_on, seed, step, base, env0 = 0, 0, 0, None, 0
-    if rng is not None and noise is None:
-        rng_on, seed, step = 1, int(rng[0]) & 0xFFFFFFFF, int(rng[1])
-        base = _ptr(rng[2]) if len(rng) > 2 and rng[2] is not None else None
-        env0 = int(rng[3]) if len(rng) > 3 else 0      # global id of env 0 (multi-GPU shards)
-    if rollout is not None:
-        opt = lambda k: _ptr(rollout[k]) if rollout.get(k) is not None else None
-        row = int(rollout["row"])
-        rptr = [_ptr(rollout["mb_obs"]), _ptr(rollout["mb_actions"]), _ptr(rollout["mb_values"]),
-                _ptr(rollout["mb_neglogpacs"]), _ptr(rollout["mb_dones"]), opt("mb_rewards"), opt("prev_reward")]
-    else:
-        row, rptr = -1, [None] * 7
-    rc = lib.irrl_lstm_policy_step(hid, ob_dim, act, N, _ptr(obs), _ptr(dones), _ptr(states), _ptr(states_out), warr,
-                                   _ptr(policy.pi.w), _ptr(policy.pi.b), _ptr(policy.vf.w), _ptr(policy.vf.b), _ptr(policy.logstd),
-                                   _ptr(noise) if noise is not None else None, rng_on, seed, step, base, env0,
-                                   _ptr(action), _ptr(clipped), _ptr(value), _ptr(neglogp), row,
-                                   *rptr, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError("irrl_lstm_policy_step failed (rc=%d)" % rc)
+    row, rptr = _step_buffer_ptrs(rollout)
+    rc = lib.irrl_lstm_policy_step(hid, ob_dim, act, N, ptr(obs), ptr(dones), ptr(states), ptr(states_out), warr, *_head_ptrs(policy),
+                                   *_sampling_args(noise, rng), ptr(action), ptr(clipped), ptr(value), ptr(neglogp), row, *rptr, stream_ptr(dev))
+    check_rc(rc, "irrl_lstm_policy_step", hid=hid, ob_dim=ob_dim, act_dim=act, N=N)
     return action, clipped, value, neglogp, states_out
 
 
@@ -317,30 +357,13 @@ def policy_rollout(policy, env_impl, steps, obs, states, dones, rng, rollout, ou
     N, ob_dim = obs.shape
     hid, act = policy.n_lstm[0], policy.act_dim
     dev = obs.device
-    perm = _perm(hid, dev)[0]
-    ptrs = []
-    for l in list(policy.lstm_pi) + list(policy.lstm_v):
-        wx_p, wh_p, b_p = _permuted_weights(l.wx, l.wh, l.b, perm)
-        ptrs += [wx_p.data_ptr(), wh_p.data_ptr(), b_p.data_ptr()]
-    warr = (C.c_void_p * 12)(*ptrs)
-    assert obs.is_contiguous() and states.is_contiguous() and dones.is_contiguous() and dones.element_size() == 1
-    assert env_reward.is_contiguous() and env_extra.is_contiguous() and tuple(env_extra.shape) == (N, 6)
+    warr = _lstm_weight_table(policy, dev)
+    _check_rollout_args(N, act, steps, dones, env_reward, env_extra, noise_all, obs, states)
     action, clipped, value, neglogp = out
-    rng_on, seed, step, base, env0 = 0, 0, 0, None, 0
-    if noise_all is not None:
-        assert noise_all.is_contiguous() and tuple(noise_all.shape[1:]) == (N, act) and noise_all.shape[0] >= steps
-    elif rng is not None:
-        rng_on, seed, step = 1, int(rng[0]) & 0xFFFFFFFF, int(rng[1])
-        base = _ptr(rng[2]) if len(rng) > 2 and rng[2] is not None else None
-        env0 = int(rng[3]) if len(rng) > 3 else 0      # global id of env 0 (multi-GPU shards)
-    rc = lib.irrl_lstm_rollout(env_impl._h, int(steps), hid, ob_dim, act, _ptr(obs), _ptr(dones), _ptr(states), _ptr(states), warr,
-                               _ptr(policy.pi.w), _ptr(policy.pi.b), _ptr(policy.vf.w), _ptr(policy.vf.b), _ptr(policy.logstd),
-                               _ptr(noise_all) if noise_all is not None else None, rng_on, seed, step, base, env0,
-                               _ptr(action), _ptr(clipped), _ptr(value), _ptr(neglogp), int(rollout["row"]),
-                               _ptr(rollout["mb_obs"]), _ptr(rollout["mb_actions"]), _ptr(rollout["mb_values"]), _ptr(rollout["mb_neglogpacs"]),
-                               _ptr(rollout["mb_dones"]), _ptr(rollout["mb_rewards"]), _ptr(env_reward), _ptr(env_extra), int(fused),
-                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    _lib.check(rc)
+    row, rptr = _rollout_buffer_ptrs(rollout, env_reward, env_extra)
+    _lib.check(lib.irrl_lstm_rollout(env_impl._h, int(steps), hid, ob_dim, act, ptr(obs), ptr(dones), ptr(states), ptr(states), warr, *_head_ptrs(policy),
+                                     *_sampling_args(noise_all, rng), ptr(action), ptr(clipped), ptr(value), ptr(neglogp), row, *rptr, int(fused),
+                                     stream_ptr(dev)))
 
 
 def mlp_policy_step_supported(policy, obs):
@@ -354,34 +377,16 @@ def mlp_policy_step(policy, obs, dones, noise=None, rng=None, rollout=None, out=
     N, ob_dim = obs.shape
     act = policy.act_dim
     dev = obs.device
-    ws = [policy.pi_fc[0].w, policy.pi_fc[0].b, policy.pi_fc[1].w, policy.pi_fc[1].b,
-          policy.vf_fc[0].w, policy.vf_fc[0].b, policy.vf_fc[1].w, policy.vf_fc[1].b]
-    warr = (C.c_void_p * 8)(*[t.data_ptr() for t in ws])
+    warr = _mlp_weight_table(policy)
     obs = obs.contiguous()
     assert dones.is_contiguous() and dones.element_size() == 1
-    if out is None:
-        out = (torch.empty(N, act, device=dev), torch.empty(N, act, device=dev), torch.empty(N, device=dev), torch.empty(N, device=dev))
-    action, clipped, value, neglogp = out
+    action, clipped, value, neglogp = _outputs(out, N, act, dev)
     if noise is not None:
         noise = noise.contiguous()
-    rng_on, seed, step, base, env0 = 0, 0, 0, None, 0
-    if rng is not None and noise is None:
-        rng_on, seed, step = 1, int(rng[0]) & 0xFFFFFFFF, int(rng[1])
-        base = _ptr(rng[2]) if len(rng) > 2 and rng[2] is not None else None
-        env0 = int(rng[3]) if len(rng) > 3 else 0      # global id of env 0 (multi-GPU shards)
-    if rollout is not None:
-        opt = lambda k: _ptr(rollout[k]) if rollout.get(k) is not None else None
-        row = int(rollout["row"])
-        rptr = [_ptr(rollout["mb_obs"]), _ptr(rollout["mb_actions"]), _ptr(rollout["mb_values"]),
-                _ptr(rollout["mb_neglogpacs"]), _ptr(rollout["mb_dones"]), opt("mb_rewards"), opt("prev_reward")]
-    else:
-        row, rptr = -1, [None] * 7
-    rc = lib.irrl_mlp_policy_step(64, ob_dim, act, N, _ptr(obs), _ptr(dones), warr, _ptr(policy.pi.w), _ptr(policy.pi.b), _ptr(policy.vf.w),
-                                  _ptr(policy.vf.b), _ptr(policy.logstd), _ptr(noise) if noise is not None else None, rng_on, seed, step, base, env0,
-                                  _ptr(action), _ptr(clipped), _ptr(value), _ptr(neglogp), row, *rptr,
-                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError("irrl_mlp_policy_step failed (rc=%d)" % rc)
+    row, rptr = _step_buffer_ptrs(rollout)
+    rc = lib.irrl_mlp_policy_step(64, ob_dim, act, N, ptr(obs), ptr(dones), warr, *_head_ptrs(policy), *_sampling_args(noise, rng),
+                                  ptr(action), ptr(clipped), ptr(value), ptr(neglogp), row, *rptr, stream_ptr(dev))
+    check_rc(rc, "irrl_mlp_policy_step", hid=64, ob_dim=ob_dim, act_dim=act, N=N)
     return action, clipped, value, neglogp
 
 
@@ -398,29 +403,14 @@ def mlp_policy_rollout(policy, env_impl, steps, obs, dones, rng, rollout, out, e
     lib = _lib.load()
     N, ob_dim = obs.shape
     act = policy.act_dim
-    dev = obs.device
-    ws = [policy.pi_fc[0].w, policy.pi_fc[0].b, policy.pi_fc[1].w, policy.pi_fc[1].b,
-          policy.vf_fc[0].w, policy.vf_fc[0].b, policy.vf_fc[1].w, policy.vf_fc[1].b]
-    assert all(t.is_contiguous() for t in ws)
-    warr = (C.c_void_p * 8)(*[t.data_ptr() for t in ws])
-    assert obs.is_contiguous() and dones.is_contiguous() and dones.element_size() == 1
-    assert env_reward.is_contiguous() and env_extra.is_contiguous() and tuple(env_extra.shape) == (N, 6)
+    warr = _mlp_weight_table(policy)
+    _check_rollout_args(N, act, steps, dones, env_reward, env_extra, noise_all, obs)
     action, clipped, value, neglogp = out
-    rng_on, seed, step, base, env0 = 0, 0, 0, None, 0
-    if noise_all is not None:
-        assert noise_all.is_contiguous() and tuple(noise_all.shape[1:]) == (N, act) and noise_all.shape[0] >= steps
-    elif rng is not None:
-        rng_on, seed, step = 1, int(rng[0]) & 0xFFFFFFFF, int(rng[1])
-        base = _ptr(rng[2]) if len(rng) > 2 and rng[2] is not None else None
-        env0 = int(rng[3]) if len(rng) > 3 else 0      # global id of env 0 (multi-GPU shards)
     if fused is None:
         if MLP_ROLLOUT not in ("persistent", "direct"):
             raise ValueError("IRRL_MLP_ROLLOUT / lstm_fused.MLP_ROLLOUT is 'persistent' or 'direct', not %r" % (MLP_ROLLOUT,))
         fused = 2 if MLP_ROLLOUT == "persistent" else 0
-    rc = lib.irrl_mlp_rollout(env_impl._h, int(steps), 64, ob_dim, act, _ptr(obs), _ptr(dones), warr, _ptr(policy.pi.w), _ptr(policy.pi.b),
-                              _ptr(policy.vf.w), _ptr(policy.vf.b), _ptr(policy.logstd), _ptr(noise_all) if noise_all is not None else None,
-                              rng_on, seed, step, base, env0, _ptr(action), _ptr(clipped), _ptr(value), _ptr(neglogp), int(rollout["row"]),
-                              _ptr(rollout["mb_obs"]), _ptr(rollout["mb_actions"]), _ptr(rollout["mb_values"]), _ptr(rollout["mb_neglogpacs"]),
-                              _ptr(rollout["mb_dones"]), _ptr(rollout["mb_rewards"]), _ptr(env_reward), _ptr(env_extra), int(fused),
-                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    _lib.check(rc)
+    row, rptr = _rollout_buffer_ptrs(rollout, env_reward, env_extra)
+    _lib.check(lib.irrl_mlp_rollout(env_impl._h, int(steps), 64, ob_dim, act, ptr(obs), ptr(dones), warr, *_head_ptrs(policy),
+                                    *_sampling_args(noise_all, rng), ptr(action), ptr(clipped), ptr(value), ptr(neglogp), row, *rptr, int(fused),
+                                    stream_ptr(obs.device)))

@@ -24,7 +24,6 @@ advantage moments so that normalisation equals the single-process full batch.  `
 The GAE scan runs in the HIP kernel `irrl_gae` (include/irrl_env.h) for CUDA tensors; CPU tensors (only the
 gloo / unit tests create those) take the literal torch transcription below.
 """
-import ctypes as C
 import math
 import os
 import pickle
@@ -33,6 +32,8 @@ import time
 import numpy as np
 import torch
 
+from . import _lib
+from ._lib import contig, ptr, stream_ptr
 from .policies import ActorCriticPolicy, CustomLSTMPolicy, MlpPolicy  # noqa: F401
 
 
@@ -57,7 +58,6 @@ def gae_reference(rewards, values, dones, last_values, last_dones, gamma, lam):
 def gae(rewards, values, dones, last_values, last_dones, gamma, lam):
     """[T,N] f32 rewards/values, [T,N] bool dones (flag before step t), [N] last_values/last_dones."""
     if rewards.is_cuda:
-        from . import _lib
         lib = _lib.load()
         rewards, values = rewards.contiguous(), values.contiguous()
         d8 = dones.to(torch.uint8).contiguous()
@@ -65,10 +65,8 @@ def gae(rewards, values, dones, last_values, last_dones, gamma, lam):
         lv = last_values.contiguous()
         adv, ret = torch.empty_like(rewards), torch.empty_like(rewards)
         T, N = rewards.shape
-        stream = torch.cuda.current_stream(rewards.device).cuda_stream
-        _lib.check(lib.irrl_gae(T, N, C.c_void_p(rewards.data_ptr()), C.c_void_p(values.data_ptr()), C.c_void_p(d8.data_ptr()),
-                                C.c_void_p(lv.data_ptr()), C.c_void_p(ld8.data_ptr()), float(gamma), float(lam),
-                                C.c_void_p(adv.data_ptr()), C.c_void_p(ret.data_ptr()), C.c_void_p(stream)))
+        _lib.check(lib.irrl_gae(T, N, ptr(rewards), ptr(values), ptr(d8), ptr(lv), ptr(ld8), float(gamma), float(lam), ptr(adv), ptr(ret),
+                                stream_ptr(rewards.device)))
         return adv, ret
     return gae_reference(rewards, values, dones, last_values, last_dones, gamma, lam)
 
@@ -93,18 +91,15 @@ class _FusedPPOLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mean, vpred, logstd, actions, returns, old_values, old_neglogp, adv_stats, cliprange, ent_coef, vf_coef):
-        from . import _lib
         lib = _lib.load()
         A = mean.shape[-1]
         M = vpred.numel()
         mean_c, v_c = mean.contiguous(), vpred.contiguous()
         d_mean, d_v = torch.empty_like(mean_c), torch.empty_like(v_c)
         partials = torch.empty(_FusedPPOLoss.N_BLOCKS, 4 + A, device=mean.device, dtype=torch.float32)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        _lib.check(lib.irrl_ppo_loss(M, A, p(mean_c), p(logstd.contiguous()), p(v_c), p(actions.contiguous()), p(returns.contiguous()),
-                                     p(old_values.contiguous()), p(old_neglogp.contiguous()), p(adv_stats), float(cliprange), float(vf_coef),
-                                     p(d_mean), p(d_v), p(partials), _FusedPPOLoss.N_BLOCKS,
-                                     C.c_void_p(torch.cuda.current_stream(mean.device).cuda_stream)))
+        _lib.check(lib.irrl_ppo_loss(M, A, ptr(mean_c), ptr(logstd.contiguous()), ptr(v_c), ptr(actions.contiguous()), ptr(returns.contiguous()),
+                                     ptr(old_values.contiguous()), ptr(old_neglogp.contiguous()), ptr(adv_stats), float(cliprange), float(vf_coef),
+                                     ptr(d_mean), ptr(d_v), ptr(partials), _FusedPPOLoss.N_BLOCKS, stream_ptr(mean.device)))
         sums = partials.sum(0)
         pg, vf, kl, cf = sums[0] / M, sums[1] / M, sums[2] / M, sums[3] / M
         ent = (logstd + 0.5 * (math.log(2.0 * math.pi) + 1.0)).sum()
@@ -133,7 +128,6 @@ class _FusedHeadsLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h_pi, h_v, pi_w, pi_b, vf_w, vf_b, logstd, actions, returns, old_values, old_neglogp, adv_stats, cliprange, ent_coef, vf_coef,
                 unit_grad=False):
-        from . import _lib
         lib = _lib.load()
         ctx.unit_grad = bool(unit_grad)
         H, A = h_pi.shape[-1], pi_w.shape[1]
@@ -142,11 +136,10 @@ class _FusedHeadsLoss(torch.autograd.Function):
         d_hp, d_hv = torch.empty_like(hp), torch.empty_like(hv)
         P = 4 + A + A + 1 + H + H * A
         partials = torch.empty(_FusedHeadsLoss.N_BLOCKS, P, device=hp.device, dtype=torch.float32)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        _lib.check(lib.irrl_ppo_heads_loss(M, A, H, p(hp), p(hv), p(pi_w.contiguous()), p(pi_b.contiguous()), p(vf_w.contiguous()), p(vf_b.contiguous()),
-                                           p(logstd.contiguous()), p(actions.contiguous()), p(returns.contiguous()), p(old_values.contiguous()),
-                                           p(old_neglogp.contiguous()), p(adv_stats), float(cliprange), float(vf_coef), p(d_hp), p(d_hv), None, None,
-                                           p(partials), _FusedHeadsLoss.N_BLOCKS, C.c_void_p(torch.cuda.current_stream(hp.device).cuda_stream)))
+        _lib.check(lib.irrl_ppo_heads_loss(M, A, H, ptr(hp), ptr(hv), ptr(pi_w.contiguous()), ptr(pi_b.contiguous()), ptr(vf_w.contiguous()), ptr(vf_b.contiguous()),
+                                           ptr(logstd.contiguous()), ptr(actions.contiguous()), ptr(returns.contiguous()), ptr(old_values.contiguous()),
+                                           ptr(old_neglogp.contiguous()), ptr(adv_stats), float(cliprange), float(vf_coef), ptr(d_hp), ptr(d_hv), None, None,
+                                           ptr(partials), _FusedHeadsLoss.N_BLOCKS, stream_ptr(hp.device)))
         sums = partials.sum(0)
         pg, vf, kl, cf = sums[0] / M, sums[1] / M, sums[2] / M, sums[3] / M
         ent = (logstd + 0.5 * (math.log(2.0 * math.pi) + 1.0)).sum()
@@ -185,12 +178,55 @@ MLP_PRECISION = os.environ.get("IRRL_MLP_PRECISION", "bf16x3")
 MLP_RECORDS = os.environ.get("IRRL_MLP_RECORDS", "0") != "0"
 
 
-def _mlp_grads_entry(lib):
-    if MLP_PRECISION == "bf16x3":
-        return lib.irrl_mlp_ppo_grads_bf16
-    if MLP_PRECISION == "f32":
-        return lib.irrl_mlp_ppo_grads
-    raise ValueError("IRRL_MLP_PRECISION / ppo2.MLP_PRECISION is 'bf16x3' or 'f32', not %r" % (MLP_PRECISION,))
+# partial-sum row of the MlpPolicy gradient kernels, in the order and with the PADDED shapes the kernels write it (csrc/mlp_update.hpp
+# IRRL_MLP_P_*: W1 has 48 input rows for 35 observations, the head 16 columns for 12 actions / 1 value): (name, rows, cols)
+_MLP_PARTIAL_PIECES = (("scalars", 1, 4), ("dlogstd", 1, 16), ("db1", 1, 64), ("db2", 1, 64), ("db3", 1, 16),
+                       ("dW1", 48, 64), ("dW2", 64, 64), ("dW3", 64, 16))
+MLP_PARTIAL_LAYOUT = {}       # name -> (offset, rows, cols); the pieces tile [0, MLP_PARTIAL_LEN)
+MLP_PARTIAL_LEN = 0           # IRRL_MLP_P
+for _name, _r, _c in _MLP_PARTIAL_PIECES:
+    MLP_PARTIAL_LAYOUT[_name] = (MLP_PARTIAL_LEN, _r, _c)
+    MLP_PARTIAL_LEN += _r * _c
+MLP_RECORD_FLOATS = 64        # IRRL_MLP_REC: one 256-byte record per sample
+
+
+def _mlp_nets(policy):
+    return ((policy.pi_fc, policy.pi), (policy.vf_fc, policy.vf))
+
+
+def _mlp_pieces(policy, kind):
+    """[(piece of network `kind`'s partial-sum row, the parameter whose gradient its top-left corner holds)]"""
+    fc, head = _mlp_nets(policy)[kind]
+    pieces = [("db1", fc[0].b), ("db2", fc[1].b), ("db3", head.b), ("dW1", fc[0].w), ("dW2", fc[1].w), ("dW3", head.w)]
+    return pieces + ([("dlogstd", policy.logstd)] if kind == 0 else [])
+
+
+def _mlp_piece_of(row, name, prm):
+    """the entries of piece `name` of a partial-sum row (or of anything indexed like one) that belong to `prm`, in the parameter's shape"""
+    o, r, c = MLP_PARTIAL_LAYOUT[name]
+    rows, cols = prm.shape if prm.dim() == 2 else (1, prm.numel())
+    assert rows <= r and cols <= c
+    return row[o:o + r * c].reshape(r, c)[:rows, :cols].reshape(prm.shape)
+
+
+def _launch_mlp_grads(policy, partials, n, index, obs, actions, returns, old_values, old_neglogp, adv_stats, cliprange, vf_coef, rec=None):
+    """The two networks' gradient kernels (policy, then value) over `n` samples into partials [2, n_blocks, MLP_PARTIAL_LEN].  Entry point by
+    MLP_PRECISION (read now) and by `rec`: packed records are read by the bf16x3 kernels only, otherwise the five (contiguous) arrays are."""
+    lib = _lib.load()
+    assert lib.irrl_mlp_ppo_partial_len() == MLP_PARTIAL_LEN == partials.shape[-1]
+    if index is not None:
+        assert index.dtype == torch.int64 and index.is_contiguous()
+    if MLP_PRECISION not in ("bf16x3", "f32"):
+        raise ValueError("IRRL_MLP_PRECISION / ppo2.MLP_PRECISION is 'bf16x3' or 'f32', not %r" % (MLP_PRECISION,))
+    use_rec = rec is not None and MLP_PRECISION == "bf16x3"
+    entry = lib.irrl_mlp_ppo_grads_bf16_rec if use_rec else lib.irrl_mlp_ppo_grads_bf16 if MLP_PRECISION == "bf16x3" else lib.irrl_mlp_ppo_grads
+    n_blocks, stream = partials.shape[1], stream_ptr(obs.device)
+    for kind, (fc, head) in enumerate(_mlp_nets(policy)):
+        samples = (ptr(rec),) if use_rec else (obs.shape[-1], fc[0].w.shape[1], actions.shape[-1], ptr(obs), ptr(actions), ptr(returns),
+                                               ptr(old_values), ptr(old_neglogp))
+        weights = [ptr(contig(t)) for t in (fc[0].w, fc[0].b, fc[1].w, fc[1].b, head.w, head.b, policy.logstd)]
+        _lib.check(entry(kind, n, ptr(index), *samples, *weights, ptr(adv_stats), float(cliprange), float(vf_coef), ptr(partials[kind]), n_blocks,
+                         stream))
 
 
 def mlp_ppo_grads_supported(policy, obs):
@@ -207,43 +243,26 @@ def mlp_ppo_grads(policy, obs, actions, returns, old_values, old_neglogp, adv_st
     in two launches (policy network, value network; csrc/mlp_update.hpp) -- the whole of ppo2.py:243-298's graph evaluation.
     obs / actions / returns / old_values / old_neglogp are the FLAT rollout arrays; index (int64 device vector) picks the
     minibatch's rows in place (None: all rows).  -> (loss, stats[pg, vf, entropy, approxkl, clipfrac], {parameter: gradient})."""
-    from . import _lib
     lib = _lib.load()
     dev = obs.device
     n = int(index.numel()) if index is not None else int(returns.numel())
-    P = lib.irrl_mlp_ppo_partial_len()
+    P = MLP_PARTIAL_LEN
     partials = torch.empty(2, n_blocks, P, device=dev, dtype=torch.float32)
-    p = lambda t: C.c_void_p(t.data_ptr())
-    c = lambda t: t if t.is_contiguous() else t.contiguous()
-    obs, actions, returns, old_values, old_neglogp = c(obs), c(actions), c(returns), c(old_values), c(old_neglogp)
-    ip = p(index) if index is not None else None
-    if index is not None:
-        assert index.dtype == torch.int64 and index.is_contiguous()
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    nets = ((0, policy.pi_fc, policy.pi), (1, policy.vf_fc, policy.vf))
-    for kind, fc, head in nets:
-        _lib.check(_mlp_grads_entry(lib)(kind, n, ip, obs.shape[-1], fc[0].w.shape[1], actions.shape[-1], p(obs), p(actions), p(returns),
-                                          p(old_values), p(old_neglogp), p(c(fc[0].w)), p(c(fc[0].b)), p(c(fc[1].w)), p(c(fc[1].b)),
-                                          p(c(head.w)), p(c(head.b)), p(c(policy.logstd)), p(adv_stats), float(cliprange), float(vf_coef),
-                                          p(partials[kind]), n_blocks, stream))
+    obs, actions, returns, old_values, old_neglogp = contig(obs), contig(actions), contig(returns), contig(old_values), contig(old_neglogp)
+    _launch_mlp_grads(policy, partials, n, index, obs, actions, returns, old_values, old_neglogp, adv_stats, cliprange, vf_coef)
     sums = torch.empty(2, P, device=dev, dtype=torch.float32)   # workgroups added in one fixed order
     for kind in (0, 1):
-        if lib.irrl_sum_rows(p(partials[kind]), n_blocks, P, 0, p(sums[kind]), stream) != 0:
-            raise RuntimeError("irrl_sum_rows failed")
+        _lib.check_rc(lib.irrl_sum_rows(ptr(partials[kind]), n_blocks, P, 0, ptr(sums[kind]), stream_ptr(dev)), "irrl_sum_rows", rows=n_blocks, cols=P)
     A = actions.shape[-1]
     sc = sums[:, :4] / n                                        # per-sample means: [pg, kl, clipfrac, -] and [vf, -, -, -]
     pg, kl, cf, vf = sc[0, 0], sc[0, 1], sc[0, 2], sc[1, 0]
     ent = policy.logstd.detach().sum() + 0.5 * (math.log(2.0 * math.pi) + 1.0) * A
     loss = (pg - ent * ent_coef + vf * vf_coef) if want_loss else None
-    grads = {policy.logstd: (sums[0, 4:4 + A] - ent_coef).reshape(policy.logstd.shape)}
-    o1, o2, o3, w1, w2, w3 = 20, 84, 148, 164, 164 + 48 * 64, 164 + 48 * 64 + 64 * 64
-    for kind, fc, head in nets:
-        r = sums[kind]
-        out = head.w.shape[1]
-        grads[fc[0].b], grads[fc[1].b], grads[head.b] = r[o1:o1 + 64], r[o2:o2 + 64], r[o3:o3 + out]
-        grads[fc[0].w] = r[w1:w1 + 48 * 64].view(48, 64)[:35]
-        grads[fc[1].w] = r[w2:w2 + 64 * 64].view(64, 64)
-        grads[head.w] = r[w3:w3 + 64 * 16].view(64, 16)[:, :out]
+    grads = {}
+    for kind in (0, 1):
+        for name, prm in _mlp_pieces(policy, kind):
+            g = _mlp_piece_of(sums[kind], name, prm)
+            grads[prm] = g - ent_coef if name == "dlogstd" else g
     return loss, torch.stack([pg, vf, ent, kl, cf]), grads
 
 
@@ -322,6 +341,8 @@ class FlatParams(object):
                 self.grad_views.append(self.grad[off:off + p.numel()].view_as(p))
         self._dirty = [False] * len(self.params)      # slot holds a gradient some earlier step wrote
         self.offset_of = {id(p): off for p, off in zip(self.params, self.offsets)}
+        self.mlp_maps = {}         # ent_coef -> (map, add) of `_mlp_scatter_map`: they describe THIS buffer's slots and go with it
+        self.mlp_partials = {}     # n_blocks -> the gradient kernels' [2, n_blocks, MLP_PARTIAL_LEN] scratch
 
     def gather(self):
         """autograd left the gradients in separate tensors (p.grad): ONE multi-tensor copy into the flat buffer; slots of parameters
@@ -346,57 +367,39 @@ class FlatParams(object):
             p.grad = gv
 
 
-_MLP_MAPS = {}
-
-
 def _mlp_scatter_map(policy, flat, ent_coef):
-    """column of a partial-sum row of the MlpPolicy gradient kernels (csrc/mlp_update.hpp: scalars[4] | d logstd[16] | d b1[64] | d b2[64] |
-    d b3[16] | d W1[48][64] | d W2[64][64] | d W3[64][16]) -> slot of the flat gradient buffer; the four scalars of network k go to the
-    tail slots n + 4 k ..; `add` carries -ent_coef for d logstd.  Built once per (policy, ent_coef)."""
-    from . import _lib
-    key = (id(flat), float(ent_coef))
-    hit = _MLP_MAPS.get(key)
-    if hit is not None:
-        return hit
-    P = _lib.load().irrl_mlp_ppo_partial_len()
-    A = policy.act_dim
-    mp = np.full((2, P), -1, np.int32)
-    add = np.zeros((2, P), np.float32)
-    o1, o2, o3, w1, w2, w3 = 20, 84, 148, 164, 164 + 48 * 64, 164 + 48 * 64 + 64 * 64
-    off = flat.offset_of
-    for kind, fc, head in ((0, policy.pi_fc, policy.pi), (1, policy.vf_fc, policy.vf)):
-        out = head.w.shape[1]
-        mp[kind, 0:4] = flat.n + 4 * kind + np.arange(4)
-        if kind == 0:
-            mp[0, 4:4 + A] = off[id(policy.logstd)] + np.arange(A)
-            add[0, 4:4 + A] = -float(ent_coef)
-        mp[kind, o1:o1 + 64] = off[id(fc[0].b)] + np.arange(64)
-        mp[kind, o2:o2 + 64] = off[id(fc[1].b)] + np.arange(64)
-        mp[kind, o3:o3 + out] = off[id(head.b)] + np.arange(out)
-        k35 = np.arange(35)[:, None] * 64 + np.arange(64)[None, :]
-        mp[kind, w1:w1 + 35 * 64] = (off[id(fc[0].w)] + k35).reshape(-1)
-        mp[kind, w2:w2 + 64 * 64] = off[id(fc[1].w)] + np.arange(64 * 64)
-        cols = (w3 + np.arange(64)[:, None] * 16 + np.arange(out)[None, :]).reshape(-1)
-        mp[kind, cols] = (off[id(head.w)] + np.arange(64)[:, None] * out + np.arange(out)[None, :]).reshape(-1)
-    dev = flat.grad.device
-    hit = (torch.from_numpy(mp).to(dev), torch.from_numpy(add).to(dev), P, {})
-    _MLP_MAPS.clear()          # one live learner per process is the rule; do not keep dead ones' buffers
-    _MLP_MAPS[key] = hit
+    """column of a partial-sum row of the MlpPolicy gradient kernels (MLP_PARTIAL_LAYOUT) -> slot of the flat gradient buffer (-1: padding, dropped);
+    the four scalars of network k go to the tail slots n + 4 k ..; `add` carries -ent_coef for d logstd.  Built once per (flat, ent_coef) and kept
+    on `flat`."""
+    key = float(ent_coef)
+    hit = flat.mlp_maps.get(key)
+    if hit is None:
+        P = MLP_PARTIAL_LEN
+        mp = np.full((2, P), -1, np.int32)
+        add = np.zeros((2, P), np.float32)
+        columns = np.arange(P)
+        for kind in (0, 1):
+            mp[kind, 0:4] = flat.n + 4 * kind + np.arange(4)
+            for name, prm in _mlp_pieces(policy, kind):
+                cols = _mlp_piece_of(columns, name, prm).reshape(-1)
+                mp[kind, cols] = flat.offset_of[id(prm)] + np.arange(prm.numel())
+                if name == "dlogstd":
+                    add[kind, cols] = -key
+        dev = flat.grad.device
+        hit = flat.mlp_maps[key] = (torch.from_numpy(mp).to(dev), torch.from_numpy(add).to(dev))
     return hit
 
 
 def mlp_pack_records(obs, actions, returns, old_values, old_neglogp):
     """The five per-sample arrays of the flat rollout as ONE 256-byte record per sample (csrc/mlp_update.hpp IRRL_MLP_REC; built once per
     update): a shuffled minibatch row then costs two 128-byte lines instead of seven or eight (`irrl_mlp_ppo_grads_bf16_rec`)."""
-    from . import _lib
     lib = _lib.load()
+    assert lib.irrl_mlp_record_floats() == MLP_RECORD_FLOATS
     n = int(returns.numel())
-    rec = torch.empty(n, lib.irrl_mlp_record_floats(), device=obs.device, dtype=torch.float32)
+    rec = torch.empty(n, MLP_RECORD_FLOATS, device=obs.device, dtype=torch.float32)
     assert rec.data_ptr() % 256 == 0
-    p = lambda t: C.c_void_p(t.data_ptr())
-    c = lambda t: t if t.is_contiguous() else t.contiguous()
-    _lib.check(lib.irrl_mlp_pack_records(n, p(c(obs)), p(c(actions)), p(c(returns)), p(c(old_values)), p(c(old_neglogp)), p(rec),
-                                         C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)))
+    _lib.check(lib.irrl_mlp_pack_records(n, ptr(contig(obs)), ptr(contig(actions)), ptr(contig(returns)), ptr(contig(old_values)),
+                                         ptr(contig(old_neglogp)), ptr(rec), stream_ptr(obs.device)))
     return rec
 
 
@@ -405,31 +408,16 @@ def mlp_ppo_grads_flat(policy, flat, obs, actions, returns, old_values, old_negl
     `irrl_sum_rows_scatter` launch for both networks instead of two row sums + one copy per parameter).  -> the step's raw
     statistics row [8 sums | logstd 12] (one small launch; `mlp_stats_rows` turns the rows of an update into the logged means).
     rec: the samples as packed records (`mlp_pack_records`; bf16x3 kernels only) -- same values, bit-identical gradients."""
-    from . import _lib
     lib = _lib.load()
     dev = obs.device
     n = int(index.numel()) if index is not None else int(returns.numel())
-    mp, add, P, cache = _mlp_scatter_map(policy, flat, ent_coef)
-    partials = cache.get(n_blocks)
+    mp, add = _mlp_scatter_map(policy, flat, ent_coef)
+    partials = flat.mlp_partials.get(n_blocks)
     if partials is None:
-        partials = cache[n_blocks] = torch.empty(2, n_blocks, P, device=dev, dtype=torch.float32)
-    p = lambda t: C.c_void_p(t.data_ptr())
-    c = lambda t: t if t.is_contiguous() else t.contiguous()
-    obs, actions, returns, old_values, old_neglogp = c(obs), c(actions), c(returns), c(old_values), c(old_neglogp)
-    ip = p(index) if index is not None else None
-    if index is not None:
-        assert index.dtype == torch.int64 and index.is_contiguous()
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    for kind, fc, head in ((0, policy.pi_fc, policy.pi), (1, policy.vf_fc, policy.vf)):
-        if rec is not None and MLP_PRECISION == "bf16x3":
-            _lib.check(lib.irrl_mlp_ppo_grads_bf16_rec(kind, n, ip, p(rec), p(fc[0].w), p(fc[0].b), p(fc[1].w), p(fc[1].b), p(head.w), p(head.b),
-                                                       p(policy.logstd), p(adv_stats), float(cliprange), float(vf_coef), p(partials[kind]), n_blocks, stream))
-            continue
-        _lib.check(_mlp_grads_entry(lib)(kind, n, ip, obs.shape[-1], fc[0].w.shape[1], actions.shape[-1], p(obs), p(actions), p(returns),
-                                          p(old_values), p(old_neglogp), p(fc[0].w), p(fc[0].b), p(fc[1].w), p(fc[1].b),
-                                          p(head.w), p(head.b), p(policy.logstd), p(adv_stats), float(cliprange), float(vf_coef),
-                                          p(partials[kind]), n_blocks, stream))
-    _lib.check(lib.irrl_sum_rows_scatter(p(partials), 2, n_blocks, P, p(mp), p(add), p(flat.grad), stream))
+        partials = flat.mlp_partials[n_blocks] = torch.empty(2, n_blocks, MLP_PARTIAL_LEN, device=dev, dtype=torch.float32)
+    obs, actions, returns, old_values, old_neglogp = contig(obs), contig(actions), contig(returns), contig(old_values), contig(old_neglogp)
+    _launch_mlp_grads(policy, partials, n, index, obs, actions, returns, old_values, old_neglogp, adv_stats, cliprange, vf_coef, rec=rec)
+    _lib.check(lib.irrl_sum_rows_scatter(ptr(partials), 2, n_blocks, MLP_PARTIAL_LEN, ptr(mp), ptr(add), ptr(flat.grad), stream_ptr(dev)))
     for i in range(len(flat._dirty)):
         flat._dirty[i] = True
     return torch.cat([flat.grad[flat.n:flat.n + 8], policy.logstd.detach().reshape(-1)])
@@ -503,6 +491,8 @@ class Runner(object):
         self.use_graph = (dev.type == "cuda") if use_graph is None else bool(use_graph)
         self._graph = None
         self._graph_epoch = 0
+        self._actor_only_epoch, self._actor_only_ok = None, False   # `_actor_only_supported`: the answer and the pool's params_epoch it holds for
+        self._fallback_noted = False                                # `_note_rollout_fallback` printed its line
         # sampling noise: the model's seeded generator; under graph capture it is registered with the graph
         self._gen = model.generator
         # single-launch policy step + raw env step when the policy / env pair supports it (LSTM policy on the GPU)
@@ -570,11 +560,10 @@ class Runner(object):
         Crutial off and the published contact rule; MlpPolicy has no critic stack to take off the path.  The answer is kept per
         `params_epoch` of the pool (as `_maybe_capture` keeps its graph): the time-step setters change which kernels a pool runs."""
         epoch = getattr(getattr(self.env, "wrapper", None), "params_epoch", 0)
-        if getattr(self, "_actor_only_epoch", None) != epoch:
+        if self._actor_only_epoch != epoch:
             pol = self.model.policy
             ok = False
             if hasattr(pol, "lstm_v") and hasattr(getattr(self.env, "wrapper", None), "_h"):
-                from . import _lib
                 rc = _lib.load().irrl_lstm_rollout_supports(self.env.wrapper._h, int(pol.n_lstm[0]), 3)
                 if rc < 0:
                     _lib.check(1)
@@ -586,12 +575,11 @@ class Runner(object):
         """One line, once per runner, at the first run() that asks for a persistent rollout the pool has no kernel for: the rollout about to
         run is two launches per step.  Asked through the C-ABI per run() until then (nothing is launched); names the pool's kernel variant and
         why it has no such kernel."""
-        if getattr(self, "_fallback_noted", False):
+        if self._fallback_noted:
             return                                       # (set where the line is printed: a run() that did not ask for a persistent rollout uses nothing up)
         raw = getattr(self.env, "wrapper", None)
         if not hasattr(raw, "_h") or not hasattr(raw, "kernel_variant"):
             return
-        from . import _lib
         pol, lib = self.model.policy, _lib.load()
         if hasattr(pol, "lstm_v"):
             if mode < 2:
@@ -832,27 +820,27 @@ class PPO2(object):
         self.fused_mlp = True    # MlpPolicy: forward + loss + every gradient in one launch per network (tests flip it likewise)
         self.fused_heads = True  # ... including the policy / value heads and their gradients (LSTM policy, 48-unit latents)
         self.log = []
+        self._shuffles = 0       # minibatch permutations drawn so far (`_sample_order`)
 
     # -- one optimizer step on one minibatch (ppo2.py:243-298) --
-    def _adv_stats_indexed(self, returns, values, index):
+    def _adv_stats_indexed(self, returns, values, index, rec=None, adv=None):
         """adv_stats = (mean, std) of the raw advantages of the minibatch `index` picks from the flat rollout, float32 [2] on the device:
-        two launches of `irrl_adv_moments` instead of the gathers, casts and reductions; several ranks all-reduce the sums first."""
-        from . import _lib
+        two launches of `irrl_adv_moments` instead of the gathers, casts and reductions; several ranks all-reduce the sums first.
+        rec: the packed sample records of this update (the advantage is word 51 of a record); adv: returns - values of the whole rollout,
+        formed once per update (one gather, not two).  `update` makes one of the two and hands it down."""
         lib = _lib.load()
         dev = returns.device
         scratch = torch.empty(2 * 256 + 3, device=dev, dtype=torch.float64)
         stats = torch.empty(2, device=dev, dtype=torch.float32)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        rec = getattr(self, "_records", None)       # the packed sample records of this update (`update`): the advantage is word 51 of a record
-        adv = getattr(self, "_flat_adv", None)      # returns - values of the whole rollout, formed once per update (`update`): one gather, not two
-        if rec is not None and rec.shape[0] == returns.numel():
-            _lib.check(lib.irrl_adv_moments_rec(int(index.numel()), p(index), p(rec), p(scratch), 256, p(scratch[512:]),
-                                                p(stats) if not self.collective else None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        out = (ptr(scratch), 256, ptr(scratch[512:]), ptr(stats) if not self.collective else None, stream_ptr(dev))
+        if rec is not None:
+            assert rec.shape[0] == returns.numel()
+            _lib.check(lib.irrl_adv_moments_rec(int(index.numel()), ptr(index), ptr(rec), *out))
         else:
-            if adv is not None and adv.numel() == returns.numel():
+            if adv is not None:
+                assert adv.numel() == returns.numel()
                 returns, values = adv, None
-            _lib.check(lib.irrl_adv_moments(int(index.numel()), p(index), p(returns), p(values) if values is not None else None, p(scratch), 256, p(scratch[512:]),
-                                            p(stats) if not self.collective else None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            _lib.check(lib.irrl_adv_moments(int(index.numel()), ptr(index), ptr(returns), ptr(values), *out))
         if not self.collective:
             return stats
         mean, var = self._adv_moments(None, None, moments=scratch[512:])
@@ -872,9 +860,10 @@ class PPO2(object):
         return mean, var
 
     def _train_step(self, lr_now, cliprange_now, obs, returns, masks, actions, values, neglogpacs, states=None, adv_moments=None, index=None,
-                    grad_weight=1.0, empty=False):
+                    grad_weight=1.0, empty=False, rec=None, adv=None):
         """index: the arrays are the FLAT rollout and `index` picks this minibatch's rows (MlpPolicy's gradient kernels read them
-        in place); otherwise the arrays are the minibatch.  grad_weight: this rank's share of a GLOBAL minibatch that the ranks hold
+        in place; rec / adv: the update's packed records or returns - values, see `_adv_stats_indexed`); otherwise the arrays are the
+        minibatch.  grad_weight: this rank's share of a GLOBAL minibatch that the ranks hold
         unequal parts of (`_global_minibatches`): its mean gradient is weighted m_r * world / m before the all-reduce, so that the
         averaged sum is the mean over the global minibatch's m samples; empty: this rank holds none of them (it still joins the collectives)."""
         if empty:
@@ -887,9 +876,9 @@ class PPO2(object):
             if adv_moments is not None:
                 adv_stats = torch.stack([adv_moments[0], torch.sqrt(adv_moments[1])]).to(torch.float32)
             else:
-                adv_stats = self._adv_stats_indexed(returns, values, index)
+                adv_stats = self._adv_stats_indexed(returns, values, index, rec=rec, adv=adv)
             row = mlp_ppo_grads_flat(self.policy, self.flat, obs, actions, returns, values, neglogpacs, adv_stats, cliprange_now, self.ent_coef,
-                                     self.vf_coef, index, rec=getattr(self, "_records", None))
+                                     self.vf_coef, index, rec=rec)
             self._apply_gradients(lr_now, gathered=True, weight=grad_weight)
             return row      # raw sums: `update` turns the rows of all steps into the logged means at once (mlp_stats_rows)
         mean, var = adv_moments if adv_moments is not None else self._adv_moments(returns, values)
@@ -933,12 +922,10 @@ class PPO2(object):
         if self.collective:
             torch.distributed.all_reduce(fl.grad[:fl.n])              # C1: the only collective of the step besides the 3 moment floats
         if self.flat_optim and self.device.type == "cuda":
-            from . import _lib
             fl.step += 1
-            p = lambda t: C.c_void_p(t.data_ptr())
-            _lib.check(_lib.load().irrl_clip_adam(fl.n, p(fl.theta), p(fl.grad), p(fl.m), p(fl.v), 1.0 / self.world,
+            _lib.check(_lib.load().irrl_clip_adam(fl.n, ptr(fl.theta), ptr(fl.grad), ptr(fl.m), ptr(fl.v), 1.0 / self.world,
                                                   float(self.max_grad_norm) if self.max_grad_norm is not None else 0.0, float(lr_now), 0.9, 0.999, 1e-5,
-                                                  fl.step, None, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+                                                  fl.step, None, stream_ptr(self.device)))
             if hasattr(self.policy, "prepare"):
                 self.policy.prepare()      # the LSTM kernels read [unit][gate]-permuted COPIES of the weights
             return
@@ -957,13 +944,11 @@ class PPO2(object):
         """np.random.shuffle(inds) of ppo2.py:366-367 as a keyed bijection of [0, n) (one launch on the GPU instead of the radix sort behind
         torch.randperm; the numpy twin on the CPU gives the same order): depends on (n, seed, number of shuffles so far) only, so it is the
         same on every rank and on either device."""
-        self._shuffles = getattr(self, "_shuffles", 0) + 1
+        self._shuffles += 1
         key = (self.seed * 1000003 + 12345) & 0xFFFFFFFF
         if self.device.type == "cuda" and n <= (1 << 30):
-            from . import _lib
             out = torch.empty(n, dtype=torch.int64, device=self.device)
-            _lib.check(_lib.load().irrl_random_permutation(n, key, self._shuffles, C.c_void_p(out.data_ptr()),
-                                                           C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+            _lib.check(_lib.load().irrl_random_permutation(n, key, self._shuffles, ptr(out), stream_ptr(self.device)))
             return out
         return torch.from_numpy(feistel_permutation(n, key, self._shuffles)).to(self.device)
 
@@ -1038,9 +1023,10 @@ class PPO2(object):
             flat = {k: batch[k].reshape(n_batch, *batch[k].shape[2:]) for k in ("obs", "returns", "masks", "actions", "values", "neglogpacs")}
             in_place = self.fused_mlp and mlp_ppo_grads_supported(self.policy, flat["obs"])
             # the samples as packed 256-byte records, built once for the update's noptepochs x nminibatches passes (`MLP_RECORDS`; bf16x3 kernels)
-            self._records = (mlp_pack_records(flat["obs"], flat["actions"], flat["returns"], flat["values"], flat["neglogpacs"])
-                             if in_place and MLP_RECORDS and MLP_PRECISION == "bf16x3" else None)
-            self._flat_adv = (flat["returns"] - flat["values"]).contiguous() if in_place and self._records is None else None
+            # (either lives for this update only and is handed to every `_train_step` of it)
+            records = (mlp_pack_records(flat["obs"], flat["actions"], flat["returns"], flat["values"], flat["neglogpacs"])
+                       if in_place and MLP_RECORDS and MLP_PRECISION == "bf16x3" else None)
+            flat_adv = (flat["returns"] - flat["values"]).contiguous() if in_place and records is None else None
             split = self.world > 1 and self.nminibatches > 1      # ONE permutation over ALL ranks' samples (ppo2.py:364-380), every rank keeps its own
             weights = []
             for _ in range(self.noptepochs):
@@ -1057,14 +1043,12 @@ class PPO2(object):
                     weights.append(w / self.world)
                     if in_place:     # the gradient kernels read the minibatch's rows through the index: nothing is gathered
                         losses.append(self._train_step(lr_now, cliprange_now, flat["obs"], flat["returns"], flat["masks"], flat["actions"],
-                                                       flat["values"], flat["neglogpacs"], index=mb.contiguous(), grad_weight=w))
+                                                       flat["values"], flat["neglogpacs"], index=mb.contiguous(), grad_weight=w, rec=records, adv=flat_adv))
                         continue
                     losses.append(self._train_step(lr_now, cliprange_now, flat["obs"][mb], flat["returns"][mb], flat["masks"][mb],
                                                    flat["actions"][mb], flat["values"][mb], flat["neglogpacs"][mb], grad_weight=w))
             if split:
                 # logged means over the GLOBAL minibatches: every rank's rows are sums (kernels) / means (graph) over ITS share
-                self._flat_adv = None
-                self._records = None
                 if in_place:
                     tot = mlp_stats_rows(losses, float(bs * self.world), self.policy.act_dim)
                     tot[:, 2] *= torch.tensor(weights, device=tot.device, dtype=tot.dtype)      # (the entropy column is not a sum over samples)
@@ -1074,8 +1058,6 @@ class PPO2(object):
                 tot = tot / (self.noptepochs * self.nminibatches)
                 torch.distributed.all_reduce(tot)
                 return tot
-            self._flat_adv = None
-            self._records = None
             if in_place:
                 return mlp_stats_rows(losses, float(bs), self.policy.act_dim).mean(0)
         return torch.stack(losses).mean(0)
