@@ -94,6 +94,10 @@ SIGNATURES = {
     "irrl_lstm_rollout_supports": (C.c_int, [vp, C.c_int, C.c_int]),
     "irrl_mlp_rollout_supports": (C.c_int, [vp, C.c_int, C.c_int]),
     "irrl_lstm_rollout": (C.c_int, [vp] + [C.c_int] * 4 + [vp] * 11 + [C.c_int, C.c_uint, C.c_longlong, vp, C.c_int] + [vp] * 4 + [C.c_longlong] + [vp] * 8 + [C.c_int, vp]),
+    # handle, steps, step0, hid, ob, act | weight table + 5 head arrays | depth, 7 state arrays, work | delay, cmd_target | a_cmd, a_vel, a_act,
+    # cmd_mean, cmd_std (host), clip | 8 recorders, stats | stream
+    "irrl_lstm_eval_rollout": (C.c_int, [vp, C.c_int, C.c_longlong] + [C.c_int] * 3 + [vp] * 6 + [C.c_int] + [vp] * 8 + [vp] * 2 + [C.c_float] * 3 + [fp, fp, C.c_int]
+                               + [vp] * 9 + [vp]),
 }
 
 

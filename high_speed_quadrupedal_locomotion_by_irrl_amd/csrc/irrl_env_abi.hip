@@ -20,6 +20,7 @@
 #include "irrl_terrain.hpp"
 #include "irrl_csv.hpp"
 #include "../../include/irrl_env.h"
+#include "eval_rollout.hpp"   // the evaluation loop's kernels (irrl_lstm_eval_rollout below)
 
 #include <cmath>
 #include <string>
@@ -483,6 +484,63 @@ int irrl_lstm_rollout(irrl_env *h, int steps, int hid, int ob_dim, int act_dim, 
       launch_step(h, h->P, (const float *)clipped, obs, env_reward, dones, env_extra);
       if (k + 1 < steps && policy(k + 1) != 0) { g_err = "irrl_lstm_rollout: policy step refused its arguments"; return 1; }
     }
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// The evaluation loop of a trained policy (csrc/eval_rollout.hpp): per control step conditioning -> policy step -> action filter -> env step -> record,
+// plain launches back to back on `hip_stream`.  Stateless: everything that survives a call lives in the caller's buffers, so a second call with
+// step0 + steps continues where the first stopped.  Arguments are refused BEFORE any HIP call.
+int irrl_lstm_eval_rollout(irrl_env *h, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *lstm_w, const float *pi_w,
+                           const float *pi_b, const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring, float *cmd, float *vel_his,
+                           float *act_his, float *lstm_state, uint8_t *done, float *obs, float *work, const int *delay, const float *cmd_target, float a_cmd,
+                           float a_vel, float a_act, const float *cmd_mean, const float *cmd_std, int clip, float *rec_obs_cond, float *rec_act_clipped,
+                           float *rec_act_applied, float *rec_body, float *rec_torque, float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats,
+                           void *hip_stream) {
+  if (!h) { g_err = "irrl_lstm_eval_rollout: NULL handle"; return 1; }
+  if (steps < 0 || step0 < 0) { g_err = "irrl_lstm_eval_rollout: steps >= 0, step0 >= 0"; return 1; }
+  if (depth < 1) { g_err = "irrl_lstm_eval_rollout: the delay line needs a depth D >= 1"; return 1; }
+  if (hid != 32 && hid != 48 && hid != 64) { g_err = "irrl_lstm_eval_rollout: hid is 32, 48 or 64"; return 1; }
+  if (ob_dim != 35 || act_dim != 12) { g_err = "irrl_lstm_eval_rollout: ob 35, act 12"; return 1; }
+  if (!(ring && cmd && vel_his && act_his && lstm_state && done && obs && work && delay && cmd_target && cmd_mean && cmd_std)) {
+    g_err = "irrl_lstm_eval_rollout: NULL evaluator state / parameter pointer"; return 1;
+  }
+  if (!(lstm_w && pi_w && pi_b && vf_w && vf_b && logstd)) { g_err = "irrl_lstm_eval_rollout: NULL weight pointer"; return 1; }
+  for (int i = 0; i < 12; i++)
+    if (!lstm_w[i]) { g_err = "irrl_lstm_eval_rollout: the LSTM weight table has a NULL entry"; return 1; }
+  if (!(a_cmd > 0.0f && a_cmd <= 1.0f && a_vel > 0.0f && a_vel <= 1.0f && a_act > 0.0f && a_act <= 1.0f)) {
+    g_err = "irrl_lstm_eval_rollout: filter coefficients lie in (0, 1] (1 = off)"; return 1;
+  }
+  if (need_init(h)) return 1;
+  HIP_TRY(hipSetDevice(h->device));
+  h->stream = (hipStream_t)hip_stream;
+  const int n = h->P.n_envs;
+  const size_t N = (size_t)n;
+  // the work array [N, IRRL_EVAL_WORK_DIM]: obs_cond 35 | action 12 | clipped 12 | applied 12 | value | neglogp | reward | extra 6
+  float *obs_cond = work, *action = obs_cond + N * 35, *clipped = action + N * 12, *applied = clipped + N * 12, *value = applied + N * 12,
+        *neglogp = value + N, *reward = neglogp + N, *extra = reward + N;
+  EvalArgs a;
+  a.N = n; a.D = depth;
+  a.ring = ring; a.cmd = cmd; a.vel_his = vel_his; a.act_his = act_his; a.obs = obs; a.done = done;
+  a.delay = delay; a.cmd_target = cmd_target;
+  a.a_cmd = a_cmd; a.a_vel = a_vel; a.a_act = a_act;
+  a.mean0 = cmd_mean[0]; a.mean1 = cmd_mean[1]; a.mean2 = cmd_mean[2]; a.std0 = cmd_std[0]; a.std1 = cmd_std[1]; a.std2 = cmd_std[2];
+  a.obs_cond = obs_cond; a.act_in = clip ? clipped : action; a.applied = applied; a.reward = reward;
+  a.gc = h->S.gc; a.gv = h->S.gv; a.torque = h->S.torque;
+  a.rec_obs_cond = rec_obs_cond; a.rec_act_clipped = rec_act_clipped; a.rec_act_applied = rec_act_applied; a.rec_body = rec_body;
+  a.rec_torque = rec_torque; a.rec_obs_raw = rec_obs_raw; a.rec_reward = rec_reward; a.rec_done = rec_done; a.stats = stats;
+  for (int k = 0; k < steps; k++) {
+    a.slot = (int)((step0 + k) % depth);
+    a.row = k;
+    hipLaunchKernelGGL(irrl_eval_condition_kernel, eval_grid(n * 35), dim3(256), 0, h->stream, a);
+    if (irrl_lstm_policy_step(hid, ob_dim, act_dim, n, obs_cond, done, lstm_state, lstm_state, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, nullptr, 0, 0u, 0, nullptr, 0,
+                              action, clipped, value, neglogp, -1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, hip_stream) != 0) {
+      g_err = "irrl_lstm_eval_rollout: policy step refused its arguments"; return 1;
+    }
+    hipLaunchKernelGGL(irrl_eval_action_kernel, eval_grid(n * 12), dim3(256), 0, h->stream, a);
+    launch_step(h, h->P, (const float *)applied, obs, reward, done, extra);
+    hipLaunchKernelGGL(irrl_eval_record_kernel, eval_grid(n * 35), dim3(256), 0, h->stream, a);
   }
   HIP_TRY(hipGetLastError());
   return 0;

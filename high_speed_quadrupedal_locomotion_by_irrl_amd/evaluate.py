@@ -1,0 +1,292 @@
+"""Device-resident evaluation of a trained policy: the reference's robustness study (run_bp_v5.py:300-470 -- friction, observation delay,
+rate / action low-passes, command ramp) without a host round trip per control step.
+
+  PolicyEvaluator     the evaluation loop on the GPU (C-ABI irrl_lstm_eval_rollout, kernels csrc/eval_rollout.hpp): per-env delay and command,
+                      recorders, per-env f64 statistics
+  condition           numpy float64 twin of the loop's observation conditioning (command low-pass, delay line, rate low-pass, command overwrite)
+  reference_rollout   numpy float64 twin of the whole loop around any env adapter with reset / step / get_state / set_contact_coeff
+  robustness_sweep    friction x delay x command grid in ONE Manual-mode pool -> one row of statistics per condition
+
+Semantics of control step t (global counter, carried across `run` calls), per env:
+   cmd = (1 - a_cmd) cmd + a_cmd cmd_target;  ring[t % D] = obs;  o = ring[(t - delay) mod D];
+   o[17:29], o[32:35] = (1 - a_vel) vel_his + a_vel o;  vel_his = o;  o[0:3] = (cmd - mean) / std;
+   a = actor(o) (deterministic, clipped; LSTM state reset where `done`);  a = (1 - a_act) act_his + a_act a;  act_his = a;
+   env.step(a);  record;  cmd = 0 where done.
+a = 2 pi dt f / (2 pi dt f + 1); f None or <= 0 means "filter off" (a = 1 exactly, the value passes unchanged).
+"""
+import ctypes as C
+import math
+
+import numpy as np
+
+from .helper import obs_normalisation
+
+# offsets into the flat per-env state of get_state() (include/irrl_env.h IRRL_S_*)
+_S_GC, _S_GV, _S_TORQUE = 0, 19, 61
+# rows of the device statistics (include/irrl_env.h IRRL_EVAL_STAT_*)
+STAT_SLOTS = ("n", "vx", "vx2", "z", "z2", "roll", "roll2", "pitch", "pitch2", "wx", "wx2", "wy", "wy2", "vz", "vz2", "vy", "wz", "falls")
+WORK_DIM = 80            # IRRL_EVAL_WORK_DIM
+RECORDERS = {"obs_cond": 35, "act_clipped": 12, "act_applied": 12, "body": 13, "torque": 12, "obs_raw": 35, "reward": 0, "done": 0}   # C argument order
+
+
+def lowpass_alpha(dt, hz):
+    """coefficient of the script's first-order low-pass (run_bp_v5.py:83); None / <= 0: the filter is off (exactly 1.0)"""
+    if hz is None or not hz > 0:
+        return 1.0
+    w = 2.0 * math.pi * float(dt) * float(hz)
+    return w / (w + 1.0)
+
+
+def _cmd_rows(cmd, n):
+    """[n] forward-velocity commands or [n, 3] (vx, vy, omega) -> [n, 3] float64"""
+    c = np.asarray(cmd, np.float64)
+    if c.ndim == 0:
+        c = np.full(n, float(c))
+    if c.ndim == 1:
+        c = np.stack([c, np.zeros_like(c), np.zeros_like(c)], 1)
+    if c.shape != (n, 3):
+        raise ValueError("cmd must have shape (%d,) or (%d, 3)" % (n, n))
+    return c
+
+
+def _delay_rows(delay, n, depth=None):
+    d = np.asarray(delay)
+    if d.ndim == 0:
+        d = np.full(n, int(d))
+    if d.shape != (n,) or np.any(d != np.floor(d)):
+        raise ValueError("delay must be %d whole numbers of control steps" % n)
+    d = d.astype(np.int64)
+    depth = int(d.max()) + 1 if depth is None else int(depth)
+    if depth < 1 or d.min() < 0 or d.max() >= depth:
+        raise ValueError("0 <= delay < depth (%d) violated: delays span %d .. %d" % (depth, d.min(), d.max()))
+    return d, depth
+
+
+# ---- numpy float64 twin ----
+def condition_state(ob0, depth):
+    """state of `condition` after a reset: the reset observation fills the whole delay line, command and history are zero"""
+    ob0 = np.asarray(ob0, np.float64)
+    return dict(ring=np.repeat(ob0[None], int(depth), 0), cmd=np.zeros((ob0.shape[0], 3)), vel_his=np.zeros_like(ob0))
+
+
+def condition(state, t, obs, delay, cmd_target, a_cmd, a_vel, mean3, std3):
+    """steps 1-6 of control step `t` for a batch: obs [n, 35] raw observation -> what the actor sees.  Updates `state` in place."""
+    ring = state["ring"]
+    depth = ring.shape[0]
+    rows = np.arange(ring.shape[1])
+    state["cmd"] = (1 - a_cmd) * state["cmd"] + a_cmd * cmd_target if a_cmd != 1.0 else np.array(cmd_target, np.float64)
+    ring[t % depth] = np.asarray(obs, np.float64)
+    o = ring[(t - np.asarray(delay)) % depth, rows].copy()
+    if a_vel != 1.0:
+        o[:, 32:35] = (1 - a_vel) * state["vel_his"][:, 32:35] + a_vel * o[:, 32:35]
+        o[:, 17:29] = (1 - a_vel) * state["vel_his"][:, 17:29] + a_vel * o[:, 17:29]
+    state["vel_his"] = o.copy()
+    o[:, 0:3] = (state["cmd"] - mean3) / std3
+    return o
+
+
+def reference_rollout(env, actor, env_cfg, delay, cmd, steps, cmd_hz=1.0, vel_hz=None, act_hz=None, mu=None, warm=0, mu_warm=0.8, depth=None):
+    """The evaluation loop in numpy float64 around `env` (reset() -> ob, step(a) -> ob, reward, done, extra, get_state() -> [n, 288],
+    set_contact_coeff([n, 3])) and `actor` (act(o [n, 35], done [n]) -> [n, 12], already clipped if it clips).
+    mu [n]: friction per env, installed at step `warm` (mu_warm before; warm = 0: from the start), restitution 0.2 / threshold 0.01 like
+    run_bp_v5.py:317; None leaves the env's material alone.
+    -> dict of per-step records body [steps, n, 13], torque, obs_raw, obs_cond, act_clipped, act_applied, reward, done, and falls [n]."""
+    n = env.n
+    delay, depth = _delay_rows(delay, n, depth)
+    target = _cmd_rows(cmd, n)
+    mean, std, _, _ = obs_normalisation(env_cfg)
+    dt = float(env_cfg["control_dt"])
+    a_cmd, a_vel, a_act = lowpass_alpha(dt, cmd_hz), lowpass_alpha(dt, vel_hz), lowpass_alpha(dt, act_hz)
+    warm = int(warm)
+    if mu is not None:
+        coeff = np.zeros((n, 3), np.float32)
+        coeff[:, 0] = mu if warm == 0 else mu_warm
+        coeff[:, 1] = 0.2
+        coeff[:, 2] = 0.01
+        env.set_contact_coeff(coeff)
+    ob = env.reset()
+    st = condition_state(ob, depth)
+    act_his = np.zeros((n, 12))
+    done = np.zeros(n, bool)
+    rec = dict(body=np.zeros((steps, n, 13)), torque=np.zeros((steps, n, 12)), obs_raw=np.zeros((steps, n, 35)), obs_cond=np.zeros((steps, n, 35)),
+               act_clipped=np.zeros((steps, n, 12)), act_applied=np.zeros((steps, n, 12)), reward=np.zeros((steps, n)), done=np.zeros((steps, n), bool))
+    for t in range(steps):
+        if mu is not None and warm > 0 and t == warm:
+            coeff[:, 0] = mu
+            env.set_contact_coeff(coeff)
+        o = condition(st, t, ob, delay, target, a_cmd, a_vel, mean[0:3], std[0:3])
+        a = actor.act(o, done)
+        rec["obs_cond"][t] = o
+        rec["act_clipped"][t] = a
+        if a_act != 1.0:
+            a = (1 - a_act) * act_his + a_act * a
+        act_his = np.asarray(a, np.float64)
+        rec["act_applied"][t] = a
+        ob, rew, done, _ = env.step(np.asarray(a, np.float32))
+        s = env.get_state()
+        rec["body"][t, :, 0:7] = s[:, _S_GC:_S_GC + 7]
+        rec["body"][t, :, 7:13] = s[:, _S_GV:_S_GV + 6]
+        rec["torque"][t] = s[:, _S_TORQUE:_S_TORQUE + 12]
+        rec["obs_raw"][t] = ob
+        rec["reward"][t] = rew
+        rec["done"][t] = done
+        st["cmd"][np.asarray(done, bool)] = 0.0              # the env restarted from rest
+    rec["falls"] = rec["done"].sum(0).astype(int)
+    return rec
+
+
+def statistics_from_sums(sums):
+    """sums [18, n] (STAT_SLOTS) -> dict of [n] arrays: the keys of the body-log statistics (mean / standard deviation over the accumulated
+    frames) plus `frames` and `falls`"""
+    s = {k: np.asarray(sums[i], np.float64) for i, k in enumerate(STAT_SLOTS)}
+    cnt = np.maximum(s["n"], 1.0)
+    mean = lambda k: s[k] / cnt
+    std = lambda k: np.sqrt(np.maximum(s[k + "2"] / cnt - (s[k] / cnt) ** 2, 0.0))
+    return {"vx_body_mean": mean("vx"), "vx_body_std": std("vx"), "vy_body_mean": mean("vy"), "z_mean": mean("z"), "z_std": std("z"), "roll_std": std("roll"),
+            "pitch_mean": mean("pitch"), "pitch_std": std("pitch"), "yaw_rate_mean": mean("wz"), "roll_rate_body_std": std("wx"),
+            "pitch_rate_body_std": std("wy"), "vz_std": std("vz"), "frames": s["n"].astype(np.int64), "falls": s["falls"].astype(np.int64)}
+
+
+# ---- the device loop ----
+class PolicyEvaluator(object):
+    """PolicyEvaluator(env_impl, policy, delay, cmd, cmd_hz=1.0, vel_hz=None, act_hz=None, clip=True)
+
+    env_impl: an initialised FlexibleGymEnv (Manual mode: the evaluator owns obs[0:3]); policy: a CustomLSTMPolicy on the pool's device;
+    delay [N] control steps and cmd [N] (v_x) or [N, 3] per env; depth: length of the delay line (default max(delay) + 1).
+    Friction goes through env_impl.SetContactCoefficient between `run` calls (a warm-up on another material = two calls)."""
+
+    def __init__(self, env_impl, policy, delay, cmd, cmd_hz=1.0, vel_hz=None, act_hz=None, clip=True, depth=None):
+        import torch
+        self.env, self.policy = env_impl, policy
+        self.n = n = env_impl.getNumOfEnvs()
+        self.dev = dev = torch.device("cuda", env_impl.device_index)
+        self.hid = int(policy.n_lstm[0])
+        if len(policy.n_lstm) != 2 or policy.n_lstm[0] != policy.n_lstm[1] or self.hid not in (32, 48, 64) or policy.act_dim != 12:
+            raise ValueError("PolicyEvaluator runs CustomLSTMPolicy with two equal LSTM layers of 32, 48 or 64 units and 12 actions")
+        delay, self.depth = _delay_rows(delay, n, depth)
+        cfg = {k: env_impl.cfg_value(k) for k in ("abad", "Vx", "Vy", "Omega", "control_dt")}
+        mean, std, _, _ = obs_normalisation(cfg)
+        self.cmd_mean, self.cmd_std = (C.c_float * 3)(*mean[0:3]), (C.c_float * 3)(*std[0:3])
+        dt = cfg["control_dt"]
+        self.a_cmd, self.a_vel, self.a_act = (float(np.float32(lowpass_alpha(dt, f))) for f in (cmd_hz, vel_hz, act_hz))
+        self.clip = bool(clip)
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.delay = torch.from_numpy(delay.astype(np.int32)).to(dev)
+        self.cmd_target = torch.from_numpy(_cmd_rows(cmd, n).astype(np.float32)).to(dev)
+        self.ring = torch.zeros(self.depth, n, 35, **f32)
+        self.cmd = torch.zeros(n, 3, **f32)
+        self.vel_his = torch.zeros(n, 35, **f32)
+        self.act_his = torch.zeros(n, 12, **f32)
+        self.lstm_state = torch.zeros(n, 8 * self.hid, **f32)
+        self.done = torch.zeros(n, dtype=torch.bool, device=dev)
+        self.obs = torch.zeros(n, 35, **f32)
+        self.work = torch.zeros(n, WORK_DIM, **f32)
+        self.stats = torch.zeros(len(STAT_SLOTS), n, device=dev, dtype=torch.float64)
+        self.t = 0
+        self.reset()
+
+    def reset(self):
+        """reset every env; the reset observation fills the delay line, command / histories / LSTM state / done are zeroed, t = 0"""
+        self.env.reset(self.obs)
+        self.ring.copy_(self.obs.unsqueeze(0).expand_as(self.ring))
+        for b in (self.cmd, self.vel_his, self.act_his, self.lstm_state):
+            b.zero_()
+        self.done.zero_()
+        self.t = 0
+
+    def run(self, steps, record=(), accumulate=True):
+        """`steps` control steps from ONE C call (stream-ordered on torch's current stream, no synchronisation).  record: names out of
+        RECORDERS -> dict of device tensors [steps, N, .]; accumulate: add these steps' frames to the per-env statistics."""
+        import torch
+        from . import _lib
+        from ._lib import ptr
+        from .lstm_fused import _head_ptrs, _lstm_weight_table
+        steps = int(steps)
+        unknown = [k for k in record if k not in RECORDERS]
+        if unknown:
+            raise KeyError("unknown recorder(s) %s: choose from %s" % (unknown, sorted(RECORDERS)))
+        out = {}
+        for k in record:
+            shape = (steps, self.n) + ((RECORDERS[k],) if RECORDERS[k] else ())
+            out[k] = torch.empty(shape, device=self.dev, dtype=torch.bool if k == "done" else torch.float32)
+        with torch.cuda.device(self.dev):
+            self.policy.prepare()                              # the kernels' permuted weight copies follow the parameters (a learner may have stepped)
+            warr = _lstm_weight_table(self.policy, self.dev)
+            _lib.check(_lib.load().irrl_lstm_eval_rollout(
+                self.env._h, steps, self.t, self.hid, 35, 12, warr, *_head_ptrs(self.policy), self.depth, ptr(self.ring), ptr(self.cmd), ptr(self.vel_his),
+                ptr(self.act_his), ptr(self.lstm_state), ptr(self.done), ptr(self.obs), ptr(self.work), ptr(self.delay), ptr(self.cmd_target),
+                self.a_cmd, self.a_vel, self.a_act, self.cmd_mean, self.cmd_std, int(self.clip), *[ptr(out.get(k)) for k in RECORDERS],
+                ptr(self.stats) if accumulate else None, _lib.stream_ptr(self.dev)))
+        self.t += steps
+        return out
+
+    def zero_statistics(self):
+        self.stats.zero_()
+
+    def statistics(self):
+        """per-env statistics over the frames accumulated since zero_statistics() (synchronises): dict of [N] numpy arrays, see statistics_from_sums"""
+        return statistics_from_sums(self.stats.cpu().numpy())
+
+
+def load_policy(model_or_policy, device):
+    """a CustomLSTMPolicy on `device` from: the policy itself, a model that has `.policy` (PPO2), or the path of a checkpoint (this build's or a
+    stable-baselines pickle of the reference)"""
+    import torch
+    from .policies import CustomLSTMPolicy
+    pol = getattr(model_or_policy, "policy", model_or_policy)
+    if isinstance(pol, str):
+        from .checkpoint import read_checkpoint
+        _, params = read_checkpoint(pol)
+        pol = CustomLSTMPolicy(ob_dim=params[0].shape[0], act_dim=params[14].shape[1], n_lstm=(params[1].shape[0], params[4].shape[0]))
+        ps = pol.sb_parameters()
+        if len(ps) != len(params):
+            raise ValueError("checkpoint holds %d tensors, CustomLSTMPolicy has %d" % (len(params), len(ps)))
+        with torch.no_grad():
+            for p, a in zip(ps, params):
+                p.copy_(torch.as_tensor(np.asarray(a), dtype=p.dtype).reshape(p.shape))
+    pol = pol.to(device)
+    pol.prepare()
+    return pol
+
+
+def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=1000, steps=2000, cmd_hz=1.0, vel_hz=None, act_hz=None, clip=True,
+                     mu_warm=0.8, device=None):
+    """The reference's robustness grid in one pool: len(mus) x len(delays) x len(cmds) Manual-mode envs (condition index = (i_mu * len(delays) +
+    i_delay) * len(cmds) + i_cmd), `warm_steps` control steps on friction mu_warm, then `steps` on the condition's own friction over which the
+    statistics are taken.  env_cfg: the `environment:` mapping of a config.  -> list of rows dict(mu, delay, cmd, falls, frames, <statistics>)."""
+    import torch
+    import yaml
+    from . import __BLACKPANTHER_V55_RESOURCE_DIRECTORY__ as rsc
+    from .flexible_robot import FlexibleGymEnv
+    grid = [(float(m), int(d), float(c)) for m in mus for d in delays for c in cmds]
+    if not grid:
+        raise ValueError("empty sweep")
+    cfg = dict(env_cfg.get("environment", env_cfg))
+    cfg["num_envs"] = len(grid)
+    cfg["Manual"] = True
+    dev_index = torch.cuda.current_device() if device is None else int(device)
+    env = FlexibleGymEnv(rsc, yaml.safe_dump(cfg, default_flow_style=False, width=float("inf")), device=dev_index)
+    env.init()
+    policy = load_policy(model_or_policy, torch.device("cuda", dev_index))
+    coeff = np.zeros((len(grid), 3), np.float32)
+    coeff[:, 0] = mu_warm if warm_steps > 0 else [g[0] for g in grid]
+    coeff[:, 1] = 0.2
+    coeff[:, 2] = 0.01                                        # run_bp_v5.py:317
+    env.SetContactCoefficient(coeff)
+    ev = PolicyEvaluator(env, policy, [g[1] for g in grid], [g[2] for g in grid], cmd_hz=cmd_hz, vel_hz=vel_hz, act_hz=act_hz, clip=clip)
+    if warm_steps > 0:
+        ev.run(warm_steps, accumulate=False)
+        coeff[:, 0] = [g[0] for g in grid]                     # (the setter's copy is ordered on the pool's stream, behind the warm-up)
+        env.SetContactCoefficient(coeff)
+    ev.zero_statistics()
+    ev.run(steps)
+    st = ev.statistics()
+    return [dict(mu=m, delay=d, cmd=c, **{k: (int(v[i]) if k in ("falls", "frames") else float(v[i])) for k, v in st.items()}) for i, (m, d, c) in enumerate(grid)]
+
+
+def sweep_table(rows):
+    keys = ("vx_body_mean", "vx_body_std", "z_mean", "z_std", "roll_std", "pitch_mean", "pitch_std", "yaw_rate_mean")
+    out = ["%-6s %-5s %-5s %-5s " % ("mu", "delay", "cmd", "falls") + " ".join("%-12s" % k for k in keys)]
+    for r in rows:
+        out.append("%-6g %-5d %-5g %-5d " % (r["mu"], r["delay"], r["cmd"], r["falls"]) + " ".join("%+12.4f" % r[k] for k in keys))
+    return "\n".join(out)

@@ -390,6 +390,57 @@ int irrl_mlp_rollout(irrl_env *env, int steps, int hid, int ob_dim, int act_dim,
  * -1 = bad handle.  The twin of irrl_lstm_rollout_supports. */
 int irrl_mlp_rollout_supports(irrl_env *env, int hid, int fuse);
 
+/* ---- DEVICE-RESIDENT POLICY EVALUATION (run_bp_v5.py:353-470, the reference's robustness study: friction, observation delay, rate / action
+ * low-passes, command ramp).  `steps` control steps of the closed loop  conditioning -> CustomLSTMPolicy (deterministic) -> action filter ->
+ * env.step -> record  issued by ONE call as plain launches back to back on `hip_stream` (five per step; kernels csrc/eval_rollout.hpp, the policy
+ * step and the env step are the existing ones, so every pool kind and kernel variant works).  Nothing is captured, nothing synchronises, and the
+ * call keeps no state: a second call with step0 + steps continues exactly where the first stopped.  A persistent single-launch form is out of scope.
+ *
+ * Control step t = step0 + k, per env e:
+ *    1. cmd = (1 - a_cmd) cmd + a_cmd cmd_target            2. ring[t % D] = obs              3. o = ring[(t - delay_e) mod D]
+ *    4. o[17:29], o[32:35] = (1 - a_vel) vel_his + a_vel o   5. vel_his = o (whole vector)     6. o[0:3] = (cmd - cmd_mean) / cmd_std
+ *    7. the actor on o (irrl_lstm_policy_step without noise: it resets the LSTM state of an env whose `done` is set)
+ *    8. a = clipped mean (clip != 0) or the mean             9. a = (1 - a_act) act_his + a_act a   10. act_his = a
+ *   11. env.step(a) -> obs, done                            12. recorders, statistics          13. cmd = 0 where done
+ * A coefficient a_* = 2 pi dt f / (2 pi dt f + 1) of EXACTLY 1.0f switches that filter off (values pass bit for bit).  The ring and the filter
+ * histories are not cleared by an in-episode `done` (the script does not clear them either).
+ *
+ * Evaluator state, caller-owned device memory (N = num_envs of `env`, D = depth >= 1): ring [D, N, 35], cmd [N, 3], vel_his [N, 35], act_his [N, 12],
+ * lstm_state [N, 8 hid], done [N] u8, obs [N, 35] (raw observation: in = the last env output / the reset observation, out = the last step's),
+ * work [N, IRRL_EVAL_WORK_DIM] f32 scratch.  A fresh evaluation: obs = irrl_env_reset's, every plane of ring = obs, everything else zero.
+ * Per-env parameters (device): delay [N] int32 in 0 .. D-1 (the caller validates; values outside are clamped), cmd_target [N, 3].
+ * Scalars: a_cmd, a_vel, a_act in (0, 1]; cmd_mean / cmd_std: HOST arrays of 3 floats (scaling of obs[0:3], Environment.hpp:371-393).
+ * lstm_w (HOST array of 12 device pointers), the heads and hid / ob_dim / act_dim as irrl_lstm_policy_step; hid in {32, 48, 64}, ob 35, act 12.
+ * Recorders (device, each may be NULL = off), row k = step k OF THIS CALL: rec_obs_cond [steps, N, 35] (what the actor saw), rec_act_clipped /
+ * rec_act_applied [steps, N, 12] (before / after the action filter), rec_body [steps, N, 13] = base x y z, quaternion wxyz, world linear and
+ * angular velocity after the env step (the layout of the reference's body-center logs), rec_torque [steps, N, 12], rec_obs_raw [steps, N, 35],
+ * rec_reward [steps, N], rec_done [steps, N] u8.
+ * stats (device f64 [IRRL_EVAL_STAT_COUNT, N], may be NULL): per-env accumulators over the recorded body frames, ADDED to by every step (zero them
+ * to start a window; one thread owns one env's column, no atomics; body frame, roll = atan2, pitch = asin evaluated in f64).
+ * Errors (non-zero, irrl_last_error() set, checked before any HIP call): NULL handle, depth < 1, hid outside {32, 48, 64}, ob_dim != 35,
+ * act_dim != 12, a NULL state / parameter / weight pointer, a coefficient outside (0, 1]. */
+#define IRRL_EVAL_WORK_DIM 80 /* obs_cond 35 | action 12 | clipped 12 | applied 12 | value | neglogp | reward | extra 6 */
+enum {
+  IRRL_EVAL_STAT_N = 0,     /* frames accumulated */
+  IRRL_EVAL_STAT_VX, IRRL_EVAL_STAT_VX2,       /* sum, sum of squares: body-frame v_x */
+  IRRL_EVAL_STAT_Z, IRRL_EVAL_STAT_Z2,         /* base height */
+  IRRL_EVAL_STAT_ROLL, IRRL_EVAL_STAT_ROLL2,
+  IRRL_EVAL_STAT_PITCH, IRRL_EVAL_STAT_PITCH2,
+  IRRL_EVAL_STAT_WX, IRRL_EVAL_STAT_WX2,       /* body-frame roll rate */
+  IRRL_EVAL_STAT_WY, IRRL_EVAL_STAT_WY2,       /* body-frame pitch rate */
+  IRRL_EVAL_STAT_VZ, IRRL_EVAL_STAT_VZ2,       /* world v_z */
+  IRRL_EVAL_STAT_VY,        /* sum of body-frame v_y */
+  IRRL_EVAL_STAT_WZ,        /* sum of world omega_z */
+  IRRL_EVAL_STAT_FALLS,     /* number of steps that ended in `done` */
+  IRRL_EVAL_STAT_COUNT
+};
+int irrl_lstm_eval_rollout(irrl_env *env, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *lstm_w, const float *pi_w,
+                           const float *pi_b, const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring, float *cmd, float *vel_his,
+                           float *act_his, float *lstm_state, uint8_t *done, float *obs, float *work, const int *delay, const float *cmd_target, float a_cmd,
+                           float a_vel, float a_act, const float *cmd_mean, const float *cmd_std, int clip, float *rec_obs_cond, float *rec_act_clipped,
+                           float *rec_act_applied, float *rec_body, float *rec_torque, float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats,
+                           void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

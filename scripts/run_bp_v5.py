@@ -8,6 +8,8 @@ reference's own (run_bp_v5.py:8-13), resolved by the compat packages at the repo
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 scripts/run_bp_v5.py --train   # 8 x 4096 envs, RCCL grads
 
     python scripts/run_bp_v5.py --test --model data/..._final.pkl --cmd 1.5 --steps 2000   # headless evaluation
+    python scripts/run_bp_v5.py --test --sweep --model data/..._final.pkl --sweep_mu 0.05,0.4,0.8 --sweep_delay 0,1,2,3,4,5 --sweep_cmd 1,2,3,4,5 \
+        --warm 1000 --steps 2000 --out table.json                                          # robustness grid, device-resident
 
 `--test` keeps the evaluation LOOP of the reference (run_bp_v5.py:353-470: Manual-mode env, externally supplied command in
 obs[0:3], observation delay line, velocity / action low-pass filters, numpy LSTM actor, per-step records of joint state,
@@ -57,7 +59,14 @@ def parse_args(argv):
     p.add_argument("--vel_filter_freq", type=float, default=1.0e6, help="low-pass on the joint-rate / omega observations [Hz]")
     p.add_argument("--act_filter_freq", type=float, default=1.0e6, help="low-pass on the action [Hz]")
     p.add_argument("--cmd_filter_freq", type=float, default=1.0, help="low-pass on the command [Hz] (GaitGenerator command_filter_freq)")
-    p.add_argument("--out", type=str, default=None, help="--test: .npz with the per-step records")
+    p.add_argument("--out", type=str, default=None, help="--test: .npz with the per-step records; --sweep: .json with the table")
+    # --test --sweep: the robustness grid of the paper (friction x observation delay x command) in one device-resident pool
+    floats = lambda s: [float(v) for v in str(s).split(",") if v != ""]
+    p.add_argument("--sweep", action="store_true", default=False, help="--test: run the friction x delay x command grid on the device (evaluate.robustness_sweep)")
+    p.add_argument("--sweep_mu", type=floats, default=[0.05, 0.4, 0.8], help="friction coefficients, comma separated")
+    p.add_argument("--sweep_delay", type=lambda s: [int(v) for v in str(s).split(",") if v != ""], default=[0, 1, 2, 3, 4, 5], help="observation delays [control steps]")
+    p.add_argument("--sweep_cmd", type=floats, default=[1.0, 2.0, 3.0, 4.0, 5.0], help="forward-velocity commands [m/s]")
+    p.add_argument("--warm", type=int, default=1000, help="--sweep: control steps on friction 0.8 before the condition's own friction is installed")
     return p.parse_args(argv)
 
 
@@ -126,6 +135,25 @@ def run_test(args, cfg):
     return out
 
 
+def run_sweep(args, cfg):
+    """--test --sweep: every (friction, delay, command) condition is one env of ONE Manual-mode pool; the loop of `run_test` runs on the device
+    (evaluate.PolicyEvaluator), `--warm` steps on the script's default material, then `--steps` on the condition's own over which the
+    statistics are taken.  Prints the table, writes it to --out as JSON."""
+    import json
+    from high_speed_quadrupedal_locomotion_by_irrl_amd.evaluate import robustness_sweep, sweep_table
+    if args.trained_model is None:
+        raise SystemExit("model path can't be ignored during test mode (--model)")
+    none_if_off = lambda f: None if f >= 1.0e6 else f
+    rows = robustness_sweep(args.trained_model, cfg["environment"], args.sweep_mu, args.sweep_delay, args.sweep_cmd, warm_steps=args.warm, steps=args.steps,
+                            cmd_hz=args.cmd_filter_freq, vel_hz=none_if_off(args.vel_filter_freq), act_hz=none_if_off(args.act_filter_freq))
+    print(sweep_table(rows))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(rows, f, indent=1)
+        print("table written to", args.out)
+    return rows
+
+
 def main(argv=None):
     import torch
     args = parse_args(argv)
@@ -147,7 +175,7 @@ def main(argv=None):
         else:
             torch.distributed.init_process_group(backend)
     if not args.train and not args.flag_output:
-        return run_test(args, cfg)
+        return run_sweep(args, cfg) if args.sweep else run_test(args, cfg)
     if args.num_envs:
         cfg["environment"]["num_envs"] = args.num_envs
     if args.seed is not None:
