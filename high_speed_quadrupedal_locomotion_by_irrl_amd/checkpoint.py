@@ -7,7 +7,8 @@
                                neither package is needed (only the hyper-parameters and the arrays are kept).
   export_actor_csv(model, dir) the reference's `--o` export (CustomerLstmNN.save_model, NN:203-224):
                                lstm_wx{i}.csv, lstm_wh{i}.csv, lstm_b{i}.csv, pi_w.csv, pi_b.csv with '%.6f'.
-  NumpyLstmActor               numpy twin of CustomerLstmNN.predict (NN:112-135) for deployment checks.
+  NumpyLstmActor               numpy float64 twin of CustomerLstmNN.predict (NN:112-135), one vector or a batch with per-row resets:
+                               the one numpy actor of the deployment checks and of every host-side evaluation loop.
 """
 import os
 import pickle
@@ -87,10 +88,14 @@ def export_actor_csv(model, out_dir):
 
 
 class NumpyLstmActor(object):
-    """Stateful numpy forward of the LSTM actor (gate order i,f,o,g; output clipped to [-1,1], NN:133-134)."""
+    """Stateful numpy float64 forward of the LSTM actor (gate order i,f,o,g) for one observation [ob_dim] or a batch [..., ob_dim]: the state
+    takes its leading shape from the first observation after a reset().  clip: the output is clipped to [-1, 1] (NN:133-134); the rollout clips
+    the sampled action itself (ppo2.py:533) and can switch it off."""
 
-    def __init__(self, wx, wh, b, pi_w, pi_b):
-        self.wx, self.wh, self.b, self.pi_w, self.pi_b = wx, wh, b, pi_w, pi_b
+    def __init__(self, wx, wh, b, pi_w, pi_b, clip=True):
+        f64 = lambda w: np.asarray(w, np.float64)
+        self.wx, self.wh, self.b = [f64(w) for w in wx], [f64(w) for w in wh], [f64(w) for w in b]
+        self.pi_w, self.pi_b, self.clip = f64(pi_w), f64(pi_b), clip
         self.reset()
 
     @classmethod
@@ -105,18 +110,37 @@ class NumpyLstmActor(object):
         return cls([params[3 * i] for i in range(n_layers)], [params[3 * i + 1] for i in range(n_layers)],
                    [params[3 * i + 2] for i in range(n_layers)], params[base + 2], params[base + 3])
 
-    def reset(self):
-        self.c = [np.zeros(w.shape[0]) for w in self.wh]
-        self.h = [np.zeros(w.shape[0]) for w in self.wh]
+    @classmethod
+    def from_npz(cls, path, clip=True):
+        """the actor export of tools/export_actor_fixture.py (tests/golden/actor_*.npz): wx<i>, wh<i>, b<i>, pi_w, pi_b"""
+        z = np.load(path)
+        layers = range(sum(k.startswith("wx") for k in z.files))
+        return cls([z["wx%d" % i] for i in layers], [z["wh%d" % i] for i in layers], [z["b%d" % i] for i in layers], z["pi_w"], z["pi_b"], clip)
 
-    def predict(self, obs):
-        x = np.asarray(obs, np.float64)
+    def reset(self):
+        self.c = self.h = None
+
+    def act(self, ob, done=None):
+        """one step on ob [..., ob_dim]; rows where `done` [...] is set start from a zero state.  -> float64 action [..., act_dim]"""
+        x = np.asarray(ob, np.float64)
+        if self.c is None:
+            self.c = [np.zeros(x.shape[:-1] + (w.shape[0],)) for w in self.wh]
+            self.h = [np.zeros(x.shape[:-1] + (w.shape[0],)) for w in self.wh]
+        keep = 1.0 if done is None else (~np.asarray(done, bool)).astype(np.float64)[..., None]
         sig = lambda v: 1.0 / (1.0 + np.exp(-v))
+        # one vector-matrix product per row: a row's action does not depend on the batch it sits in (a matrix-matrix product sums in another
+        # order: rows of a batch of >= 2 differ from the single-vector result by ~1e-14 in this numpy), so a batch IS its rows, bit for bit
+        mul = lambda v, w: (v[..., None, :] @ w)[..., 0, :]
         for i in range(len(self.wx)):
             n = self.wh[i].shape[0]
-            z = x @ self.wx[i] + self.h[i] @ self.wh[i] + self.b[i]
-            ig, fg, og, g = sig(z[:n]), sig(z[n:2 * n]), sig(z[2 * n:3 * n]), np.tanh(z[3 * n:])
-            self.c[i] = fg * self.c[i] + ig * g
+            z = mul(x, self.wx[i]) + mul(self.h[i] * keep, self.wh[i]) + self.b[i]
+            ig, fg, og, g = sig(z[..., :n]), sig(z[..., n:2 * n]), sig(z[..., 2 * n:3 * n]), np.tanh(z[..., 3 * n:])
+            self.c[i] = fg * (self.c[i] * keep) + ig * g
             self.h[i] = og * np.tanh(self.c[i])
             x = self.h[i]
-        return np.clip(x @ self.pi_w + self.pi_b, -1.0, 1.0)
+        a = mul(x, self.pi_w) + self.pi_b
+        return np.clip(a, -1.0, 1.0) if self.clip else a
+
+    def predict(self, obs):
+        """CustomerLstmNN.predict (NN:112-135): one observation vector -> one action"""
+        return self.act(obs)

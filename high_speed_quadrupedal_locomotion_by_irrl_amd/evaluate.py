@@ -4,7 +4,9 @@ rate / action low-passes, command ramp) without a host round trip per control st
   PolicyEvaluator     the evaluation loop on the GPU (C-ABI irrl_lstm_eval_rollout, kernels csrc/eval_rollout.hpp): per-env delay and command,
                       recorders, per-env f64 statistics
   condition           numpy float64 twin of the loop's observation conditioning (command low-pass, delay line, rate low-pass, command overwrite)
-  reference_rollout   numpy float64 twin of the whole loop around any env adapter with reset / step / get_state / set_contact_coeff
+  reference_rollout   numpy float64 twin of the whole loop around any env adapter with reset / step / get_state / set_contact_coeff: THE host-driven
+                      evaluation loop (the test harnesses and tools translate their cases into one call of it)
+  body_statistics     the statistics of a [frames, 13] body recording, of this build's loops and of the reference's simulator logs alike
   robustness_sweep    friction x delay x command grid in ONE Manual-mode pool -> one row of statistics per condition
 
 Semantics of control step t (global counter, carried across `run` calls), per env:
@@ -37,6 +39,13 @@ def lowpass_alpha(dt, hz):
     return w / (w + 1.0)
 
 
+def contact_material(mu):
+    """friction coefficient(s) mu [n] -> the [n, 3] float32 rows of SetContactCoefficient: (mu, restitution 0.2, restitution threshold 0.01), the
+    material of the evaluation script (run_bp_v5.py:317)"""
+    mu = np.atleast_1d(np.asarray(mu, np.float32))
+    return np.stack([mu, np.full_like(mu, 0.2), np.full_like(mu, 0.01)], 1)
+
+
 def _cmd_rows(cmd, n):
     """[n] forward-velocity commands or [n, 3] (vx, vy, omega) -> [n, 3] float64"""
     c = np.asarray(cmd, np.float64)
@@ -49,13 +58,18 @@ def _cmd_rows(cmd, n):
     return c
 
 
+def _step_rows(v, n, what):
+    """a scalar or [n] whole numbers of control steps -> [n] int64"""
+    v = np.asarray(v)
+    if v.ndim == 0:
+        v = np.full(n, int(v))
+    if v.shape != (n,) or np.any(v != np.floor(v)):
+        raise ValueError("%s must be %d whole numbers of control steps" % (what, n))
+    return v.astype(np.int64)
+
+
 def _delay_rows(delay, n, depth=None):
-    d = np.asarray(delay)
-    if d.ndim == 0:
-        d = np.full(n, int(d))
-    if d.shape != (n,) or np.any(d != np.floor(d)):
-        raise ValueError("delay must be %d whole numbers of control steps" % n)
-    d = d.astype(np.int64)
+    d = _step_rows(delay, n, "delay")
     depth = int(d.max()) + 1 if depth is None else int(depth)
     if depth < 1 or d.min() < 0 or d.max() >= depth:
         raise ValueError("0 <= delay < depth (%d) violated: delays span %d .. %d" % (depth, d.min(), d.max()))
@@ -88,21 +102,21 @@ def condition(state, t, obs, delay, cmd_target, a_cmd, a_vel, mean3, std3):
 def reference_rollout(env, actor, env_cfg, delay, cmd, steps, cmd_hz=1.0, vel_hz=None, act_hz=None, mu=None, warm=0, mu_warm=0.8, depth=None):
     """The evaluation loop in numpy float64 around `env` (reset() -> ob, step(a) -> ob, reward, done, extra, get_state() -> [n, 288],
     set_contact_coeff([n, 3])) and `actor` (act(o [n, 35], done [n]) -> [n, 12], already clipped if it clips).
-    mu [n]: friction per env, installed at step `warm` (mu_warm before; warm = 0: from the start), restitution 0.2 / threshold 0.01 like
-    run_bp_v5.py:317; None leaves the env's material alone.
-    -> dict of per-step records body [steps, n, 13], torque, obs_raw, obs_cond, act_clipped, act_applied, reward, done, and falls [n]."""
+    mu [n]: friction per env (contact_material); env i runs on mu_warm until step warm[i] (a scalar or [n]) and on mu[i] from then on, warm[i] = 0:
+    from the start.  set_contact_coeff is called before the reset and at the steps where some env switches.  None leaves the env's material alone.
+    The actor's float64 action goes through the action low-pass as it is and becomes float32 once, at env.step.
+    -> dict of per-step records body [steps, n, 13], torque, obs_raw, obs_cond, act_clipped, act_applied, reward, done, and falls [n]; a window
+    warm[i] : warm[i] + frames is the caller's slice."""
     n = env.n
     delay, depth = _delay_rows(delay, n, depth)
     target = _cmd_rows(cmd, n)
     mean, std, _, _ = obs_normalisation(env_cfg)
     dt = float(env_cfg["control_dt"])
     a_cmd, a_vel, a_act = lowpass_alpha(dt, cmd_hz), lowpass_alpha(dt, vel_hz), lowpass_alpha(dt, act_hz)
-    warm = int(warm)
+    warm = _step_rows(warm, n, "warm")
     if mu is not None:
-        coeff = np.zeros((n, 3), np.float32)
-        coeff[:, 0] = mu if warm == 0 else mu_warm
-        coeff[:, 1] = 0.2
-        coeff[:, 2] = 0.01
+        mu = np.broadcast_to(np.asarray(mu, np.float64), (n,))
+        coeff = contact_material(np.where(warm == 0, mu, mu_warm))
         env.set_contact_coeff(coeff)
     ob = env.reset()
     st = condition_state(ob, depth)
@@ -111,8 +125,9 @@ def reference_rollout(env, actor, env_cfg, delay, cmd, steps, cmd_hz=1.0, vel_hz
     rec = dict(body=np.zeros((steps, n, 13)), torque=np.zeros((steps, n, 12)), obs_raw=np.zeros((steps, n, 35)), obs_cond=np.zeros((steps, n, 35)),
                act_clipped=np.zeros((steps, n, 12)), act_applied=np.zeros((steps, n, 12)), reward=np.zeros((steps, n)), done=np.zeros((steps, n), bool))
     for t in range(steps):
-        if mu is not None and warm > 0 and t == warm:
-            coeff[:, 0] = mu
+        switch = (warm == t) & (warm > 0)
+        if mu is not None and switch.any():
+            coeff[switch, 0] = mu[switch]
             env.set_contact_coeff(coeff)
         o = condition(st, t, ob, delay, target, a_cmd, a_vel, mean[0:3], std[0:3])
         a = actor.act(o, done)
@@ -135,9 +150,38 @@ def reference_rollout(env, actor, env_cfg, delay, cmd, steps, cmd_hz=1.0, vel_hz
     return rec
 
 
+def body_frame(frames):
+    """frames [n, 13] = base x y z, quaternion wxyz, world linear velocity, world angular velocity -> (linear velocity [n, 3] and angular velocity
+    [n, 3] in the body frame, roll [n], pitch [n])"""
+    d = np.asarray(frames, np.float64)
+    w, x, y, z = d[:, 3], d[:, 4], d[:, 5], d[:, 6]
+    R = np.zeros((len(d), 3, 3))
+    R[:, 0, 0] = 1 - 2 * (y * y + z * z); R[:, 0, 1] = 2 * (x * y - w * z); R[:, 0, 2] = 2 * (w * y + x * z)
+    R[:, 1, 0] = 2 * (x * y + w * z); R[:, 1, 1] = 1 - 2 * (x * x + z * z); R[:, 1, 2] = 2 * (y * z - w * x)
+    R[:, 2, 0] = 2 * (x * z - w * y); R[:, 2, 1] = 2 * (w * x + y * z); R[:, 2, 2] = 1 - 2 * (x * x + y * y)
+    vb = np.einsum("nji,nj->ni", R, d[:, 7:10])
+    wb = np.einsum("nji,nj->ni", R, d[:, 10:13])
+    roll = np.arctan2(2 * (w * x + y * z), 1 - 2 * (x * x + y * y))
+    pitch = np.arcsin(np.clip(2 * (w * y - x * z), -1, 1))
+    return vb, wb, roll, pitch
+
+
+def body_statistics(frames, window=None):
+    """frames [n, 13] (layout of body_frame, 500 Hz) -> the statistics tests/golden/raisim_body_logs.json holds for each RaiSim log, taken over
+    `window` (a slice; default: every frame), plus the whole series `vx_body` [n]"""
+    d = np.asarray(frames, np.float64)
+    h = window if window is not None else slice(0, len(d))
+    vb, wb, roll, pitch = body_frame(d)
+    return {"vx_body_mean": float(vb[h, 0].mean()), "vx_body_std": float(vb[h, 0].std()), "vy_body_mean": float(vb[h, 1].mean()),
+            "z_mean": float(d[h, 2].mean()), "z_std": float(d[h, 2].std()), "roll_std": float(roll[h].std()),
+            "pitch_mean": float(pitch[h].mean()), "pitch_std": float(pitch[h].std()), "yaw_rate_mean": float(d[h, 12].mean()),
+            "roll_rate_body_std": float(wb[h, 0].std()), "pitch_rate_body_std": float(wb[h, 1].std()), "vz_std": float(d[h, 9].std()),
+            "vx_body": vb[:, 0]}
+
+
 def statistics_from_sums(sums):
-    """sums [18, n] (STAT_SLOTS) -> dict of [n] arrays: the keys of the body-log statistics (mean / standard deviation over the accumulated
-    frames) plus `frames` and `falls`"""
+    """sums [18, n] (STAT_SLOTS) -> dict of [n] arrays: the keys of body_statistics (mean / standard deviation over the accumulated frames), in
+    the sums form the device keeps, plus `frames` and `falls`"""
     s = {k: np.asarray(sums[i], np.float64) for i, k in enumerate(STAT_SLOTS)}
     cnt = np.maximum(s["n"], 1.0)
     mean = lambda k: s[k] / cnt
@@ -229,18 +273,26 @@ class PolicyEvaluator(object):
 
 
 def load_policy(model_or_policy, device):
-    """a CustomLSTMPolicy on `device` from: the policy itself, a model that has `.policy` (PPO2), or the path of a checkpoint (this build's or a
-    stable-baselines pickle of the reference)"""
+    """a CustomLSTMPolicy on `device` from: the policy itself, a model that has `.policy` (PPO2), the path of a checkpoint (this build's or a
+    stable-baselines pickle of the reference), or the path of an actor export `actor_*.npz` (tools/export_actor_fixture.py: two LSTM layers and
+    the action head; the critic, which the evaluation does not read, keeps the initialisation of torch.manual_seed(3))"""
     import torch
     from .policies import CustomLSTMPolicy
     pol = getattr(model_or_policy, "policy", model_or_policy)
     if isinstance(pol, str):
-        from .checkpoint import read_checkpoint
-        _, params = read_checkpoint(pol)
-        pol = CustomLSTMPolicy(ob_dim=params[0].shape[0], act_dim=params[14].shape[1], n_lstm=(params[1].shape[0], params[4].shape[0]))
-        ps = pol.sb_parameters()
-        if len(ps) != len(params):
-            raise ValueError("checkpoint holds %d tensors, CustomLSTMPolicy has %d" % (len(params), len(ps)))
+        if pol.endswith(".npz"):
+            z = np.load(pol)
+            torch.manual_seed(3)
+            pol = CustomLSTMPolicy(ob_dim=z["wx0"].shape[0], act_dim=z["pi_w"].shape[1], n_lstm=(z["wh0"].shape[0], z["wh1"].shape[0]))
+            ps = [p for l in pol.lstm_pi for p in (l.wx, l.wh, l.b)] + [pol.pi.w, pol.pi.b]
+            params = [z[k] for k in ("wx0", "wh0", "b0", "wx1", "wh1", "b1", "pi_w", "pi_b")]
+        else:
+            from .checkpoint import read_checkpoint
+            _, params = read_checkpoint(pol)
+            pol = CustomLSTMPolicy(ob_dim=params[0].shape[0], act_dim=params[14].shape[1], n_lstm=(params[1].shape[0], params[4].shape[0]))
+            ps = pol.sb_parameters()
+            if len(ps) != len(params):
+                raise ValueError("checkpoint holds %d tensors, CustomLSTMPolicy has %d" % (len(params), len(ps)))
         with torch.no_grad():
             for p, a in zip(ps, params):
                 p.copy_(torch.as_tensor(np.asarray(a), dtype=p.dtype).reshape(p.shape))
@@ -268,10 +320,7 @@ def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=100
     env = FlexibleGymEnv(rsc, yaml.safe_dump(cfg, default_flow_style=False, width=float("inf")), device=dev_index)
     env.init()
     policy = load_policy(model_or_policy, torch.device("cuda", dev_index))
-    coeff = np.zeros((len(grid), 3), np.float32)
-    coeff[:, 0] = mu_warm if warm_steps > 0 else [g[0] for g in grid]
-    coeff[:, 1] = 0.2
-    coeff[:, 2] = 0.01                                        # run_bp_v5.py:317
+    coeff = contact_material([mu_warm if warm_steps > 0 else g[0] for g in grid])
     env.SetContactCoefficient(coeff)
     ev = PolicyEvaluator(env, policy, [g[1] for g in grid], [g[2] for g in grid], cmd_hz=cmd_hz, vel_hz=vel_hz, act_hz=act_hz, clip=clip)
     if warm_steps > 0:

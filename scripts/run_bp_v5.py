@@ -76,7 +76,8 @@ def run_test(args, cfg):
     import numpy as np
     from flex_gym.env.RaisimGymVecEnv import RaisimGymVecEnv
     from high_speed_quadrupedal_locomotion_by_irrl_amd.checkpoint import NumpyLstmActor, read_checkpoint
-    from high_speed_quadrupedal_locomotion_by_irrl_amd.helper import DelayTool, obs_normalisation
+    from high_speed_quadrupedal_locomotion_by_irrl_amd.evaluate import condition, condition_state, contact_material, lowpass_alpha
+    from high_speed_quadrupedal_locomotion_by_irrl_amd.helper import obs_normalisation
     if args.trained_model is None:
         raise SystemExit("model path can't be ignored during test mode (--model)")
     ecfg = dict(cfg["environment"])
@@ -89,25 +90,20 @@ def run_test(args, cfg):
     ctrl = NumpyLstmActor.from_parameter_list(params, n_layers=len(N_LSTM))
     obs_mean, obs_std, action_mean, action_std = obs_normalisation(ecfg)
     dt = float(ecfg["control_dt"])
-    alpha = lambda f: 2 * math.pi * dt * f / (2 * math.pi * dt * f + 1.0)
-    a_vel, a_act = alpha(args.vel_filter_freq), alpha(args.act_filter_freq)
-    env.SetContactCoefficient(np.array([[0.8, 0.2, 0.01]], dtype=np.float32))      # run_bp_v5.py:317-318
+    # the default 1e6 Hz of --vel_filter_freq / --act_filter_freq goes THROUGH the filters here (alpha ~ 0.99992) as in the reference's loop,
+    # while --sweep maps >= 1e6 to "off" (run_sweep): a known difference between the two branches, kept as it is.
+    # The command low-pass is the reference's GaitGenerator filtering the gamepad / fixed command at 1 Hz.
+    a_cmd, a_vel, a_act = (lowpass_alpha(dt, f) for f in (args.cmd_filter_freq, args.vel_filter_freq, args.act_filter_freq))
+    env.SetContactCoefficient(contact_material(0.8))                                # run_bp_v5.py:317-318
     obs = env.reset()
-    d_tool = DelayTool(dt, dt * args.delay)
-    vel_his, act_his = np.zeros(35), np.zeros(12)
+    st = condition_state(obs, args.delay + 1)                                       # delay line (DelayTool), command and rate history
+    act_his = np.zeros(12)
     action_total = np.zeros([env.num_envs, env.num_acts], dtype=np.float32)
     rec = {k: [] for k in ("joint", "joint_dot", "posture", "omega", "phase", "act", "oss", "contact", "joint_effort", "cmd", "reward")}
-    cmd_target = np.array([args.flag_fix_cmd, 0.0, 0.0])
-    a_cmd = alpha(args.cmd_filter_freq)          # the reference's GaitGenerator low-passes the gamepad / fixed command at 1 Hz
-    cmd = np.zeros(3)
+    cmd_target = np.array([[args.flag_fix_cmd, 0.0, 0.0]])
     n_done = 0
     for t in range(args.steps):
-        cmd = (1 - a_cmd) * cmd + a_cmd * cmd_target
-        o = np.array(d_tool.input_output(obs[0, :].copy()), dtype=np.float64)
-        o[32:35] = (1 - a_vel) * vel_his[32:35] + a_vel * o[32:35]
-        o[17:29] = (1 - a_vel) * vel_his[17:29] + a_vel * o[17:29]
-        vel_his = o.copy()
-        o[0:3] = (cmd - obs_mean[0:3]) / obs_std[0:3]                                # Manual: the script owns obs[0:3]
+        o = condition(st, t, obs, [args.delay], cmd_target, a_cmd, a_vel, obs_mean[0:3], obs_std[0:3])[0]    # Manual: the script owns obs[0:3]
         action = ctrl.predict(o)
         action = (1 - a_act) * act_his + a_act * action
         act_his = action
@@ -117,13 +113,13 @@ def run_test(args, cfg):
         rec["joint"].append(ob_double[5:17]); rec["joint_dot"].append(ob_double[17:29]); rec["posture"].append(ob_double[29:32])
         rec["omega"].append(ob_double[32:35]); rec["phase"].append(ob_double[3:5]); rec["act"].append(action * action_std + action_mean)
         rec["oss"].append(state[0:37]); rec["contact"].append(state[37:41]); rec["joint_effort"].append(env.GetJointEffort()[0, :])
-        rec["cmd"].append(cmd.copy())
+        rec["cmd"].append(st["cmd"][0].copy())
         obs, reward, done, _ = env.step(action_total, visualize=False)
         rec["reward"].append(float(reward[0]))
         if done[0]:
             n_done += 1
             ctrl.reset()
-            cmd = np.zeros(3)                   # the env restarted from rest
+            st["cmd"][:] = 0.0                  # the env restarted from rest
     out = {k: np.asarray(v) for k, v in rec.items()}
     vx = out["oss"][:, 19]
     print("test: %d steps (%.2f s), command %.2f m/s, mean forward velocity %.3f m/s (last half %.3f), falls %d, mean reward %.4f"

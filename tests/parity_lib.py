@@ -11,13 +11,16 @@ Tolerances (fp32 kernels vs f64 oracle; the north-star asks for "a stated fp32 t
 Discrete outcomes (done flags, contact sets, RNG draws) must match exactly except where a threshold sits
 within rounding distance, which the fixed seeds below avoid.
 """
-import math
+import os
 
 import numpy as np
 
 import oracle as O
+from high_speed_quadrupedal_locomotion_by_irrl_amd.checkpoint import NumpyLstmActor
+from high_speed_quadrupedal_locomotion_by_irrl_amd.evaluate import body_statistics, reference_rollout
 
 S = O.S
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 TOL_STEP = dict(ob=5e-4, rew=2e-4, extra=2e-4, pos=2e-5, vel=5e-3)
 # THRESHOLD EVENTS.  gap <= 0 is a hard threshold: a toe (trunk corner, meteorite) that touches down in substep k in one precision and
 # in k + 1 in the other takes its impact one 0.25 ms substep apart, and the env-step's error is then the size of that IMPACT, not of
@@ -299,66 +302,21 @@ def ref_table(rows=900, seed=5):
 def closed_loop_reference_policy(env, cfg, cmd_vx, steps, fixture="actor_bp5_155.npz"):
     """Drive `env` (1 Manual-mode env with reset/step of the test adapters) with the reference's RaiSim-trained bp5_155 actor
     (tests/golden/actor_bp5_155.npz, decoded from IRRL/script/pkl/bp5_155.pkl by tools/gen_golden.py) exactly like the
-    evaluation script does (run_bp_v5.py:397-409: the command is written into obs[0:3]).  -> (vx per step, falls)."""
-    import os
-    from high_speed_quadrupedal_locomotion_by_irrl_amd.checkpoint import NumpyLstmActor
-    from high_speed_quadrupedal_locomotion_by_irrl_amd.helper import obs_normalisation
-    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", fixture))
-    ctrl = NumpyLstmActor([z["wx0"].astype(np.float64), z["wx1"].astype(np.float64)], [z["wh0"].astype(np.float64), z["wh1"].astype(np.float64)],
-                          [z["b0"].astype(np.float64), z["b1"].astype(np.float64)], z["pi_w"].astype(np.float64), z["pi_b"].astype(np.float64))
-    mean, std, _, _ = obs_normalisation(cfg)
-    cmd = np.array([cmd_vx, 0.0, 0.0])
-    ob = env.reset()
-    vx, falls = [], 0
-    for _ in range(steps):
-        o = np.array(ob[0], np.float64)
-        o[0:3] = (cmd - mean[0:3]) / std[0:3]
-        a = ctrl.predict(o)
-        ob, _, d, _ = env.step(a[None, :].astype(np.float32))
-        vx.append(env.get_state()[0, S["GV"]])
-        if d[0]:
-            falls += 1
-            ctrl.reset()
-    return np.array(vx), falls
-
-
-class BatchedNumpyActor(object):
-    """The two-layer LSTM actor of a fixture (tests/golden/actor_*.npz) for a batch of envs, float64 numpy."""
-
-    def __init__(self, fixture, n, clip=True):
-        import os
-        z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", fixture))
-        self.w = {k: z[k].astype(np.float64) for k in z.files}
-        self.c = [np.zeros((n, 48)), np.zeros((n, 48))]
-        self.h = [np.zeros((n, 48)), np.zeros((n, 48))]
-        self.clip = clip      # the rollout clips the sampled action (ppo2.py:533); the evaluation script hands the mean over as it is
-
-    def act(self, ob, done):
-        sig = lambda v: 1.0 / (1.0 + np.exp(-v))
-        x = np.asarray(ob, np.float64)
-        keep = (~np.asarray(done, bool)).astype(np.float64)[:, None]
-        for i in range(2):
-            self.c[i] *= keep
-            self.h[i] *= keep
-            z = x @ self.w["wx%d" % i] + self.h[i] @ self.w["wh%d" % i] + self.w["b%d" % i]
-            ig, fg, og, g = sig(z[:, :48]), sig(z[:, 48:96]), sig(z[:, 96:144]), np.tanh(z[:, 144:])
-            self.c[i] = fg * self.c[i] + ig * g
-            self.h[i] = og * np.tanh(self.c[i])
-            x = self.h[i]
-        a = x @ self.w["pi_w"] + self.w["pi_b"]
-        return (np.clip(a, -1.0, 1.0) if self.clip else a).astype(np.float32)
+    evaluation script does (run_bp_v5.py:397-409: the command is written into obs[0:3]): evaluate.reference_rollout without delay,
+    filters or a material call.  -> (vx per step, falls)."""
+    rec = reference_rollout(env, NumpyLstmActor.from_npz(os.path.join(GOLDEN, fixture)), cfg, 0, cmd_vx, steps, cmd_hz=None)
+    return rec["body"][:, 0, 7], int(rec["falls"][0])
 
 
 def closed_loop_training_mode(env, fixture, steps):
     """Training-mode envs (command process, resets, noise as configured) driven by the fixture's actor.
     -> dict(mean reward per step, mean |v_x|, terminations)."""
-    n = env.n
-    actor = BatchedNumpyActor(fixture, n)
+    actor = NumpyLstmActor.from_npz(os.path.join(GOLDEN, fixture))
     ob = env.observe()
-    done = np.zeros(n, bool)
+    done = np.zeros(env.n, bool)
     rew, vx, n_done = [], [], 0
     for _ in range(steps):
-        ob, r, done, _ = env.step(actor.act(ob, done))
+        ob, r, done, _ = env.step(np.asarray(actor.act(ob, done), np.float32))
         rew.append(r.mean())
         vx.append(np.abs(env.get_state()[:, S["GV"]]).mean())
         n_done += int(done.sum())
@@ -366,82 +324,18 @@ def closed_loop_training_mode(env, fixture, steps):
 
 
 # ---- the reference's simulator logs (tests/golden/raisim_body_logs.json <- tools/gen_raisim_log_fixture.py) ----
-def body_log_statistics(frames, window=None):
-    """Twin of tools/gen_raisim_log_fixture.py `summary`: frames [n, 13] = base x y z, quaternion wxyz, world linear velocity, world angular
-    velocity at 500 Hz -> the statistics the fixture holds for each RaiSim log."""
-    d = np.asarray(frames, np.float64)
-    h = window if window is not None else slice(0, len(d))
-    w, x, y, z = d[:, 3], d[:, 4], d[:, 5], d[:, 6]
-    R = np.zeros((len(d), 3, 3))
-    R[:, 0, 0] = 1 - 2 * (y * y + z * z); R[:, 0, 1] = 2 * (x * y - w * z); R[:, 0, 2] = 2 * (w * y + x * z)
-    R[:, 1, 0] = 2 * (x * y + w * z); R[:, 1, 1] = 1 - 2 * (x * x + z * z); R[:, 1, 2] = 2 * (y * z - w * x)
-    R[:, 2, 0] = 2 * (x * z - w * y); R[:, 2, 1] = 2 * (w * x + y * z); R[:, 2, 2] = 1 - 2 * (x * x + y * y)
-    vb = np.einsum("nji,nj->ni", R, d[:, 7:10])
-    wb = np.einsum("nji,nj->ni", R, d[:, 10:13])
-    roll = np.arctan2(2 * (w * x + y * z), 1 - 2 * (x * x + y * y))
-    pitch = np.arcsin(np.clip(2 * (w * y - x * z), -1, 1))
-    return {"vx_body_mean": float(vb[h, 0].mean()), "vx_body_std": float(vb[h, 0].std()), "vy_body_mean": float(vb[h, 1].mean()),
-            "z_mean": float(d[h, 2].mean()), "z_std": float(d[h, 2].std()), "roll_std": float(roll[h].std()),
-            "pitch_mean": float(pitch[h].mean()), "pitch_std": float(pitch[h].std()), "yaw_rate_mean": float(d[h, 12].mean()),
-            "roll_rate_body_std": float(wb[h, 0].std()), "pitch_rate_body_std": float(wb[h, 1].std()), "vz_std": float(d[h, 9].std()),
-            "vx_body": vb[:, 0]}
-
-
-def closed_loop_log_conditions(env, cfg, conds, fixture="actor_bp5_155.npz", cmd_hz=1.0, mu_warm=0.8, record_torque=False):
+def closed_loop_log_conditions(env, cfg, conds, fixture="actor_bp5_155.npz", cmd_hz=1.0, mu_warm=0.8):
     """One Manual-mode env per condition of the reference's RaiSim logs, all driven by the bp5_155 actor the way the evaluation script drives it
     (run_bp_v5.py:300-470: command low-passed at 1 Hz from zero and written into obs[0:3], observation delay line = DelayTool.py:5-21, material
-    through SetContactCoefficient like run_bp_v5.py:317-318).  conds[i] = dict(cmd, mu, delay [control steps], warm [steps before the recording
-    starts; the condition's mu is installed there, mu_warm before], frames).  -> list of [frames_i, 13] recordings (layout of the logs), falls,
-    and with record_torque the per-step joint torques / rates [frames_i, 12] each."""
-    from high_speed_quadrupedal_locomotion_by_irrl_amd.helper import obs_normalisation
-    n = env.n
-    assert n == len(conds)
-    actor = BatchedNumpyActor(fixture, n, clip=True)       # CustomerLstmNN.predict clips its output to [-1, 1] (NN:133-134)
-    mean, std, _, _ = obs_normalisation(cfg)
-    dt = float(cfg["control_dt"])
-    a_cmd = 2 * math.pi * dt * cmd_hz / (2 * math.pi * dt * cmd_hz + 1.0)
-    target = np.zeros((n, 3)); target[:, 0] = [c["cmd"] for c in conds]
-    delay = np.array([int(c.get("delay", 0)) for c in conds])
+    through SetContactCoefficient like run_bp_v5.py:317-318) in ONE evaluate.reference_rollout.  conds[i] = dict(cmd, mu, delay [control steps],
+    warm [steps before the recording starts; the condition's mu is installed there, mu_warm before], frames).
+    -> list of [frames_i, 13] recordings (layout of the logs), falls."""
+    assert env.n == len(conds)
     warm = np.array([int(c.get("warm", 0)) for c in conds])
     frames = np.array([int(c["frames"]) for c in conds])
-    steps = int((warm + frames).max())
-    coeff = np.zeros((n, 3), np.float32); coeff[:, 0] = mu_warm; coeff[:, 1] = 0.2; coeff[:, 2] = 0.01      # run_bp_v5.py:317
-    for i, c in enumerate(conds):
-        if warm[i] == 0:
-            coeff[i, 0] = c["mu"]
-    env.set_contact_coeff(coeff)
-    ob = env.reset()
-    depth = int(delay.max()) + 1
-    hist = np.repeat(np.asarray(ob, np.float64)[None], depth, 0)          # "the first sample fills the line"
-    cmd = np.zeros((n, 3))
-    done = np.zeros(n, bool)
-    falls = np.zeros(n, int)
-    rec = np.zeros((steps, n, 13))
-    tq = np.zeros((steps, n, 12)); qd = np.zeros((steps, n, 12))
-    rows = np.arange(n)
-    for t in range(steps):
-        switch = np.nonzero((warm == t) & (warm > 0))[0]
-        if len(switch):
-            for i in switch:
-                coeff[i, 0] = conds[i]["mu"]
-            env.set_contact_coeff(coeff)
-        cmd = (1 - a_cmd) * cmd + a_cmd * target
-        hist[t % depth] = np.asarray(ob, np.float64)
-        o = hist[(t - delay) % depth, rows].copy()
-        o[:, 0:3] = (cmd - mean[0:3]) / std[0:3]
-        ob, _, done, _ = env.step(actor.act(o, done))
-        st = env.get_state()
-        rec[t, :, 0:7] = st[:, S["GC"]:S["GC"] + 7]
-        rec[t, :, 7:13] = st[:, S["GV"]:S["GV"] + 6]
-        if record_torque:
-            tq[t] = st[:, S["TQ"]:S["TQ"] + 12]
-            qd[t] = st[:, S["GV"] + 6:S["GV"] + 18]
-        falls += done
-        cmd[done] = 0.0                                                    # the env restarted from rest
-    out = [rec[warm[i]:warm[i] + frames[i], i] for i in range(n)]
-    if record_torque:
-        return out, falls, [tq[warm[i]:warm[i] + frames[i], i] for i in range(n)], [qd[warm[i]:warm[i] + frames[i], i] for i in range(n)]
-    return out, falls
+    rec = reference_rollout(env, NumpyLstmActor.from_npz(os.path.join(GOLDEN, fixture)), cfg, [int(c.get("delay", 0)) for c in conds],
+                            [c["cmd"] for c in conds], int((warm + frames).max()), cmd_hz=cmd_hz, mu=[c["mu"] for c in conds], warm=warm, mu_warm=mu_warm)
+    return [rec["body"][warm[i]:warm[i] + frames[i], i] for i in range(len(conds))], rec["falls"]
 
 
 # Tolerances of the comparison with the RaiSim logs.  They are set from the LOGS' OWN scatter, not from this build's results: the reference
@@ -486,7 +380,7 @@ def compare_with_raisim_logs(env_factory, cfg_loader, fixture, max_frames=4000):
     for c, r, f in zip(conds, rec, falls):
         n = len(r)
         window = slice(0, n) if c["family"] == "steady_2s" else slice(n // 2, n)
-        got = body_log_statistics(r, window)
+        got = body_statistics(r, window)
         row = dict(name=c["name"], family=c["family"], mu=c["mu"], delay=c["delay"], falls=int(f), ref=c["log"]["stats"], got=got)
         if c["family"] == "start_from_rest_20s":
             vb = got["vx_body"]

@@ -1,6 +1,6 @@
 """The device-resident evaluation loop (evaluate.PolicyEvaluator -> irrl_lstm_eval_rollout, kernels csrc/eval_rollout.hpp) on the MI355X, piece by
 piece against what already exists: the numpy conditioning, the policy-step kernel, the float64 action filter, a second pool replaying the applied
-actions, get_state, parity_lib.body_log_statistics, and the host-driven closed loop.
+actions, get_state, evaluate.body_statistics, and the host-driven closed loop.
 
 One scenario is computed once and shared: bp5_manual_eval.yaml with N = 19 envs (ragged against the 16-env policy workgroup and the
 4-robots-per-wave env layout), the bp5_155 actor (hid 48), D = 6 with delays e % 6, commands 0.5 .. 5 m/s, frictions 0.05 .. 0.8, command / rate /
@@ -28,6 +28,7 @@ CMDS = np.linspace(0.5, 5.0, N)
 MUS = np.linspace(0.05, 0.8, N)
 HZ = dict(cmd_hz=1.0, vel_hz=50.0, act_hz=30.0)
 ALL = tuple(EV.RECORDERS)
+ACTOR = os.path.join(GOLDEN, "actor_bp5_155.npz")      # the reference's trained bp5_155 actor
 
 
 def _cfg(n=N):
@@ -39,27 +40,8 @@ def _pool(n=N, mus=MUS):
     from high_speed_quadrupedal_locomotion_by_irrl_amd.flexible_robot import FlexibleGymEnv
     env = FlexibleGymEnv(pkg.__BLACKPANTHER_V55_RESOURCE_DIRECTORY__, yaml.safe_dump(_cfg(n), default_flow_style=False, width=float("inf")))
     env.init()
-    coeff = np.zeros((n, 3), np.float32)
-    coeff[:, 0] = mus
-    coeff[:, 1] = 0.2
-    coeff[:, 2] = 0.01
-    env.SetContactCoefficient(coeff)
+    env.SetContactCoefficient(EV.contact_material(mus))
     return env
-
-
-def _policy():
-    """the reference's trained bp5_155 actor in a CustomLSTMPolicy (as tests/test_gpu_ppo.py loads it)"""
-    from high_speed_quadrupedal_locomotion_by_irrl_amd.policies import CustomLSTMPolicy
-    z = np.load(os.path.join(GOLDEN, "actor_bp5_155.npz"))
-    dev = torch.device("cuda")
-    torch.manual_seed(3)
-    pol = CustomLSTMPolicy().to(dev)
-    with torch.no_grad():
-        for i, l in enumerate(pol.lstm_pi):
-            l.wx.copy_(torch.from_numpy(z["wx%d" % i])); l.wh.copy_(torch.from_numpy(z["wh%d" % i])); l.b.copy_(torch.from_numpy(z["b%d" % i]))
-        pol.pi.w.copy_(torch.from_numpy(z["pi_w"])); pol.pi.b.copy_(torch.from_numpy(z["pi_b"]))
-    pol.prepare()
-    return pol
 
 
 def _drop(env):
@@ -74,7 +56,7 @@ def _cat(a, b):
 
 @pytest.fixture(scope="module")
 def scene():
-    pol = _policy()
+    pol = EV.load_policy(ACTOR, torch.device("cuda"))
     env = _pool()
     ev = EV.PolicyEvaluator(env, pol, DELAYS, CMDS, depth=D, **HZ)
     ob_reset = ev.obs.clone()
@@ -185,13 +167,13 @@ def test_statistics_equal_the_body_log_statistics_of_the_recorded_rows(scene):
     st = scene["stats"]
     worst = {}
     for e in range(N):
-        want = PL.body_log_statistics(scene["np"]["body"][:, e])
+        want = EV.body_statistics(scene["np"]["body"][:, e])
         for k, v in want.items():
             if k == "vx_body":
                 continue
             err = abs(st[k][e] - v) if k.endswith("_mean") else abs(st[k][e] - v) / abs(v)
             worst[k] = max(worst.get(k, 0.0), err)
-    print("worst |device - body_log_statistics| (means absolute, stds relative):", {k: "%.2e" % v for k, v in worst.items()})
+    print("worst |device - body_statistics| (means absolute, stds relative):", {k: "%.2e" % v for k, v in worst.items()})
     for k, v in worst.items():
         assert v <= (1e-9 if k.endswith("_mean") else 1e-6), (k, v)
     assert np.array_equal(st["falls"], scene["np"]["done"].sum(0)) and np.all(st["frames"] == T)
@@ -201,7 +183,7 @@ def test_filters_off_is_the_plain_loop_of_the_existing_calls():
     """a_cmd = a_vel = a_act = 1 and no delay: rec_obs_raw, rec_act_applied and the final pool state are bit-identical to a host-driven loop of
     the existing calls (command written into obs[:, 0:3] in torch, policy step, env.step on the clipped action)"""
     steps = 30
-    pol = _policy()
+    pol = EV.load_policy(ACTOR, torch.device("cuda"))
     env = _pool()
     ev = EV.PolicyEvaluator(env, pol, np.zeros(N, int), CMDS, cmd_hz=None, vel_hz=None, act_hz=None)
     assert ev.depth == 1 and ev.a_cmd == ev.a_vel == ev.a_act == 1.0
@@ -238,9 +220,9 @@ def test_sweep_agrees_with_the_host_driven_loop():
     conds = sorted([c for c in conds if c["family"] == "steady_2s" and c["delay"] <= 3 and c["mu"] == 0.8], key=lambda c: c["delay"])
     assert [c["delay"] for c in conds] == [0, 1, 2, 3] and all(c["cmd"] == 5.0 and c["warm"] == 1000 and c["frames"] == 1000 for c in conds)
     cfg = _cfg(4)
-    rows = EV.robustness_sweep(_policy(), cfg, [0.8], [0, 1, 2, 3], [5.0], warm_steps=1000, steps=1000)
+    rows = EV.robustness_sweep(ACTOR, cfg, [0.8], [0, 1, 2, 3], [5.0], warm_steps=1000, steps=1000)
     recs, falls = PL.closed_loop_log_conditions(HipVecEnv(cfg), cfg, conds)
-    host = [PL.body_log_statistics(r) for r in recs]
+    host = [EV.body_statistics(r) for r in recs]
     print("\ndevice evaluator (evaluate.robustness_sweep):\n" + EV.sweep_table(rows))
     print("host-driven loop (closed_loop_log_conditions on HipVecEnv):\n" + EV.sweep_table(
         [dict(mu=c["mu"], delay=c["delay"], cmd=c["cmd"], falls=int(f), **{k: v for k, v in h.items() if k != "vx_body"}) for c, f, h in zip(conds, falls, host)]))

@@ -1,6 +1,7 @@
 """Control steps per second of the policy evaluation loop at 4096 envs: the device-resident evaluator (evaluate.PolicyEvaluator: five launches per
-step, no host round trip) and the host-driven loop it replaces (tests/parity_lib.closed_loop_log_conditions through HipVecEnv: numpy boundary, float64
-numpy actor, get_state on every step).  Same pool size, same actor, same conditions; wall clock around work that ends in a device synchronise.
+step, no host round trip) and the host-driven loop it replaces (evaluate.reference_rollout, reached through tests/parity_lib.closed_loop_log_conditions,
+on HipVecEnv: numpy boundary, float64 numpy actor, get_state and every record on every step).  Same pool size, same actor, same conditions; wall
+clock around work that ends in a device synchronise.
 
     python tools/eval_rate.py [--envs 4096] [--steps 2000] [--host-steps 200]
 """
@@ -32,11 +33,10 @@ def main():
     cfg = yaml.safe_load(open(os.path.join(pkg.__BLACKPANTHER_V55_RESOURCE_DIRECTORY__, "bp5_manual_eval.yaml")))["environment"]
     cfg["num_envs"] = n
     delays, cmds, mus = np.arange(n) % 6, np.linspace(0.5, 5.0, n), np.linspace(0.05, 0.8, n)
-    pol = EV.load_policy(_actor_policy(), torch.device("cuda"))
+    pol = EV.load_policy(os.path.join(ROOT, "tests", "golden", "actor_bp5_155.npz"), torch.device("cuda"))
     env = FlexibleGymEnv(pkg.__BLACKPANTHER_V55_RESOURCE_DIRECTORY__, yaml.safe_dump(cfg, default_flow_style=False, width=float("inf")))
     env.init()
-    coeff = np.stack([mus, np.full(n, 0.2), np.full(n, 0.01)], 1).astype(np.float32)
-    env.SetContactCoefficient(coeff)
+    env.SetContactCoefficient(EV.contact_material(mus))
     out = {"envs": n}
     for name, record in (("statistics only", ()), ("all recorders", tuple(EV.RECORDERS))):
         ev = EV.PolicyEvaluator(env, pol, delays, cmds, cmd_hz=1.0, vel_hz=50.0, act_hz=30.0)
@@ -62,19 +62,6 @@ def main():
     print("host-driven loop (closed_loop_log_conditions on HipVecEnv): %d envs x %d steps in %.3f s = %.1f control steps/s (%.2f ms per step, %.3f M env-steps/s)"
           % (n, args.host_steps, dt, args.host_steps / dt, 1e3 * dt / args.host_steps, args.host_steps * n / dt / 1e6))
     print(json.dumps(out))
-
-
-def _actor_policy():
-    """CustomLSTMPolicy carrying the bp5_155 actor of tests/golden (the critic keeps its initialisation: the evaluation does not read it)"""
-    from high_speed_quadrupedal_locomotion_by_irrl_amd.policies import CustomLSTMPolicy
-    z = np.load(os.path.join(ROOT, "tests", "golden", "actor_bp5_155.npz"))
-    torch.manual_seed(3)
-    pol = CustomLSTMPolicy()
-    with torch.no_grad():
-        for i, l in enumerate(pol.lstm_pi):
-            l.wx.copy_(torch.from_numpy(z["wx%d" % i])); l.wh.copy_(torch.from_numpy(z["wh%d" % i])); l.b.copy_(torch.from_numpy(z["b%d" % i]))
-        pol.pi.w.copy_(torch.from_numpy(z["pi_w"])); pol.pi.b.copy_(torch.from_numpy(z["pi_b"]))
-    return pol
 
 
 if __name__ == "__main__":

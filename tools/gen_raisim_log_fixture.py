@@ -5,16 +5,21 @@
 (not in the repository) driving the `bp5_155` policy: 13 float32 per 500 Hz frame = base position (3), quaternion wxyz (4), world linear
 velocity (3), world angular velocity (3); decoder = Data_Visualization_Code/Figure3.py:17-75 (`seg_len` frames per segment, each segment stored
 feature-major), frame period 0.002 s = Figure3.py:193.  They are the only outputs of `world_->integrate()` the reference holds.
-This script imports nothing but numpy / yaml / json, decodes every log and writes per log: the Param keys, the first frame, summary statistics
-over the window the figure scripts use, the rise curve of the starts from rest and the dominant lines of the z / pitch spectra.  No reference
-source text goes into the fixture -- numbers only.      python tools/gen_raisim_log_fixture.py
+This script decodes every log with numpy / yaml / json alone and writes per log: the Param keys, the first frame, summary statistics over the
+window the figure scripts use (evaluate.body_statistics, the same function the tests apply to this build's recordings), the rise curve of the
+starts from rest and the dominant lines of the z / pitch spectra.  No reference source text goes into the fixture -- numbers only.
+    python tools/gen_raisim_log_fixture.py
 """
 import glob
 import json
 import os
+import sys
 
 import numpy as np
 import yaml
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from high_speed_quadrupedal_locomotion_by_irrl_amd.evaluate import body_frame, body_statistics  # noqa: E402
 
 SRC = "/root/reference/Exp_Raw_Data"
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "raisim_body_logs.json")
@@ -33,30 +38,6 @@ def decode(bin_file, cfg):
         tail = min(head + seg, total)
         data[:, head:tail] = raw[head * 13:tail * 13].reshape(13, -1)
     return data.T
-
-
-def body_frame(d):
-    w, x, y, z = d[:, 3], d[:, 4], d[:, 5], d[:, 6]
-    R = np.zeros((len(d), 3, 3))
-    R[:, 0, 0] = 1 - 2 * (y * y + z * z); R[:, 0, 1] = 2 * (x * y - w * z); R[:, 0, 2] = 2 * (w * y + x * z)
-    R[:, 1, 0] = 2 * (x * y + w * z); R[:, 1, 1] = 1 - 2 * (x * x + z * z); R[:, 1, 2] = 2 * (y * z - w * x)
-    R[:, 2, 0] = 2 * (x * z - w * y); R[:, 2, 1] = 2 * (w * x + y * z); R[:, 2, 2] = 1 - 2 * (x * x + y * y)
-    vb = np.einsum("nji,nj->ni", R, d[:, 7:10])
-    wb = np.einsum("nji,nj->ni", R, d[:, 10:13])
-    roll = np.arctan2(2 * (w * x + y * z), 1 - 2 * (x * x + y * y))
-    pitch = np.arcsin(np.clip(2 * (w * y - x * z), -1, 1))
-    return vb, wb, roll, pitch
-
-
-def summary(d, window):
-    """Statistics of the frames in `window` (a slice) -- the same function of a [frames, 13] array the tests apply to this build's recording
-    (tests/parity_lib.py body_log_statistics is its twin)."""
-    vb, wb, roll, pitch = body_frame(d)
-    h = window
-    return {"vx_body_mean": float(vb[h, 0].mean()), "vx_body_std": float(vb[h, 0].std()), "vy_body_mean": float(vb[h, 1].mean()),
-            "z_mean": float(d[h, 2].mean()), "z_std": float(d[h, 2].std()), "roll_std": float(roll[h].std()),
-            "pitch_mean": float(pitch[h].mean()), "pitch_std": float(pitch[h].std()), "yaw_rate_mean": float(d[h, 12].mean()),
-            "roll_rate_body_std": float(wb[h, 0].std()), "pitch_rate_body_std": float(wb[h, 1].std()), "vz_std": float(d[h, 9].std())}
 
 
 def spectrum_lines(sig, k=3):
@@ -83,19 +64,20 @@ def main():
         else:
             family, window = "steady_20s", slice(n // 2, n)
         # consistency of the decoding itself: |q| = 1, x(t) is the integral of the logged v_x
+        stats = body_statistics(d, window)
+        vb = stats.pop("vx_body")
         qn = np.sqrt((d[:, 3:7] ** 2).sum(1))
         dx_int = float(np.sum(0.5 * (d[1:, 7] + d[:-1, 7])) * DT)
         rec = {"name": date, "params": {k: v for k, v in cfg.items()}, "frames": n, "family": family, "runs_in_minus_x": bool(reverse),
-               "first_frame": [float(v) for v in d[0]], "window": [window.start, window.stop], "stats": summary(d, window),
+               "first_frame": [float(v) for v in d[0]], "window": [window.start, window.stop], "stats": stats,
                "check": {"quat_norm_min": float(qn.min()), "quat_norm_max": float(qn.max()), "x_travel": float(d[-1, 0] - d[0, 0]),
                          "x_travel_from_logged_vx": dx_int},
                "z_spectrum_hz_amp": spectrum_lines(d[window, 2]), "pitch_spectrum_hz_amp": spectrum_lines(body_frame(d)[3][window])}
         if from_rest:
-            vb = body_frame(d)[0]
             ts = [0.1, 0.2, 0.3, 0.5, 0.75, 1.0, 1.25, 1.5, 2.0, 3.0, 4.0]
-            rec["rise"] = {"t": ts, "vx_body": [float(vb[int(t / DT) - 25:int(t / DT) + 25, 0].mean()) for t in ts]}   # 0.1 s = half a stride
+            rec["rise"] = {"t": ts, "vx_body": [float(vb[int(t / DT) - 25:int(t / DT) + 25].mean()) for t in ts]}   # 0.1 s = half a stride
             final = rec["stats"]["vx_body_mean"]
-            above = np.nonzero(np.convolve(vb[:, 0], np.ones(100) / 100, "same") >= 0.9 * final)[0]
+            above = np.nonzero(np.convolve(vb, np.ones(100) / 100, "same") >= 0.9 * final)[0]
             rec["time_to_90_percent_s"] = float(above[0] * DT)
         logs.append(rec)
     # the power log of one run (Figure5.py:98-126): per frame Num_sub_loop x 12 joint torques then Num_sub_loop x 12 joint rates, 4 kHz
