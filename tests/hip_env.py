@@ -48,6 +48,11 @@ class HipVecEnv(object):
         self.impl.GetSphereInfo(out)
         return out
 
+    def joint_effort(self):
+        out = np.zeros((self.n, 12), np.float32)
+        self.impl.GetJointEffort(out)
+        return out
+
     def get_state(self):
         return self.impl.get_state()
 

@@ -117,6 +117,11 @@ class EmuVecEnv(object):
         self.l.emu_heightfield(self.h, _fp(out))
         return out
 
+    def joint_effort(self):
+        """what the C-ABI's GetJointEffort returns (irrl_env_joint_effort_host copies EnvState::torque): the clamped torques of the step's
+        last substep -- words 61..72 of the flat state"""
+        return self.get_state()[:, 61:73].astype(np.float32)
+
     def get_state(self):
         out = np.zeros((self.n, STATE_DIM), np.float64)
         self.l.emu_get_state(self.h, out.ctypes.data_as(C.POINTER(C.c_double)))

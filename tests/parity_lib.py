@@ -99,9 +99,14 @@ def check_probe(orc, cand):
 
 
 def check_teacher_forced(orc, cand, steps, seed=0, action_scale=0.5, force_terminal_every=0, max_factor=10.0, perturb=None, cap_factor=None,
-                         event_budget=0.005):
+                         event_budget=0.005, pos_xy_ulps=0, after_step=None):
     """Every step starts from the oracle's state (rounded to f32) in BOTH implementations.  max_factor / cap_factor / event_budget: the
-    threshold-event rule stated at the top of this file."""
+    threshold-event rule stated at the top of this file.
+    pos_xy_ulps > 0: the base's x and y (gc[0:2]) are held to TOL_STEP["pos"] + pos_xy_ulps f32 ulps of their own magnitude instead of
+    TOL_STEP["pos"] alone (their error is scaled by the ratio of the two, so percentile, event and cap rules read the same); the other 17
+    position entries stay under TOL_STEP["pos"].  For robots hundreds of metres from the origin: one f32 ulp at 250 m is 1.5e-5 m, and a
+    control step is eight substeps of x += dt * v, each rounded to at most half an ulp -> 4 ulps.
+    after_step(k, d_o, d_c): called behind every step with both pools in their post-step state (witnesses of the edge scenarios below)."""
     if cap_factor is None:
         cap_factor = 10.0 * max_factor
     rng = np.random.RandomState(seed)
@@ -122,6 +127,8 @@ def check_teacher_forced(orc, cand, steps, seed=0, action_scale=0.5, force_termi
         ob_o, r_o, d_o, x_o = orc.step(a)
         ob_c, r_c, d_c, x_c = cand.step(a)
         so, sc = orc.get_state(), cand.get_state()
+        if after_step is not None:
+            after_step(k, d_o, d_c)
         # A toe whose gap sits within rounding distance of zero can enter the contact list in one precision and
         # not in the other (gap <= 0 is a hard threshold); the same holds for the termination thresholds.  Such
         # envs are counted, must stay rare (< 0.5 % of env-steps), and are left out of this step's error norms.
@@ -135,7 +142,11 @@ def check_teacher_forced(orc, cand, steps, seed=0, action_scale=0.5, force_termi
         samples["ob"].append(np.abs(ob_o[ok] - ob_c[ok]).max(1))
         samples["rew"].append(np.abs(r_o[ok] - r_c[ok]))
         samples["extra"].append(np.abs(x_o[ok] - x_c[ok]).max(1))
-        samples["pos"].append(np.abs(so[ok, 0:19] - sc[ok, 0:19]).max(1))
+        e_pos = np.abs(so[ok, 0:19] - sc[ok, 0:19])
+        if pos_xy_ulps > 0:
+            tol_xy = TOL_STEP["pos"] + pos_xy_ulps * np.spacing(np.abs(so[ok, 0:2]).astype(np.float32)).astype(np.float64)
+            e_pos[:, 0:2] *= TOL_STEP["pos"] / tol_xy
+        samples["pos"].append(e_pos.max(1))
         samples["vel"].append(np.abs(so[ok, 19:37] - sc[ok, 19:37]).max(1))
         # the meteorite of a Crutial pool (zeros otherwise): centre, velocity, radius, mass, body type
         sph = np.abs(so[ok, S["SPHERE"]:S["SPHERE"] + 9] - sc[ok, S["SPHERE"]:S["SPHERE"] + 9])
@@ -214,6 +225,189 @@ def tilt_onto_box_corner(st, k, rng, z_lo=0.152, z_hi=0.172, tilt_lo=52.0, tilt_
         out[e, S["GV"]:S["GV"] + 3] = [0.3 * rng.normal(), 0.3 * rng.normal(), -0.5 * rng.uniform()]
         out[e, S["GV"] + 3:S["GV"] + 6] = 1.0 * rng.normal(size=3)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Edge scenarios: regions of the state space that random actions from a fresh reset never reach (long episode clocks, the rim of
+# the height field, the sloped and crossed parts of the motor's torque-speed envelope, the z > 0.65 m and tilt terminations).
+# Each is a `perturb` hook of check_teacher_forced with a WITNESS: a count, taken on the reference side (the state handed to
+# set_state, or the oracle's own flags), that the scenario really was in its region -- a passing test cannot be one that never
+# got there.  What a hook draws depends on (step k, env i) alone, not on the order of anybody else's draws.
+# ------------------------------------------------------------------------------------------------------------------------
+def _draws(tag, k, i):
+    return np.random.RandomState([tag, k, i])
+
+
+class long_clock(object):
+    """Step 0 puts env i at episode frame frame0 + 13 i: the episode clock t0 + frame * control_dt (f32 in the kernels) is what the
+    phase observation, the gait generator and the time-based contact flag are evaluated at.  Witness: every env of the oracle is still
+    at or beyond frame0 after the last step (no reset took the clock back)."""
+
+    def __init__(self, orc, frame0):
+        self.orc, self.frame0 = orc, int(frame0)
+
+    def __call__(self, st, k, rng):
+        if k == 0:
+            st[:, S["FRAME"]] = self.frame0 + 13 * np.arange(st.shape[0])
+        return st
+
+    def witness(self):
+        frames = self.orc.get_state()[:, S["FRAME"]]
+        print("[long_clock] frame0 %d: the oracle's frames end at %d .. %d" % (self.frame0, frames.min(), frames.max()))
+        assert frames.min() >= self.frame0, frames
+
+
+class motor_envelope(object):
+    """Airborne robots (base at 0.5 m, base at rest: no toe reaches the ground, no contact threshold) whose joint rates are uniform in
+    +-3 rad/s, except that in env i of step k joint j = (k n + i) % 12 gets a rate inside regime r = ((k n + i) // 12) % 5 of the motor
+    speed w = qd * ratio (1.55 on the knees, 1 otherwise; ENV:1273-1312):
+        0: -1.3 w_max .. -w_max   1: -w_max .. -w_crit   2: |w| < w_crit   3: w_crit .. w_max   4: w_max .. 1.3 w_max
+    In 1 and 3 one bound of the clamp slopes; in 0 and 4 it has gone through zero (a motor beyond its no-load speed can only brake).
+    The sloped bound CROSSES the other one -- up < low, so that the ORDER of max(min(tau, up), low) is the result -- only from
+    |w| = 2 w_max - w_crit on (65.8 rad/s with the evaluation config's 14.2 / 40): `crossed=True` draws regimes 0 and 4 from 1 to 1.3
+    times that speed instead, and counts them.  Witness: the (joint, regime) counts recomputed from the f32-rounded state handed to set_state --
+    12 envs x 40 steps put 8 samples into each of the 60 cells -- and every other joint inside regime 2.  `after_step` compares the
+    joint effort getters (the clamped torque of the step's last substep) at the bound of test_diagnostic_getters_match_the_oracle_values."""
+    RATIO = np.tile([1.0, 1.0, 1.55], 4)
+    EFFORT_ATOL = 2e-2
+
+    def __init__(self, orc, cand, w_crit, w_max, crossed=False):
+        self.orc, self.cand = orc, cand
+        self.inner = np.array([-w_max, -w_crit, w_crit, w_max], float)
+        self.w_cross = 2.0 * w_max - w_crit
+        outer = self.w_cross if crossed else w_max
+        self.lo = np.array([-1.3 * outer, -w_max, -w_crit, w_crit, outer])
+        self.hi = np.array([-outer, -w_crit, w_crit, w_max, 1.3 * outer])
+        self.crossed, self.n_crossed = crossed, 0
+        self.counts = np.zeros((12, 5), int)
+        self.others_outside = 0
+        self.effort_worst = 0.0
+        self.effort_scale = 0.0
+
+    def __call__(self, st, k, rng):
+        n = st.shape[0]
+        gv = S["GV"]
+        cell = []
+        for i in range(n):
+            r = _draws(2, k, i)
+            st[i, S["GC"] + 2] = 0.5
+            st[i, gv:gv + 6] = 0.0
+            st[i, gv + 6:gv + 18] = r.uniform(-3.0, 3.0, 12)
+            j, reg = (k * n + i) % 12, ((k * n + i) // 12) % 5
+            st[i, gv + 6 + j] = r.uniform(self.lo[reg], self.hi[reg]) / self.RATIO[j]
+            cell.append(j)
+        st = f32_round_state(st)
+        w = st[:, gv + 6:gv + 18] * self.RATIO
+        regime = np.searchsorted(self.inner, w)                    # 0 .. 4
+        for i, j in enumerate(cell):
+            self.counts[j, regime[i, j]] += 1
+            self.n_crossed += int(abs(w[i, j]) > self.w_cross)
+            self.others_outside += int((np.delete(regime[i], j) != 2).sum())
+        return st
+
+    def after_step(self, k, d_o, d_c):
+        je_o, je_c = self.orc.joint_effort(), self.cand.joint_effort()
+        self.effort_worst = max(self.effort_worst, float(np.abs(je_c - je_o).max()))
+        self.effort_scale = max(self.effort_scale, float(np.abs(je_o).max()))
+        np.testing.assert_allclose(je_c, je_o, atol=self.EFFORT_ATOL)
+
+    def witness(self, n_done=0):
+        total = int(self.counts.sum())
+        print("[motor_envelope] samples per (joint, regime) cell: min %d max %d of %d env-steps, %d with crossed bounds; other joints outside "
+              "|w| < w_crit: %d; joint effort: worst error %.2e N m (bound %.0e), largest %.1f N m; episodes ended: %d"
+              % (self.counts.min(), self.counts.max(), total, self.n_crossed, self.others_outside, self.effort_worst, self.EFFORT_ATOL, self.effort_scale, n_done))
+        assert total >= 480 and self.counts.min() >= total // 60, self.counts
+        assert self.n_crossed == (int(self.counts[:, [0, 4]].sum()) if self.crossed else 0)
+        assert self.others_outside == 0 and n_done == 0
+
+
+class field_edge(object):
+    """Rough ground (bp5_terrain.yaml: the 500 m x 20 m height field, 5000 x 500 cells): every step moves every robot to the rim,
+    y = +-(10 + U(-0.3, 0.3)) for axis "y", x = +-(250 + U(-0.4, 0.4)) for "x", both with half those offsets for "corner", and lifts the
+    base by h(new) - h(old) so that the feet keep their height over the ground.  Beyond the table terrain_sample clamps the cell
+    coordinate: the ground continues with the rim's values.  The four loads of the clamped coordinate stay inside the table for every
+    finite input; what is checked is the clamped VALUES.  Witness (independent numpy kinematics on the state handed to set_state):
+    at least 40 % of the toe placements are beyond the table and at least 25 % inside."""
+    HALF_X, HALF_Y = 250.0, 10.0
+
+    def __init__(self, orc, axis, seed=0):
+        assert axis in ("x", "y", "corner")
+        self.orc, self.axis, self.seed = orc, axis, seed
+        self.beyond = self.total = 0
+
+    def __call__(self, st, k, rng):
+        import _np_robot as R
+        scale = 0.5 if self.axis == "corner" else 1.0
+        for i in range(st.shape[0]):
+            r = _draws(3 + 16 * self.seed, k, i)
+            dx, dy = scale * r.uniform(-0.4, 0.4), scale * r.uniform(-0.3, 0.3)
+            h_old = self.orc.terrain_sample(st[i, 0], st[i, 1])[0]
+            s = k + i
+            if self.axis in ("x", "corner"):
+                st[i, 0] = (1.0 if s % 2 == 0 else -1.0) * (self.HALF_X + dx)
+            if self.axis == "y":
+                st[i, 1] = (1.0 if s % 2 == 0 else -1.0) * (self.HALF_Y + dy)
+            if self.axis == "corner":
+                st[i, 1] = (1.0 if (s // 2) % 2 == 0 else -1.0) * (self.HALF_Y + dy)
+            st[i, 2] += self.orc.terrain_sample(st[i, 0], st[i, 1])[0] - h_old
+        st = f32_round_state(st)
+        for i in range(st.shape[0]):
+            toes = R.toe_positions(st[i, :19])
+            out = np.zeros(4, bool)
+            if self.axis in ("x", "corner"):
+                out |= np.abs(toes[:, 0]) > self.HALF_X
+            if self.axis in ("y", "corner"):
+                out |= np.abs(toes[:, 1]) > self.HALF_Y
+            self.beyond += int(out.sum())
+            self.total += 4
+        return st
+
+    def witness(self):
+        share = self.beyond / float(self.total)
+        print("[field_edge %s] %d of %d toe placements beyond the table (%.0f %%), %d inside (%.0f %%)"
+              % (self.axis, self.beyond, self.total, 100 * share, self.total - self.beyond, 100 * (1 - share)))
+        assert share >= 0.40 and 1.0 - share >= 0.25, (self.beyond, self.total)
+
+
+class other_terminations(object):
+    """The two termination clauses no other scenario builds a case for (ENV:1560: z < 0.15 | z > 0.65 | cos(tilt) < 0.5).  Step k
+    changes env k % n, by k % 4: base at 0.66 m | at 0.64 m | tilted 63 degrees | 57 degrees about a horizontal axis at 0.5 m -- always
+    at rest (one control step moves a resting base by 2e-5 m and well under a degree).  Witness (`after_step`): the 0.66 m and 63 degree
+    envs are `done` in that very step in BOTH implementations, and the oracle keeps the 0.64 m and 57 degree envs running; that the
+    candidate keeps them running too is check_teacher_forced's own d_o == d_c rule."""
+    CASES = ("z 0.66", "z 0.64", "tilt 63", "tilt 57")
+
+    def __init__(self):
+        self.case = {}
+        self.done_both = np.zeros(4, int)
+        self.seen = np.zeros(4, int)
+
+    def __call__(self, st, k, rng):
+        i, c = k % st.shape[0], k % 4
+        gc, gv = S["GC"], S["GV"]
+        st[i, gv:gv + 18] = 0.0
+        if c < 2:
+            st[i, gc + 2] = (0.66, 0.64)[c]
+        else:
+            r = _draws(4, k, i)
+            phi, half = r.uniform(0.0, 2.0 * np.pi), 0.5 * np.radians((63.0, 57.0)[c - 2])
+            st[i, gc + 2] = 0.5
+            st[i, gc + 3:gc + 7] = [np.cos(half), np.sin(half) * np.cos(phi), np.sin(half) * np.sin(phi), 0.0]
+        self.case[k] = (i, c)
+        return st
+
+    def after_step(self, k, d_o, d_c):
+        i, c = self.case[k]
+        self.seen[c] += 1
+        self.done_both[c] += int(d_o[i] and d_c[i])
+        if c in (0, 2):
+            assert d_o[i] and d_c[i], "step %d env %d (%s): done oracle %s candidate %s" % (k, i, self.CASES[c], d_o[i], d_c[i])
+        else:
+            assert not d_o[i], "step %d env %d (%s): the oracle ended the near-miss episode" % (k, i, self.CASES[c])
+
+    def witness(self):
+        print("[other_terminations] done in both / cases built: " + ", ".join("%s: %d / %d" % (n, d, s) for n, d, s in zip(self.CASES, self.done_both, self.seen)))
+        assert self.seen.min() >= 4 and (self.done_both[[0, 2]] == self.seen[[0, 2]]).all() and (self.done_both[[1, 3]] == 0).all()
 
 
 def check_free_running(make_orc, make_cand, cfg, preroll=90):

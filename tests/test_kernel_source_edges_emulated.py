@@ -1,0 +1,151 @@
+"""The kernel source (csrc/env_core.hpp, through the host lane emulation, both lane layouts) against the f64 oracle in the regions
+that random actions from a fresh reset never reach -- long episode clocks, the rim of the height field, the sloped and crossed parts
+of the motor's torque-speed envelope, the z > 0.65 m and tilt terminations.  Scenario hooks and their witnesses: parity_lib.py
+("Edge scenarios"); the same scenarios through the C-ABI on an MI355X: test_gpu_parity_edges.py.  Tolerances: the unchanged TOL_STEP,
+TERRAIN_MAX_FACTOR on rough ground, and the derived 4 f32 ulps on base x / y where robots are moved to x = +-250 m."""
+import numpy as np
+import pytest
+
+import oracle as O
+import parity_lib as PL
+from conftest import load_env_cfg
+from host_emulation import emu as E
+
+EMUS = [E.EmuVecEnv, E.EmuVecEnv16]
+STEPS = 40
+# The supported horizon of an episode: 25 000 control steps (50 s, 2.5 times the longest RaiSim recording).  The episode clock
+# t0 + frame * control_dt is f32 in the kernels; its rounding reaches the observation through the gait phase, and the error grows
+# linearly with the frame (it meets the 5e-4 observation tolerance near 100 000 frames: DESIGN.md section 5).
+HORIZON_FRAMES = 25000
+CLOCK_CFGS = {"eval": ("bp5_manual_eval.yaml", {}), "eval_time_based_contact": ("bp5_manual_eval.yaml", {"TimeBasedContact": True}),
+              "train": ("default_cfg.yaml", {})}
+
+
+def clock_case(make_cand, cfg_key, frame0, n=8, **over):
+    name, extra = CLOCK_CFGS[cfg_key]
+    cfg = load_env_cfg(name, num_envs=n, **dict(extra, **over))
+    orc, cand = O.OracleVecEnv(cfg), make_cand(cfg)
+    hook = PL.long_clock(orc, frame0)
+    worst, n_done = PL.check_teacher_forced(orc, cand, steps=STEPS, seed=1, perturb=hook)
+    hook.witness()
+    return worst
+
+
+def field_edge_case(make_cand, axis, n=8, **over):
+    cfg = load_env_cfg("bp5_terrain.yaml", num_envs=n, **over)
+    orc, cand = O.OracleVecEnv(cfg), make_cand(cfg)
+    hook = PL.field_edge(orc, axis)
+    worst, n_done = PL.check_teacher_forced(orc, cand, steps=STEPS, seed=2, perturb=hook, max_factor=PL.TERRAIN_MAX_FACTOR,
+                                            pos_xy_ulps=0 if axis == "y" else 4)
+    hook.witness()
+    return worst
+
+
+def motor_envelope_case(make_cand, n=12, crossed=False, **over):
+    cfg = load_env_cfg("bp5_manual_eval.yaml", num_envs=n, **over)
+    assert (cfg["MotorCriticalSpeed"], cfg["MotorMaxSpeed"]) == (14.2, 40)
+    orc, cand = O.OracleVecEnv(cfg), make_cand(cfg)
+    hook = PL.motor_envelope(orc, cand, cfg["MotorCriticalSpeed"], cfg["MotorMaxSpeed"], crossed=crossed)
+    worst, n_done = PL.check_teacher_forced(orc, cand, steps=STEPS, seed=3, action_scale=1.0, perturb=hook, after_step=hook.after_step)
+    hook.witness(n_done)
+    assert worst["threshold_events"] == 0           # airborne: there is no threshold to straddle
+    return worst
+
+
+def terminations_case(make_cand, n=13, **over):
+    cfg = load_env_cfg("bp5_imitation.yaml", num_envs=n, **over)      # (no observation noise: ENV:1560 tests the NOISY observation's tilt entry)
+    orc, cand = O.OracleVecEnv(cfg), make_cand(cfg)
+    hook = PL.other_terminations()
+    worst, n_done = PL.check_teacher_forced(orc, cand, steps=STEPS, seed=4, perturb=hook, after_step=hook.after_step)
+    hook.witness()
+    assert n_done >= STEPS // 2
+    return worst
+
+
+def edge_state(scenario, n):
+    """-> (config, the f32-rounded state of an oracle pool after the scenario's step-0 perturbation): where the multi-step tests start"""
+    if scenario == "clock":
+        cfg = load_env_cfg("default_cfg.yaml", num_envs=n)
+        orc = O.OracleVecEnv(cfg)
+        hook = PL.long_clock(orc, HORIZON_FRAMES - 10)            # 16 steps from here cross the horizon
+    elif scenario == "corner":
+        cfg = load_env_cfg("bp5_terrain.yaml", num_envs=n)
+        orc = O.OracleVecEnv(cfg)
+        hook = PL.field_edge(orc, "corner")
+    else:
+        cfg = load_env_cfg("bp5_manual_eval.yaml", num_envs=n)
+        orc = O.OracleVecEnv(cfg)
+        hook = PL.motor_envelope(orc, None, cfg["MotorCriticalSpeed"], cfg["MotorMaxSpeed"])
+    return cfg, PL.f32_round_state(hook(PL.f32_round_state(orc.get_state()), 0, None))
+
+
+@pytest.mark.parametrize("emu", EMUS)
+@pytest.mark.parametrize("frame0", [6390, 10000, HORIZON_FRAMES])        # 6390: two_pi_over_period * t passes 2^8 pi / 2 inside the 40 steps
+@pytest.mark.parametrize("cfg_key", sorted(CLOCK_CFGS))
+def test_long_episode_clock(emu, frame0, cfg_key):
+    clock_case(emu, cfg_key, frame0)
+
+
+@pytest.mark.parametrize("emu", EMUS)
+@pytest.mark.parametrize("axis", ["y", "x", "corner"])
+def test_rim_of_the_height_field(emu, axis):
+    field_edge_case(emu, axis)
+
+
+@pytest.mark.parametrize("emu", EMUS)
+@pytest.mark.parametrize("crossed", [False, True], ids=["to_1.3_w_max", "crossed"])
+def test_motor_envelope_slopes_and_crossed_bounds(emu, crossed):
+    motor_envelope_case(emu, crossed=crossed)
+
+
+@pytest.mark.parametrize("emu", EMUS)
+def test_height_and_tilt_terminations(emu):
+    terminations_case(emu)
+
+
+@pytest.mark.parametrize("scenario", ["clock", "corner", "motor"])
+def test_carried_lane_context_equals_store_and_load_from_edge_states(scenario):
+    """The host counterpart of test_multi_step_kernel_equals_one_launch_per_step_from_edge_states (test_gpu_parity_edges.py): 16 steps with
+    the lane context carried in registers (sub-lanes 1-3 poisoned behind every step) == 16 step() calls, from frame 24 990, from over the
+    corner of the height field and from joint rates beyond the motor's no-load speed -- every step's outputs and the final pool, bit for bit."""
+    n, K = 12, 16
+    cfg, st = edge_state(scenario, n)
+    a, b = E.EmuVecEnv16(cfg), E.EmuVecEnv16(cfg)
+    a.set_state(st)
+    b.set_state(st)
+    rng = np.random.RandomState(8)
+    acts = np.stack([PL.random_actions(rng, n, 0.5) for _ in range(K)])
+    got = a.steps_carried(acts, poison=True)
+    want = [b.step(acts[k]) for k in range(K)]
+    for j, name in enumerate(("ob", "reward", "done", "extraInfo")):
+        assert np.array_equal(np.stack([w[j] for w in want]), got[j], equal_nan=True), name
+    np.testing.assert_array_equal(a.get_state(), b.get_state())
+
+
+def test_base_xy_allowance_is_off_by_default_and_scales_only_x_and_y():
+    """pos_xy_ulps: with the default 0 a base 5.8e-5 m off at x = 250 m (4 f32 ulps there are 6.1e-5 m) fails the position check as before;
+    with 4 it passes under 2e-5 + 6.1e-5 m; the same offset on z (entry 2) fails either way."""
+    cfg = load_env_cfg("bp5_imitation.yaml", num_envs=4)
+
+    class Shifted(O.OracleVecEnv):
+        entry, shift = 0, 5.8e-5
+
+        def get_state(self):
+            st = O.OracleVecEnv.get_state(self)
+            st[:, self.entry] += self.shift
+            return st
+
+    def far_out(st, k, rng):
+        st[:, 0] = 250.0
+        return st
+
+    for entry, ulps, passes in ((0, 0, False), (0, 4, True), (2, 4, False)):
+        orc, cand = O.OracleVecEnv(cfg), Shifted(cfg)
+        cand.entry = entry
+        try:
+            PL.check_teacher_forced(orc, cand, steps=3, perturb=far_out, pos_xy_ulps=ulps)
+            ok = True
+        except AssertionError:
+            ok = False
+        assert ok == passes, (entry, ulps)
+    assert 4 * np.spacing(np.float32(250.0)) == pytest.approx(6.1e-5, rel=0.01)
