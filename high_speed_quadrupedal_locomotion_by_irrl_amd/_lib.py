@@ -98,6 +98,10 @@ SIGNATURES = {
     # cmd_mean, cmd_std (host), clip | 8 recorders, stats | stream
     "irrl_lstm_eval_rollout": (C.c_int, [vp, C.c_int, C.c_longlong] + [C.c_int] * 3 + [vp] * 6 + [C.c_int] + [vp] * 8 + [vp] * 2 + [C.c_float] * 3 + [fp, fp, C.c_int]
                                + [vp] * 9 + [vp]),
+    # the same loop as one persistent launch: the same argument list
+    "irrl_lstm_eval_rollout_persistent": (C.c_int, [vp, C.c_int, C.c_longlong] + [C.c_int] * 3 + [vp] * 6 + [C.c_int] + [vp] * 8 + [vp] * 2 + [C.c_float] * 3
+                                          + [fp, fp, C.c_int] + [vp] * 9 + [vp]),
+    "irrl_lstm_eval_rollout_supports": (C.c_int, [vp, C.c_int]),
 }
 
 

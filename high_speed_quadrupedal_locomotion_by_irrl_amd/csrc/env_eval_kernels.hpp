@@ -1,0 +1,222 @@
+// env_eval_kernels.hpp -- THE WHOLE POLICY EVALUATION IN ONE LAUNCH (irrl_lstm_eval_rollout_persistent): the closed loop of eval_rollout.hpp --
+// conditioning -> actor -> action filter -> env.step -> record -- for all `steps` control steps inside one persistent kernel, modelled on
+// irrl_rollout_persistent_actor_wave_kernel (env_rollout_kernels.hpp).  NO INCLUDE GUARD: env_kernels.hip (its IRRL_EVAL_UNIT compilation, a
+// translation unit of this kernel's own) includes this file once per solver form, inside extern "C", with IRRL_RK / IRRL_ROLLOUT_RULE as there.
+//
+// 256-thread workgroups of 16 robots; a WAVE owns robots e4 .. e4 + 3 for all steps: the actor's operands go to LDS once, c stays in registers,
+// h of both layers in the wave's scratch, the env lane context in registers (load_lane once, lane_carry, irrl_store_lane_back once).  Beside the
+// actor's scratch a wave keeps the evaluator's state of its robots in LDS for the whole launch: vel_his [4][35] | act_his [4][12] | cmd [4][3]
+// (200 floats), the per-env parameters delay [4] | cmd_target [4][3], and the f64 statistics [4][IRRL_EVAL_STAT_COUNT] -- read once in front of
+// the loop, written back once behind it.  Only wave-level synchronisation inside the loop; nothing waits for another wave.
+//
+// Per step k, element for element the arithmetic of the five-launch form (eval_elements.hpp is the one text of it), so every buffer the two
+// forms share is BIT-IDENTICAL:
+//   1. conditioning of the wave's 4 x 35 elements: lane l owns elements l, l + 64, l + 128 for the whole launch.  The raw observation comes out
+//      of the scratch X (loaded from `obs` in front of step 0, written by the env step's observe_write afterwards); the ring lives in the
+//      caller's buffer, and the lane that wrote a ring element is the only one that ever reads it (no cross-lane visibility of global stores is
+//      needed).  The conditioned row overwrites X (the ring holds the raw copy).
+//   2. lstm_actor_wave_body<48, RAW_ACT> (deterministic: no noise, no rollout rows): the scratch ACT gets the unclipped mean,
+//   3. the [-1, 1] clip if the caller asked for it (the heads' own expression) and the action low-pass into ACT / act_his,
+//   4. step_compute with the action out of ACT; its Tail hook sees the FINAL lane (post-reset on a `done`: what the record kernel reads from the
+//      pool): observe_write into X, reward / done into the scratch, the body / torque / reward / done recorders, cmd = 0 on done and the f64
+//      statistics by the robot's lead lane (the sequence of additions per slot is the five-launch form's: the accumulators START from the
+//      caller's column),
+//   5. the raw-observation recorder out of X.
+// The critic is NOT run: the critic's half of lstm_state [N, 4 hid : 8 hid] and the `value` column of the work array are left untouched (the
+// actor never reads them, so calls of either form may follow each other).  HID 48, ob 35, act 12.
+__global__ void IRRL_ENV_BOUNDS
+IRRL_RK(irrl_eval_persistent_kernel)(EnvParams P_, EnvState S_, float *ob, float *reward, uint8_t *done, float *extra, PolicyStepArgs a_, EvalArgs ev_) {
+  IRRL_BIND_ARGS
+  IRRL_BIND_POLICY_ARGS(a, a_)
+  IRRL_BIND_EVAL_ARGS(ev, ev_)
+  constexpr int HID = 48, NG = HID / 16, SD = 8 * HID;
+  constexpr int NS = IRRL_EVAL_STAT_COUNT;
+  typedef LstmWaveLds<HID> LAY;
+  // the evaluator's part of a wave's scratch (floats)
+  constexpr int EV_VH = 0, EV_AH = 140, EV_CM = 188, EV_DL = 200, EV_TG = 204, EV_FLOATS = 216;
+  __shared__ __attribute__((aligned(16))) float wsl[4][LAY::FLOATS];
+  __shared__ __attribute__((aligned(16))) float evl[4][EV_FLOATS];
+  __shared__ double stl[4][4 * NS];
+  __shared__ float head_w[HID * 16];
+  __shared__ __attribute__((aligned(16))) float lds_w[LstmWaveImage<HID>::FLOATS];      // the ACTOR's operands, [gate column][K] (policy_step.hpp)
+  lstm_wave_image_stage<HID, 256>(a, lds_w);
+  for (int i = (int)threadIdx.x; i < HID * a.act_dim; i += 256) head_w[i] = a.pi_w[i];
+  const int steps = ev.steps;
+  const int lane0_ = (int)(threadIdx.x & 63u);
+  const int wave_ = (int)(threadIdx.x >> 6);
+  const int e4_ = ((int)blockIdx.x * 4 + wave_) * 4;            // the wave's first robot
+  const int rl_ = lane0_ >> 4;                                   // the robot this lane integrates (env part)
+  int env0_ = e4_ + rl_;
+  const int leg0_ = (lane0_ >> 2) & 3;
+  const bool valid0_ = (env0_ < P.n_envs) && ((lane0_ & 3) == 0);
+  if (env0_ >= P.n_envs) env0_ = P.n_envs - 1;
+  irrl_plain::EnvLane L;
+  irrl_plain::load_lane(P, S, env0_, leg0_, L, true);
+  float *ws = wsl[wave_];
+  float *es = evl[wave_];
+  double *st = stl[wave_];
+  // policy part: this lane's robot is l & 3, its unit inside a column group l >> 2
+  const int pr_ = lane0_ & 3, pq_ = lane0_ >> 2;
+  const bool pok_ = e4_ + pr_ < a.N;
+  const int pe_ = pok_ ? e4_ + pr_ : a.N - 1;
+  float cst[2][NG], bias[2][NG];
+#pragma unroll
+  for (int G = 0; G < NG; G++) {
+    cst[0][G] = a.states_in[(size_t)pe_ * SD + 16 * G + pq_];
+    cst[1][G] = a.states_in[(size_t)pe_ * SD + 2 * HID + 16 * G + pq_];
+    bias[0][G] = a.w[2][64 * G + lane0_];
+    bias[1][G] = a.w[5][64 * G + lane0_];
+  }
+  // the wave's robots that exist: 4, fewer in the pool's last wave, none (<= 0) in a wave behind it
+  const int nrob_ = (a.N - e4_ < 4) ? a.N - e4_ : 4;
+  // the robot whose action this lane's env part applies: its own, or -- an idle row of the pool's last wave, which shadows the last robot with
+  // its stores masked -- the last robot's, as the step kernel's clamped index reads it.  (The shadow must stay the last robot's exact twin: the
+  // contact sweeps of a substep end for the whole wave at once, so a row that went its own way would change how many sweeps its neighbours get.)
+  const int ra_ = rl_ < nrob_ ? rl_ : nrob_ > 0 ? nrob_ - 1 : 0;
+  {   // the state of things in front of step 0, from memory: observations, done flags, h of both layers; the evaluator's state and parameters
+    for (int i = lane0_; i < 4 * 35; i += 64) {
+      const bool ok = i < nrob_ * 35;
+      ws[LAY::X + i] = ok ? ev.obs[(size_t)e4_ * 35 + i] : 0.0f;
+      es[EV_VH + i] = ok ? ev.vel_his[(size_t)e4_ * 35 + i] : 0.0f;
+    }
+    for (int i = lane0_; i < 4 * HID; i += 64) {
+      const int r = i / HID, k = i - r * HID;
+      const int e = (e4_ + r < a.N) ? e4_ + r : a.N - 1;
+      ws[LAY::H0 + i] = a.states_in[(size_t)e * SD + HID + k];
+      ws[LAY::H1 + i] = a.states_in[(size_t)e * SD + 3 * HID + k];
+    }
+    if (lane0_ < 4 * 12) {
+      ws[LAY::ACT + lane0_] = 0.0f;
+      es[EV_AH + lane0_] = (lane0_ < nrob_ * 12) ? ev.act_his[(size_t)e4_ * 12 + lane0_] : 0.0f;
+    }
+    if (lane0_ < 4 * 3) {
+      const bool ok = lane0_ < nrob_ * 3;
+      es[EV_CM + lane0_] = ok ? ev.cmd[(size_t)e4_ * 3 + lane0_] : 0.0f;
+      es[EV_TG + lane0_] = ok ? ev.cmd_target[(size_t)e4_ * 3 + lane0_] : 0.0f;
+    }
+    if (lane0_ < 4) {
+      const int e = (e4_ + lane0_ < a.N) ? e4_ + lane0_ : a.N - 1;
+      ws[LAY::DON + lane0_] = a.dones[e] ? 1.0f : 0.0f;
+      ws[LAY::REW + lane0_] = 0.0f;
+      es[EV_DL + lane0_] = __int_as_float(ev.delay[e]);
+    }
+    if (ev.stats)
+      for (int i = lane0_; i < 4 * NS; i += 64) {
+        const int r = i / NS, s = i - r * NS;
+        st[i] = (r < nrob_) ? ev.stats[(size_t)s * (size_t)a.N + (size_t)(e4_ + r)] : 0.0;
+      }
+  }
+  int slot_ = ev.slot;
+  __syncthreads();   // the LDS image, the head weights and the wave's scratch have landed
+  for (int k = 0; k < steps; k++) {
+    int lane = lane0_;
+    asm volatile("" : "+v"(lane));     // (see irrl_rollout_persistent_kernel_l16: keeps the per-lane addresses inside the loop)
+    const EvalArgs &ek = IRRL_PARAMS_REFRESH(ev);
+    const size_t rowk = (size_t)ek.row + (size_t)k;
+    // ---- 1. conditioning: this lane's elements lane, lane + 64, lane + 128 of the wave's [4][35] ----
+    {
+      const size_t plane = (size_t)ek.N * 35;
+#pragma unroll
+      for (int u = 0; u < 3; u++) {
+        const int i = lane + 64 * u;
+        if (i < nrob_ * 35) {
+          const int r = i / 35, j = i - r * 35;
+          const size_t gi = (size_t)e4_ * 35 + (size_t)i;
+          const float o = irrl_eval_condition_element(ek, slot_, j, ws[LAY::X + i], ek.ring + gi, plane, __float_as_int(es[EV_DL + r]), es + EV_VH + i,
+                                                      es + EV_CM + r * 3 + j, es + EV_TG + r * 3 + j);
+          ws[LAY::X + i] = o;
+          ek.obs_cond[gi] = o;
+          if (ek.rec_obs_cond) ek.rec_obs_cond[rowk * plane + gi] = o;
+        }
+      }
+    }
+    PS_WAVE_SYNC();    // the conditioned rows are in the scratch
+    // ---- 2. the actor of the wave's four robots ----
+    {
+      const PolicyStepArgs ak = IRRL_PARAMS_REFRESH(a);
+      lstm_actor_wave_body<HID, true>(ak, e4_, ws, lds_w, head_w, lane, cst, bias);
+    }
+    PS_WAVE_SYNC();    // this wave's actions (the mean, before the clip) are in its scratch
+    // ---- 3. clip and action low-pass: lane (robot, action) ----
+    if (lane < nrob_ * 12) {
+      const float act = ws[LAY::ACT + lane];
+      const float x = ek.clip ? fminf(fmaxf(act, -1.0f), 1.0f) : act;
+      const float y = irrl_eval_action_element(ek.a_act, x, es + EV_AH + lane);
+      ws[LAY::ACT + lane] = y;
+      const size_t gi = (size_t)e4_ * 12 + (size_t)lane;
+      ek.applied[gi] = y;
+      const size_t r = rowk * (size_t)ek.N * 12 + gi;
+      if (ek.rec_act_clipped) ek.rec_act_clipped[r] = x;
+      if (ek.rec_act_applied) ek.rec_act_applied[r] = y;
+    }
+    PS_WAVE_SYNC();    // the applied actions are in the scratch
+    // ---- 4. env.step of the wave's four robots ----
+    {
+      int env_ = env0_;
+      asm volatile("" : "+v"(env_));
+      if (k > 0) irrl_plain::lane_carry(L);
+      irrl_plain::ActionRegs act;
+#pragma unroll
+      for (int j = 0; j < 3; j++) act.a[j] = ws[LAY::ACT + ra_ * 12 + leg0_ * 3 + j];
+      irrl_plain::step_compute<IRRL_ROLLOUT_RULE, irrl_plain::NoStepHook>(
+          IRRL_PARAMS_REFRESH(P), L, env_, leg0_, valid0_, act, ob, reward, done, extra, irrl_plain::NoStepHook(),
+          [&](const irrl_plain::EnvLane &Lf, float rew, bool dn) {
+            // (inside the epilogue's sub-lane-0 region) the scaled observation row, the reward and the done flag once more, into the scratch
+            irrl_plain::observe_write(P, rl_, leg0_, valid0_, Lf, ws + LAY::X);
+            if (valid0_) {
+              const size_t N = (size_t)ek.N, e = (size_t)env_;
+              if (ek.rec_torque) {
+                float *t = ek.rec_torque + rowk * N * 12 + e * 12 + leg0_ * 3;
+                t[0] = Lf.tq[0]; t[1] = Lf.tq[1]; t[2] = Lf.tq[2];
+              }
+              if (leg0_ == 0) {
+                ws[LAY::REW + rl_] = rew; ws[LAY::DON + rl_] = dn ? 1.0f : 0.0f;
+                if (ek.rec_body) {     // base x y z, quaternion wxyz | world linear and angular velocity: the words store_lane leaves in the pool
+                  float *b = ek.rec_body + rowk * N * 13 + e * 13;
+                  b[0] = Lf.pos.x; b[1] = Lf.pos.y; b[2] = Lf.pos.z; b[3] = Lf.qw; b[4] = Lf.qx; b[5] = Lf.qy; b[6] = Lf.qz;
+                  b[7] = Lf.vw.x; b[8] = Lf.vw.y; b[9] = Lf.vw.z; b[10] = Lf.ww.x; b[11] = Lf.ww.y; b[12] = Lf.ww.z;
+                }
+                if (ek.rec_reward) ek.rec_reward[rowk * N + e] = rew;
+                if (ek.rec_done) ek.rec_done[rowk * N + e] = dn ? 1 : 0;
+                irrl_eval_env_epilogue(dn, es + EV_CM + rl_ * 3, ek.stats ? st + rl_ * NS : nullptr, (size_t)1, Lf.pos.z, Lf.qw, Lf.qx, Lf.qy, Lf.qz, Lf.vw.x,
+                                       Lf.vw.y, Lf.vw.z, Lf.ww.x, Lf.ww.y, Lf.ww.z);
+              }
+            }
+          });
+    }
+    PS_WAVE_SYNC();    // observations / done flags / the reset commands of step k are in the scratch
+    // ---- 5. the raw-observation recorder: the row the env step just left in X ----
+    if (ek.rec_obs_raw) {
+      const size_t plane = (size_t)ek.N * 35;
+#pragma unroll
+      for (int u = 0; u < 3; u++) {
+        const int i = lane + 64 * u;
+        if (i < nrob_ * 35) ek.rec_obs_raw[rowk * plane + (size_t)e4_ * 35 + (size_t)i] = ws[LAY::X + i];
+      }
+    }
+    slot_ = slot_ + 1 == ek.D ? 0 : slot_ + 1;
+  }
+  if (steps > 0) {
+    irrl_store_lane_back(P, S, env0_, leg0_, valid0_, L);
+    PS_WAVE_SYNC();
+    // the evaluator's state behind the last step (obs / done were stored by the env step itself)
+    for (int i = lane0_; i < nrob_ * 35; i += 64) ev.vel_his[(size_t)e4_ * 35 + i] = es[EV_VH + i];
+    if (lane0_ < nrob_ * 12) ev.act_his[(size_t)e4_ * 12 + lane0_] = es[EV_AH + lane0_];
+    if (lane0_ < nrob_ * 3) ev.cmd[(size_t)e4_ * 3 + lane0_] = es[EV_CM + lane0_];
+    if (ev.stats)
+      for (int i = lane0_; i < nrob_ * NS; i += 64) {
+        const int r = i / NS, s = i - r * NS;
+        ev.stats[(size_t)s * (size_t)a.N + (size_t)(e4_ + r)] = st[i];
+      }
+    if (pok_) {      // the actor's LSTM state behind the last step (the critic's half is not touched)
+#pragma unroll
+      for (int G = 0; G < NG; G++) {
+        const int u = 16 * G + pq_;
+        a.states_out[(size_t)pe_ * SD + u] = cst[0][G];
+        a.states_out[(size_t)pe_ * SD + HID + u] = ws[LAY::H0 + pr_ * HID + u];
+        a.states_out[(size_t)pe_ * SD + 2 * HID + u] = cst[1][G];
+        a.states_out[(size_t)pe_ * SD + 3 * HID + u] = ws[LAY::H1 + pr_ * HID + u];
+      }
+    }
+  }
+}

@@ -27,9 +27,12 @@
 #if IRRL_LANES_PER_ROBOT == 16
 #include "policy_step.hpp"   // the LSTM policy's rollout step (device code shared with lstm_kernels.hip)
 #endif
+#ifdef IRRL_EVAL_UNIT
+#include "eval_elements.hpp"   // the evaluation loop's per-element arithmetic and its argument block (shared with eval_rollout.hpp)
+#endif
 #include "env_kernels_decl.h"   // every kernel below is declared there: the launcher (irrl_env_abi.hip) sees the same signatures
 
-// This file is compiled three times (build.py): once per lane layout, kernel names suffixed _l16 / _l4, and the 4-lane layout once more for
+// This file is compiled five times (build.py): once per lane layout, kernel names suffixed _l16 / _l4, and the 4-lane layout once more for
 // TWO waves per SIMD (_l4w2, -DIRRL_L4_WAVES2: 256 registers per wave, ~130-220 of the step kernels' values in scratch).  Pools of more than
 // 16 384 robots are more 4-lane waves than the chip has SIMDs; two resident waves issue 1.35 x what one does (HISTORY.md Appendix C, 2a), which
 // pays for the spills: 32 768 envs 394 -> 450 M env-steps/s, 131 072 envs 394 -> 482 M, 16 384 envs (one wave per SIMD either way) 393 -> 386 M
@@ -89,11 +92,17 @@ __device__ __forceinline__ LaneCtx irrl_lane_ctx(const EnvParams &P, int wave, i
   const PolicyStepArgs &A0 = irrl_kernarg<PolicyStepArgs>((unsigned)IRRL_KERNARG_ALIGN(                                            \
       IRRL_KERNARG_ALIGN(sizeof(EnvParams), EnvState) + sizeof(EnvState) + (NPTR) * sizeof(void *), PolicyStepArgs));
 #define IRRL_BIND_POLICY_ARGS(A0, A_) IRRL_BIND_POLICY_ARGS_N(A0, A_, 4)
+// the evaluation kernel's EvalArgs, the argument behind its PolicyStepArgs (behind P, S and four pointers)
+#define IRRL_BIND_EVAL_ARGS(E0, E_)                                                                                                \
+  const EvalArgs &E0 = irrl_kernarg<EvalArgs>((unsigned)IRRL_KERNARG_ALIGN(                                                        \
+      IRRL_KERNARG_ALIGN(IRRL_KERNARG_ALIGN(sizeof(EnvParams), EnvState) + sizeof(EnvState) + 4 * sizeof(void *), PolicyStepArgs) + \
+          sizeof(PolicyStepArgs), EvalArgs));
 #else
 #define IRRL_BIND_ARGS const EnvParams &P = P_; const EnvState &S = S_;
 #define IRRL_PARAMS_REFRESH(P) (P)
 #define IRRL_BIND_POLICY_ARGS_N(A0, A_, NPTR) const PolicyStepArgs &A0 = A_;
 #define IRRL_BIND_POLICY_ARGS(A0, A_) IRRL_BIND_POLICY_ARGS_N(A0, A_, 4)
+#define IRRL_BIND_EVAL_ARGS(E0, E_) const EvalArgs &E0 = E_;
 #endif
 #define IRRL_LANE_PROLOGUE IRRL_LANE_PROLOGUE_B(irrl_xcd_block())          /* the stand-alone lane kernels */
 #define IRRL_LANE_PROLOGUE_IDENTITY IRRL_LANE_PROLOGUE_B((int)blockIdx.x)  /* kernels whose policy part addresses robots by blockIdx */
@@ -131,7 +140,27 @@ struct PolicyStepBase {
 };
 #endif
 
-#ifdef IRRL_ROLLOUT_RT_UNIT
+#ifdef IRRL_EVAL_UNIT
+// FIFTH COMPILATION (build.py, 16-lane layout): nothing but the persistent evaluation kernel (env_eval_kernels.hpp) in its two solver forms --
+// RULE IRRL_RULE_SHIPPED gives irrl_eval_persistent_kernel_l16, RULE 1 (settings read from EnvParams) irrl_eval_persistent_kernel_rt_l16.  A unit
+// of its own for the reason the run-time-solver twins below have one: a second caller of the policy bodies inside an existing unit changes the
+// schedule of the shipped kernels there, and those are held to their ISA.
+#if IRRL_LANES_PER_ROBOT != 16
+#error "the evaluation kernel exists in the 16-lane layout only"
+#endif
+extern "C" {
+#define IRRL_RK(name) name##_l16
+#define IRRL_ROLLOUT_RULE IRRL_RULE_SHIPPED
+#include "env_eval_kernels.hpp"
+#undef IRRL_RK
+#undef IRRL_ROLLOUT_RULE
+#define IRRL_RK(name) name##_rt_l16
+#define IRRL_ROLLOUT_RULE 1
+#include "env_eval_kernels.hpp"
+#undef IRRL_RK
+#undef IRRL_ROLLOUT_RULE
+}  // extern "C"
+#elif defined(IRRL_ROLLOUT_RT_UNIT)
 // FOURTH COMPILATION (build.py, 16-lane layout): nothing but the run-time-solver twins of the kernels that run the policy in the same launch --
 // env_rollout_kernels.hpp with RULE 1, the published rule with contact_jacobi / contact_exit / contact_tol / contact_iters / loop_count / terrain
 // read from EnvParams: pools whose config has no Contact* keys, ContactSolver 1, another sweep cap or exit test, or a control step of other than

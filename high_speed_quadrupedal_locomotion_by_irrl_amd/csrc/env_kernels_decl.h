@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include "env_params.h"
 struct PolicyStepArgs;   // policy_step.hpp
+struct EvalArgs;         // eval_elements.hpp
 
 // The env kernels are compiled in two lane layouts from the same source (csrc/env_kernels.hip, see build.py):
 //   _l16  16 lanes per robot (lanes_hip16.hpp): 4 robots per wave -- fills all 1024 SIMDs at 4096 robots, shortest step
@@ -46,3 +47,7 @@ extern "C" __global__ void irrl_terminal_kernel(EnvParams, EnvState, uint8_t *);
 IRRL_DECLARE_ROLLOUT_KERNELS(_l16)
 IRRL_DECLARE_ROLLOUT_KERNELS(_rt_l16)
 #undef IRRL_DECLARE_ROLLOUT_KERNELS
+// the whole policy evaluation in one launch (16-lane layout; csrc/env_eval_kernels.hpp, a translation unit of its own): same suffixes
+#define IRRL_EVAL_KERNEL_ARGS EnvParams, EnvState, float *, float *, uint8_t *, float *, PolicyStepArgs, EvalArgs
+extern "C" __global__ void irrl_eval_persistent_kernel_l16(IRRL_EVAL_KERNEL_ARGS);
+extern "C" __global__ void irrl_eval_persistent_kernel_rt_l16(IRRL_EVAL_KERNEL_ARGS);

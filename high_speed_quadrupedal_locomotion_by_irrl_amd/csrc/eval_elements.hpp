@@ -1,0 +1,111 @@
+// eval_elements.hpp -- the per-element arithmetic of the evaluation loop (irrl_lstm_eval_rollout[_persistent], include/irrl_env.h) in ONE text:
+// the three small kernels of eval_rollout.hpp and the persistent kernel of env_eval_kernels.hpp call these functions, and so does a host
+// program (tests/eval_elements_main.cpp) -- this header includes no HIP header and compiles with any C++ compiler.
+// The library is built with -ffp-contract=on: a multiply-add fuses where the source writes a * b + c in ONE expression and nowhere else, so the
+// shape of the expressions below is part of the contract between the two device forms (bit-identical buffers).
+#pragma once
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+#include "../../include/irrl_env.h"
+
+#ifdef __HIPCC__
+#define IRRL_EVAL_FN __host__ __device__
+#else
+#define IRRL_EVAL_FN
+#endif
+
+struct EvalArgs {
+  int N, D;
+  int slot;          // t % D: the ring plane this step (the persistent kernel: its first step) writes
+  int steps;         // the persistent kernel's step count (the per-step kernels do not read it)
+  int clip;          // the persistent kernel: apply the [-1, 1] clipped action (the per-step kernels get act_in chosen by the host)
+  long long row;     // row of the recorders this step (the persistent kernel: its first step) fills
+  // evaluator state
+  float *ring;       // [D, N, 35]
+  float *cmd;        // [N, 3] low-passed command
+  float *vel_his;    // [N, 35] previous conditioned observation
+  float *act_his;    // [N, 12] previous applied action
+  const float *obs;  // [N, 35] raw observation (the env step's output)
+  const uint8_t *done;   // [N]
+  // per-env parameters
+  const int *delay;          // [N], 0 .. D-1 (clamped here: a bad value must not become an out-of-bounds plane)
+  const float *cmd_target;   // [N, 3]
+  float a_cmd, a_vel, a_act;
+  float mean0, mean1, mean2, std0, std1, std2;   // scaling of obs[0:3]
+  // work arrays
+  float *obs_cond;        // [N, 35] what the policy step reads
+  const float *act_in;    // [N, 12] the actor's output (clipped mean, or the mean)
+  float *applied;         // [N, 12] what the env step reads
+  const float *reward;    // [N]
+  // the pool (after the env step)
+  const float *gc, *gv, *torque;
+  // recorders, each may be NULL
+  float *rec_obs_cond, *rec_act_clipped, *rec_act_applied, *rec_body, *rec_torque, *rec_obs_raw, *rec_reward;
+  uint8_t *rec_done;
+  double *stats;     // [IRRL_EVAL_STAT_COUNT, N] or NULL
+};
+
+// steps 1-6 of a control step for ONE element (env e, component j) of the observation: ring[slot] = raw, the delayed read, the rate low-pass,
+// vel_his, and for j < 3 the command low-pass and its scaling.  ring_i: the element's column of the ring (ring + e * 35 + j; planes are
+// `plane` = N * 35 floats apart); vel_his_i / cmd_ej / target_ej: the element's own words (cmd_ej and target_ej are read for j < 3 only).
+// A delay outside 0 .. D-1 is clamped.  -> what the actor sees.
+static inline IRRL_EVAL_FN float irrl_eval_condition_element(const EvalArgs &a, int slot, int j, float raw, float *ring_i, size_t plane, int delay_e,
+                                                             float *vel_his_i, float *cmd_ej, const float *target_ej) {
+  ring_i[(size_t)slot * plane] = raw;
+  int d = delay_e;
+  d = d < 0 ? 0 : d > a.D - 1 ? a.D - 1 : d;
+  int slot_r = slot - d;
+  if (slot_r < 0) slot_r += a.D;
+  float o = d == 0 ? raw : ring_i[(size_t)slot_r * plane];
+  const bool rate = (j >= 17 && j < 29) || j >= 32;     // joint rates, body angular velocity
+  if (rate && a.a_vel != 1.0f) o = (1.0f - a.a_vel) * *vel_his_i + a.a_vel * o;
+  *vel_his_i = o;                                       // the whole vector, before the command overwrite
+  if (j < 3) {
+    const float target = *target_ej;
+    const float c = a.a_cmd != 1.0f ? (1.0f - a.a_cmd) * *cmd_ej + a.a_cmd * target : target;
+    *cmd_ej = c;
+    o = (c - (j == 0 ? a.mean0 : j == 1 ? a.mean1 : a.mean2)) / (j == 0 ? a.std0 : j == 1 ? a.std1 : a.std2);
+  }
+  return o;
+}
+
+// steps 9-10 for ONE action element: the low-pass between the policy step and the env step; act_his_i is updated.  -> the applied action
+static inline IRRL_EVAL_FN float irrl_eval_action_element(float a_act, float x, float *act_his_i) {
+  const float y = a_act != 1.0f ? (1.0f - a_act) * *act_his_i + a_act * x : x;
+  *act_his_i = y;
+  return y;
+}
+
+// steps 12-13 for ONE env, after the env step: cmd = 0 on done, and (s != NULL) the statistics of the body frame -- world -> body frame, roll and
+// pitch in f64 from the f32 samples, added to the env's column s[slot * n].  pz: base height; w x y z: the base quaternion; v0 v1 v2 / o0 o1 o2:
+// world linear / angular velocity.
+static inline IRRL_EVAL_FN void irrl_eval_env_epilogue(bool dn, float *cmd_e, double *s, size_t n, float pz_, float w_, float x_, float y_, float z_,
+                                                       float v0_, float v1_, float v2_, float o0_, float o1_, float o2_) {
+  if (dn) { cmd_e[0] = 0.0f; cmd_e[1] = 0.0f; cmd_e[2] = 0.0f; }   // the env restarted from rest
+  if (!s) return;
+  const double pz = pz_;
+  const double w = w_, x = x_, y = y_, z = z_;
+  const double v0 = v0_, v1 = v1_, v2 = v2_;
+  const double o0 = o0_, o1 = o1_, o2 = o2_;
+  const double r00 = 1 - 2 * (y * y + z * z), r01 = 2 * (x * y - w * z);
+  const double r10 = 2 * (x * y + w * z), r11 = 1 - 2 * (x * x + z * z);
+  const double r20 = 2 * (x * z - w * y), r21 = 2 * (w * x + y * z);
+  const double vx = r00 * v0 + r10 * v1 + r20 * v2, vy = r01 * v0 + r11 * v1 + r21 * v2;
+  const double wx = r00 * o0 + r10 * o1 + r20 * o2, wy = r01 * o0 + r11 * o1 + r21 * o2;
+  const double roll = atan2(2 * (w * x + y * z), 1 - 2 * (x * x + y * y));
+  double sp = 2 * (w * y - x * z);
+  sp = sp > 1.0 ? 1.0 : sp < -1.0 ? -1.0 : sp;
+  const double pitch = asin(sp);
+  s[IRRL_EVAL_STAT_N * n] += 1.0;
+  s[IRRL_EVAL_STAT_VX * n] += vx; s[IRRL_EVAL_STAT_VX2 * n] += vx * vx;
+  s[IRRL_EVAL_STAT_Z * n] += pz; s[IRRL_EVAL_STAT_Z2 * n] += pz * pz;
+  s[IRRL_EVAL_STAT_ROLL * n] += roll; s[IRRL_EVAL_STAT_ROLL2 * n] += roll * roll;
+  s[IRRL_EVAL_STAT_PITCH * n] += pitch; s[IRRL_EVAL_STAT_PITCH2 * n] += pitch * pitch;
+  s[IRRL_EVAL_STAT_WX * n] += wx; s[IRRL_EVAL_STAT_WX2 * n] += wx * wx;
+  s[IRRL_EVAL_STAT_WY * n] += wy; s[IRRL_EVAL_STAT_WY2 * n] += wy * wy;
+  s[IRRL_EVAL_STAT_VZ * n] += v2; s[IRRL_EVAL_STAT_VZ2 * n] += v2 * v2;
+  s[IRRL_EVAL_STAT_VY * n] += vy;
+  s[IRRL_EVAL_STAT_WZ * n] += o2;
+  s[IRRL_EVAL_STAT_FALLS * n] += dn ? 1.0 : 0.0;
+}

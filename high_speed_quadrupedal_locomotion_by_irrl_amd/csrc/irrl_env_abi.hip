@@ -492,56 +492,124 @@ int irrl_lstm_rollout(irrl_env *h, int steps, int hid, int ob_dim, int act_dim, 
 // The evaluation loop of a trained policy (csrc/eval_rollout.hpp): per control step conditioning -> policy step -> action filter -> env step -> record,
 // plain launches back to back on `hip_stream`.  Stateless: everything that survives a call lives in the caller's buffers, so a second call with
 // step0 + steps continues where the first stopped.  Arguments are refused BEFORE any HIP call.
+// (the refusals of both forms of the loop, with the entry point's own name in the texts)
+static int eval_rollout_check(const char *who, irrl_env *h, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *lstm_w, const float *pi_w,
+                              const float *pi_b, const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring, float *cmd, float *vel_his,
+                              float *act_his, float *lstm_state, uint8_t *done, float *obs, float *work, const int *delay, const float *cmd_target, float a_cmd,
+                              float a_vel, float a_act, const float *cmd_mean, const float *cmd_std) {
+  const std::string w = std::string(who) + ": ";
+  if (!h) { g_err = w + "NULL handle"; return 1; }
+  if (steps < 0 || step0 < 0) { g_err = w + "steps >= 0, step0 >= 0"; return 1; }
+  if (depth < 1) { g_err = w + "the delay line needs a depth D >= 1"; return 1; }
+  if (hid != 32 && hid != 48 && hid != 64) { g_err = w + "hid is 32, 48 or 64"; return 1; }
+  if (ob_dim != 35 || act_dim != 12) { g_err = w + "ob 35, act 12"; return 1; }
+  if (!(ring && cmd && vel_his && act_his && lstm_state && done && obs && work && delay && cmd_target && cmd_mean && cmd_std)) {
+    g_err = w + "NULL evaluator state / parameter pointer"; return 1;
+  }
+  if (!(lstm_w && pi_w && pi_b && vf_w && vf_b && logstd)) { g_err = w + "NULL weight pointer"; return 1; }
+  for (int i = 0; i < 12; i++)
+    if (!lstm_w[i]) { g_err = w + "the LSTM weight table has a NULL entry"; return 1; }
+  if (!(a_cmd > 0.0f && a_cmd <= 1.0f && a_vel > 0.0f && a_vel <= 1.0f && a_act > 0.0f && a_act <= 1.0f)) {
+    g_err = w + "filter coefficients lie in (0, 1] (1 = off)"; return 1;
+  }
+  return 0;
+}
+// the argument block of the evaluation kernels; the work array [N, IRRL_EVAL_WORK_DIM]: obs_cond 35 | action 12 | clipped 12 | applied 12 | value |
+// neglogp | reward | extra 6
+struct EvalWork { float *obs_cond, *action, *clipped, *applied, *value, *neglogp, *reward, *extra; };
+static EvalWork eval_work(float *work, size_t N) {
+  EvalWork w;
+  w.obs_cond = work; w.action = w.obs_cond + N * 35; w.clipped = w.action + N * 12; w.applied = w.clipped + N * 12; w.value = w.applied + N * 12;
+  w.neglogp = w.value + N; w.reward = w.neglogp + N; w.extra = w.reward + N;
+  return w;
+}
+static EvalArgs eval_args(const irrl_env *h, const EvalWork &w, int depth, float *ring, float *cmd, float *vel_his, float *act_his, uint8_t *done, float *obs,
+                          const int *delay, const float *cmd_target, float a_cmd, float a_vel, float a_act, const float *cmd_mean, const float *cmd_std, int clip,
+                          float *rec_obs_cond, float *rec_act_clipped, float *rec_act_applied, float *rec_body, float *rec_torque, float *rec_obs_raw,
+                          float *rec_reward, uint8_t *rec_done, double *stats) {
+  EvalArgs a;
+  a.N = h->P.n_envs; a.D = depth; a.slot = 0; a.steps = 0; a.clip = clip; a.row = 0;
+  a.ring = ring; a.cmd = cmd; a.vel_his = vel_his; a.act_his = act_his; a.obs = obs; a.done = done;
+  a.delay = delay; a.cmd_target = cmd_target;
+  a.a_cmd = a_cmd; a.a_vel = a_vel; a.a_act = a_act;
+  a.mean0 = cmd_mean[0]; a.mean1 = cmd_mean[1]; a.mean2 = cmd_mean[2]; a.std0 = cmd_std[0]; a.std1 = cmd_std[1]; a.std2 = cmd_std[2];
+  a.obs_cond = w.obs_cond; a.act_in = clip ? w.clipped : w.action; a.applied = w.applied; a.reward = w.reward;
+  a.gc = h->S.gc; a.gv = h->S.gv; a.torque = h->S.torque;
+  a.rec_obs_cond = rec_obs_cond; a.rec_act_clipped = rec_act_clipped; a.rec_act_applied = rec_act_applied; a.rec_body = rec_body;
+  a.rec_torque = rec_torque; a.rec_obs_raw = rec_obs_raw; a.rec_reward = rec_reward; a.rec_done = rec_done; a.stats = stats;
+  return a;
+}
 int irrl_lstm_eval_rollout(irrl_env *h, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *lstm_w, const float *pi_w,
                            const float *pi_b, const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring, float *cmd, float *vel_his,
                            float *act_his, float *lstm_state, uint8_t *done, float *obs, float *work, const int *delay, const float *cmd_target, float a_cmd,
                            float a_vel, float a_act, const float *cmd_mean, const float *cmd_std, int clip, float *rec_obs_cond, float *rec_act_clipped,
                            float *rec_act_applied, float *rec_body, float *rec_torque, float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats,
                            void *hip_stream) {
-  if (!h) { g_err = "irrl_lstm_eval_rollout: NULL handle"; return 1; }
-  if (steps < 0 || step0 < 0) { g_err = "irrl_lstm_eval_rollout: steps >= 0, step0 >= 0"; return 1; }
-  if (depth < 1) { g_err = "irrl_lstm_eval_rollout: the delay line needs a depth D >= 1"; return 1; }
-  if (hid != 32 && hid != 48 && hid != 64) { g_err = "irrl_lstm_eval_rollout: hid is 32, 48 or 64"; return 1; }
-  if (ob_dim != 35 || act_dim != 12) { g_err = "irrl_lstm_eval_rollout: ob 35, act 12"; return 1; }
-  if (!(ring && cmd && vel_his && act_his && lstm_state && done && obs && work && delay && cmd_target && cmd_mean && cmd_std)) {
-    g_err = "irrl_lstm_eval_rollout: NULL evaluator state / parameter pointer"; return 1;
-  }
-  if (!(lstm_w && pi_w && pi_b && vf_w && vf_b && logstd)) { g_err = "irrl_lstm_eval_rollout: NULL weight pointer"; return 1; }
-  for (int i = 0; i < 12; i++)
-    if (!lstm_w[i]) { g_err = "irrl_lstm_eval_rollout: the LSTM weight table has a NULL entry"; return 1; }
-  if (!(a_cmd > 0.0f && a_cmd <= 1.0f && a_vel > 0.0f && a_vel <= 1.0f && a_act > 0.0f && a_act <= 1.0f)) {
-    g_err = "irrl_lstm_eval_rollout: filter coefficients lie in (0, 1] (1 = off)"; return 1;
-  }
+  if (eval_rollout_check("irrl_lstm_eval_rollout", h, steps, step0, hid, ob_dim, act_dim, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, depth, ring, cmd, vel_his, act_his,
+                         lstm_state, done, obs, work, delay, cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std)) return 1;
   if (need_init(h)) return 1;
   HIP_TRY(hipSetDevice(h->device));
   h->stream = (hipStream_t)hip_stream;
   const int n = h->P.n_envs;
-  const size_t N = (size_t)n;
-  // the work array [N, IRRL_EVAL_WORK_DIM]: obs_cond 35 | action 12 | clipped 12 | applied 12 | value | neglogp | reward | extra 6
-  float *obs_cond = work, *action = obs_cond + N * 35, *clipped = action + N * 12, *applied = clipped + N * 12, *value = applied + N * 12,
-        *neglogp = value + N, *reward = neglogp + N, *extra = reward + N;
-  EvalArgs a;
-  a.N = n; a.D = depth;
-  a.ring = ring; a.cmd = cmd; a.vel_his = vel_his; a.act_his = act_his; a.obs = obs; a.done = done;
-  a.delay = delay; a.cmd_target = cmd_target;
-  a.a_cmd = a_cmd; a.a_vel = a_vel; a.a_act = a_act;
-  a.mean0 = cmd_mean[0]; a.mean1 = cmd_mean[1]; a.mean2 = cmd_mean[2]; a.std0 = cmd_std[0]; a.std1 = cmd_std[1]; a.std2 = cmd_std[2];
-  a.obs_cond = obs_cond; a.act_in = clip ? clipped : action; a.applied = applied; a.reward = reward;
-  a.gc = h->S.gc; a.gv = h->S.gv; a.torque = h->S.torque;
-  a.rec_obs_cond = rec_obs_cond; a.rec_act_clipped = rec_act_clipped; a.rec_act_applied = rec_act_applied; a.rec_body = rec_body;
-  a.rec_torque = rec_torque; a.rec_obs_raw = rec_obs_raw; a.rec_reward = rec_reward; a.rec_done = rec_done; a.stats = stats;
+  const EvalWork w = eval_work(work, (size_t)n);
+  EvalArgs a = eval_args(h, w, depth, ring, cmd, vel_his, act_his, done, obs, delay, cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std, clip, rec_obs_cond,
+                         rec_act_clipped, rec_act_applied, rec_body, rec_torque, rec_obs_raw, rec_reward, rec_done, stats);
   for (int k = 0; k < steps; k++) {
     a.slot = (int)((step0 + k) % depth);
     a.row = k;
     hipLaunchKernelGGL(irrl_eval_condition_kernel, eval_grid(n * 35), dim3(256), 0, h->stream, a);
-    if (irrl_lstm_policy_step(hid, ob_dim, act_dim, n, obs_cond, done, lstm_state, lstm_state, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, nullptr, 0, 0u, 0, nullptr, 0,
-                              action, clipped, value, neglogp, -1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, hip_stream) != 0) {
+    if (irrl_lstm_policy_step(hid, ob_dim, act_dim, n, w.obs_cond, done, lstm_state, lstm_state, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, nullptr, 0, 0u, 0, nullptr, 0,
+                              w.action, w.clipped, w.value, w.neglogp, -1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, hip_stream) != 0) {
       g_err = "irrl_lstm_eval_rollout: policy step refused its arguments"; return 1;
     }
     hipLaunchKernelGGL(irrl_eval_action_kernel, eval_grid(n * 12), dim3(256), 0, h->stream, a);
-    launch_step(h, h->P, (const float *)applied, obs, reward, done, extra);
+    launch_step(h, h->P, (const float *)w.applied, obs, w.reward, done, w.extra);
     hipLaunchKernelGGL(irrl_eval_record_kernel, eval_grid(n * 35), dim3(256), 0, h->stream, a);
   }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// THE SAME LOOP AS ONE PERSISTENT LAUNCH (csrc/env_eval_kernels.hpp: a wave keeps its four robots for all `steps`): exists where the actor-wave
+// rollout kernel does -- irrl_lstm_rollout_supports(h, hid, 3) -- and is refused elsewhere; there is no fallback inside the call.
+typedef void (*eval_kernel_t)(IRRL_EVAL_KERNEL_ARGS);
+static const eval_kernel_t kEvalKernels[2] = {irrl_eval_persistent_kernel_l16, irrl_eval_persistent_kernel_rt_l16};   // the order of kRolloutKernels
+int irrl_lstm_eval_rollout_supports(irrl_env *h, int hid) {
+  if (!h) { g_err = "irrl_lstm_eval_rollout_supports: NULL handle"; return -1; }
+  return rollout_one_tile(h, hid) ? 1 : 0;
+}
+int irrl_lstm_eval_rollout_persistent(irrl_env *h, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *lstm_w, const float *pi_w,
+                                      const float *pi_b, const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring, float *cmd,
+                                      float *vel_his, float *act_his, float *lstm_state, uint8_t *done, float *obs, float *work, const int *delay,
+                                      const float *cmd_target, float a_cmd, float a_vel, float a_act, const float *cmd_mean, const float *cmd_std, int clip,
+                                      float *rec_obs_cond, float *rec_act_clipped, float *rec_act_applied, float *rec_body, float *rec_torque, float *rec_obs_raw,
+                                      float *rec_reward, uint8_t *rec_done, double *stats, void *hip_stream) {
+  static const char *const who = "irrl_lstm_eval_rollout_persistent";
+  if (eval_rollout_check(who, h, steps, step0, hid, ob_dim, act_dim, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, depth, ring, cmd, vel_his, act_his, lstm_state, done,
+                         obs, work, delay, cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std)) return 1;
+  if (need_init(h)) return 1;
+  // which condition keeps the kernel from this pool / network (settings only: nothing is launched)
+  if (hid != 48) { g_err = std::string(who) + ": the persistent kernel exists for hid 48 only (this policy has hid " + std::to_string(hid) + ")"; return 1; }
+  if (h->lanes != 16) { g_err = std::string(who) + ": the persistent kernel exists in the 16-lane layout only (this pool runs 4 lanes per robot)"; return 1; }
+  const RolloutKernels *rk = rollout_kernel_set(h);
+  if (!rk) {
+    g_err = std::string(who) + ": the persistent kernel exists for the kernel variants shipped_flat / shipped / md only (this pool runs '" +
+            kVariantNames[step_variant(h)] + "': Crutial pools and ContactSolver without the published rule keep irrl_lstm_eval_rollout)";
+    return 1;
+  }
+  if (steps == 0) return 0;
+  HIP_TRY(hipSetDevice(h->device));
+  h->stream = (hipStream_t)hip_stream;
+  const int n = h->P.n_envs;
+  const EvalWork w = eval_work(work, (size_t)n);
+  EvalArgs a = eval_args(h, w, depth, ring, cmd, vel_his, act_his, done, obs, delay, cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std, clip, rec_obs_cond,
+                         rec_act_clipped, rec_act_applied, rec_body, rec_torque, rec_obs_raw, rec_reward, rec_done, stats);
+  a.slot = (int)(step0 % depth);
+  a.steps = steps;
+  // the actor alone, deterministic, no rollout rows: `value` and the critic's half of lstm_state are not written
+  const PolicyStepArgs pa = policy_step_args(n, ob_dim, act_dim, obs, done, lstm_state, lstm_state, lstm_w, 12, pi_w, pi_b, vf_w, vf_b, logstd, nullptr, 0, 0u, 0, nullptr,
+                                             0, w.action, w.clipped, w.value, w.neglogp, -1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  hipLaunchKernelGGL(kEvalKernels[rk == &kRolloutKernels[0] ? 0 : 1], dim3((n + 15) / 16), dim3(256), 0, h->stream, h->P, h->S, obs, w.reward, done, w.extra, pa, a);
   HIP_TRY(hipGetLastError());
   return 0;
 }

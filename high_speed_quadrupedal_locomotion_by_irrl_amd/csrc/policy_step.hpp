@@ -189,7 +189,9 @@ struct MlpWaveLds {
 // left them there next to the stores to memory), and the clipped actions are left there for that env step: inside the step loop nothing a wave
 // reads comes back from memory, so nothing waits for a store to complete
 // LAY: the scratch layout (offsets X, ACT, REW, DON); NO_VALUE: the critic is not part of the step (the actor-only LSTM rollout)
-template <int HID, bool XLDS, class LAY, bool NO_VALUE = false>
+// RAW_ACT: the scratch gets the action BEFORE the [-1, 1] clip (the persistent evaluation kernel, whose caller decides at run time whether the
+// clip applies and repeats it on the scratch value; the rollout kernels instantiate the default and are the code they were)
+template <int HID, bool XLDS, class LAY, bool NO_VALUE = false, bool RAW_ACT = false>
 LSTM_DEV void policy_heads_wave(const PolicyStepArgs &a, float *ws, const float *hpi, const float *hv, int LD, const float *pw, const float *vw, float (*terms)[17],
                                 int e4, int l, long long t, long long gstep) {
   // lane (env, action) for the mean / sample, four more lanes for the value and the neglogp sum (policy_heads with 4 envs instead of 16)
@@ -220,7 +222,7 @@ LSTM_DEV void policy_heads_wave(const PolicyStepArgs &a, float *ws, const float 
     const float cl = fminf(fmaxf(act, -1.0f), 1.0f);
     a.action[o] = act;
     a.clipped[o] = cl;
-    if (XLDS) ws[LAY::ACT + env * A + ai] = cl;
+    if (XLDS) ws[LAY::ACT + env * A + ai] = RAW_ACT ? act : cl;
     if (a.mb_actions) a.mb_actions[(size_t)t * a.N * A + o] = act;
   }
   float val = 0.0f;
@@ -700,7 +702,8 @@ LSTM_DEV void lstm_wave_image_stage(const PolicyStepArgs &a, float *wt) {
 }
 
 // cst: c of layer 0 / layer 1 for (robot l & 3, unit 16 G + (l >> 2)), G = 0 .. HID / 16 - 1; bias: the lane's gate columns 64 G + l of both layers
-template <int HID>
+// RAW_ACT: policy_heads_wave's switch (the unclipped action in the scratch)
+template <int HID, bool RAW_ACT = false>
 LSTM_DEV void lstm_actor_wave_body(const PolicyStepArgs &a, const int e4, float *ws, const float *wt, const float *head_w, const int l,
                                    float (&cst)[2][HID / 16], const float (&bias)[2][HID / 16]) {
   typedef LstmWaveLds<HID> LAY;
@@ -801,5 +804,5 @@ LSTM_DEV void lstm_actor_wave_body(const PolicyStepArgs &a, const int e4, float 
   PS_WAVE_SYNC();
   cell(cst[1], h1);
   PS_WAVE_SYNC();
-  policy_heads_wave<HID, true, LAY, true>(a, ws, h1, h1, HID, head_w, head_w, terms, e4, l, t, gstep);
+  policy_heads_wave<HID, true, LAY, true, RAW_ACT>(a, ws, h1, h1, HID, head_w, head_w, terms, e4, l, t, gstep);
 }

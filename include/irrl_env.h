@@ -394,7 +394,8 @@ int irrl_mlp_rollout_supports(irrl_env *env, int hid, int fuse);
  * low-passes, command ramp).  `steps` control steps of the closed loop  conditioning -> CustomLSTMPolicy (deterministic) -> action filter ->
  * env.step -> record  issued by ONE call as plain launches back to back on `hip_stream` (five per step; kernels csrc/eval_rollout.hpp, the policy
  * step and the env step are the existing ones, so every pool kind and kernel variant works).  Nothing is captured, nothing synchronises, and the
- * call keeps no state: a second call with step0 + steps continues exactly where the first stopped.  A persistent single-launch form is out of scope.
+ * call keeps no state: a second call with step0 + steps continues exactly where the first stopped.  The persistent single-launch form of the same
+ * loop is irrl_lstm_eval_rollout_persistent below.
  *
  * Control step t = step0 + k, per env e:
  *    1. cmd = (1 - a_cmd) cmd + a_cmd cmd_target            2. ring[t % D] = obs              3. o = ring[(t - delay_e) mod D]
@@ -440,6 +441,26 @@ int irrl_lstm_eval_rollout(irrl_env *env, int steps, long long step0, int hid, i
                            float a_vel, float a_act, const float *cmd_mean, const float *cmd_std, int clip, float *rec_obs_cond, float *rec_act_clipped,
                            float *rec_act_applied, float *rec_body, float *rec_torque, float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats,
                            void *hip_stream);
+
+/* THE SAME LOOP AS ONE PERSISTENT LAUNCH (kernel csrc/env_eval_kernels.hpp): a wave keeps its four robots -- lane context and LSTM cell state in
+ * registers, h, the filter histories, the command and the statistics in LDS -- for all `steps` control steps; no grid-wide boundary between steps.
+ * Same argument list, same order, same per-element arithmetic (csrc/eval_elements.hpp): every recorder, stats, ring, cmd, vel_his, act_his, done, obs,
+ * the pool, the ACTOR's half of lstm_state ([:, 0 : 4 hid]) and the work columns obs_cond | action | clipped | applied | reward | extra are
+ * BIT-IDENTICAL to irrl_lstm_eval_rollout's.  The critic is not run: the critic's half of lstm_state ([:, 4 hid : 8 hid]) and the `value` column of
+ * the work array are left untouched.  The actor never reads them, so calls of either form may follow each other on the same buffers.
+ * irrl_lstm_eval_rollout_supports: 1 = the kernel exists for this pool and a network of `hid` units -- exactly where
+ * irrl_lstm_rollout_supports(env, hid, 3) is 1: 16 lanes per robot, hid 48, kernel variant shipped_flat / shipped / md --, 0 = it does not,
+ * -1 = NULL handle (irrl_last_error() set).
+ * irrl_lstm_eval_rollout_persistent makes the refusals of irrl_lstm_eval_rollout before any HIP call, with its own name in the texts, and refuses
+ * a pool or `hid` without the kernel with a text that names the failed condition: there is NO fallback inside the call.  steps == 0 returns 0 and
+ * launches nothing. */
+int irrl_lstm_eval_rollout_supports(irrl_env *env, int hid);
+int irrl_lstm_eval_rollout_persistent(irrl_env *env, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *lstm_w,
+                                      const float *pi_w, const float *pi_b, const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring,
+                                      float *cmd, float *vel_his, float *act_his, float *lstm_state, uint8_t *done, float *obs, float *work, const int *delay,
+                                      const float *cmd_target, float a_cmd, float a_vel, float a_act, const float *cmd_mean, const float *cmd_std, int clip,
+                                      float *rec_obs_cond, float *rec_act_clipped, float *rec_act_applied, float *rec_body, float *rec_torque,
+                                      float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats, void *hip_stream);
 
 #ifdef __cplusplus
 }

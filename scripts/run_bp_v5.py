@@ -66,6 +66,9 @@ def parse_args(argv):
     p.add_argument("--sweep_mu", type=floats, default=[0.05, 0.4, 0.8], help="friction coefficients, comma separated")
     p.add_argument("--sweep_delay", type=lambda s: [int(v) for v in str(s).split(",") if v != ""], default=[0, 1, 2, 3, 4, 5], help="observation delays [control steps]")
     p.add_argument("--sweep_cmd", type=floats, default=[1.0, 2.0, 3.0, 4.0, 5.0], help="forward-velocity commands [m/s]")
+    p.add_argument("--persistent", choices=["auto", "on", "off"], default=None,
+                   help="--sweep: the whole run as one persistent launch (on; refused where the kernel does not exist), where it exists (auto), or five "
+                        "launches per control step (off); same table bit for bit.  Default: evaluate.PERSISTENT_DEFAULT")
     p.add_argument("--warm", type=int, default=1000, help="--sweep: control steps on friction 0.8 before the condition's own friction is installed")
     return p.parse_args(argv)
 
@@ -136,12 +139,13 @@ def run_sweep(args, cfg):
     (evaluate.PolicyEvaluator), `--warm` steps on the script's default material, then `--steps` on the condition's own over which the
     statistics are taken.  Prints the table, writes it to --out as JSON."""
     import json
-    from high_speed_quadrupedal_locomotion_by_irrl_amd.evaluate import robustness_sweep, sweep_table
+    from high_speed_quadrupedal_locomotion_by_irrl_amd.evaluate import PERSISTENT_DEFAULT, robustness_sweep, sweep_table
     if args.trained_model is None:
         raise SystemExit("model path can't be ignored during test mode (--model)")
     none_if_off = lambda f: None if f >= 1.0e6 else f
     rows = robustness_sweep(args.trained_model, cfg["environment"], args.sweep_mu, args.sweep_delay, args.sweep_cmd, warm_steps=args.warm, steps=args.steps,
-                            cmd_hz=args.cmd_filter_freq, vel_hz=none_if_off(args.vel_filter_freq), act_hz=none_if_off(args.act_filter_freq))
+                            cmd_hz=args.cmd_filter_freq, vel_hz=none_if_off(args.vel_filter_freq), act_hz=none_if_off(args.act_filter_freq),
+                            persistent=PERSISTENT_DEFAULT if args.persistent is None else args.persistent)
     print(sweep_table(rows))
     if args.out:
         with open(args.out, "w") as f:

@@ -4,6 +4,11 @@ on HipVecEnv: numpy boundary, float64 numpy actor, get_state and every record on
 clock around work that ends in a device synchronise.
 
     python tools/eval_rate.py [--envs 4096] [--steps 2000] [--host-steps 200]
+
+--ab: the persistent single-launch form (PolicyEvaluator.run(persistent=True), kernel csrc/env_eval_kernels.hpp) against the five-launch form, same
+process, same pool, interleaved A, B, A, B (A = five launches per step), statistics only and all recorders; the host-driven leg is skipped.
+
+    python tools/eval_rate.py --ab [--envs 4096 | --envs 90] [--steps 2000]
 """
 import argparse
 import json
@@ -23,11 +28,37 @@ from high_speed_quadrupedal_locomotion_by_irrl_amd import evaluate as EV  # noqa
 from high_speed_quadrupedal_locomotion_by_irrl_amd.flexible_robot import FlexibleGymEnv  # noqa: E402
 
 
+def ab(args, env, pol, delays, cmds, out):
+    """A, B, A, B on one pool: every leg is a fresh evaluator (reset), a 50-step warm-up of its own form, then `steps` steps timed around a
+    device synchronise.  The two forms compute the same trajectory bit for bit, so the legs do the same work."""
+    n = args.envs
+    cases = [("statistics only", (), True), ("all recorders", tuple(EV.RECORDERS), True)] + ([("no statistics", (), False)] if args.no_statistics else [])
+    for name, record, acc in cases:
+        legs = {False: [], True: []}
+        for persistent in (False, True, False, True):
+            ev = EV.PolicyEvaluator(env, pol, delays, cmds, cmd_hz=1.0, vel_hz=50.0, act_hz=30.0)
+            ev.run(50, record=record, accumulate=acc, persistent=persistent)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ev.run(args.steps, record=record, accumulate=acc, persistent=persistent)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            legs[persistent].append(1e6 * dt / args.steps)
+            print("%-15s %-12s: %d envs x %d steps in %.3f s = %.1f us per step, falls %d"
+                  % (name, "persistent" if persistent else "five-launch", n, args.steps, dt, 1e6 * dt / args.steps, int(ev.statistics()["falls"].sum())))
+        a, b = min(legs[False]), min(legs[True])
+        out[name] = {"steps": args.steps, "five_launch_us_per_step": legs[False], "persistent_us_per_step": legs[True], "persistent_over_five_launch": b / a}
+        print("%-15s: five-launch %.1f us, persistent %.1f us per step (best of two each), ratio %.3f" % (name, a, b, b / a))
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--host-steps", type=int, default=200)
+    ap.add_argument("--no-statistics", action="store_true", help="--ab: one more pair of legs with neither recorders nor statistics (accumulate=False)")
+    ap.add_argument("--ab", action="store_true", help="five launches per step (A) against the persistent launch (B), interleaved A, B, A, B")
     args = ap.parse_args()
     n = args.envs
     cfg = yaml.safe_load(open(os.path.join(pkg.__BLACKPANTHER_V55_RESOURCE_DIRECTORY__, "bp5_manual_eval.yaml")))["environment"]
@@ -38,6 +69,8 @@ def main():
     env.init()
     env.SetContactCoefficient(EV.contact_material(mus))
     out = {"envs": n}
+    if args.ab:
+        return ab(args, env, pol, delays, cmds, out)
     for name, record in (("statistics only", ()), ("all recorders", tuple(EV.RECORDERS))):
         ev = EV.PolicyEvaluator(env, pol, delays, cmds, cmd_hz=1.0, vel_hz=50.0, act_hz=30.0)
         ev.run(50, record=record)                                  # code objects loaded, buffers touched
