@@ -632,17 +632,52 @@ IRRL_DEV v3 solve_contact(const ContactBlock &B, v3 c, v3 n, vf vstar, vf mu, vm
 // gamma >= 0 from (xi - xi_c)^T P (xi - xi_c) = 1, i.e. p(gamma) / sqrt(r(gamma)) = sigma with p = det(A + gamma P), r a quadratic,
 // sigma = |xi* - xi_c| -- concave and increasing, so Newton is monotone after its first step from any start; the start is the root
 // of the isotropic problem along the far point's direction d, gamma_0 = a (sigma sqrt(rho) - 1) / rho (a = d^T A d, rho = d^T P d),
-// and IRRL_MD_NEWTON = 2 steps from there are converged to 2e-9 (f64) on the robot's own sliding problems.
-// Caps (not reached on the shipped configurations, mu |beta| <= 0.86 there): eccentricity above sqrt(1 - SMIN) (the conic turns
-// into a parabola / hyperbola at the jamming corner) -> beta shortened in the cone section; sigma > SIGMAX (a barely pressing
-// contact sliding fast, impulse ~1e-4 of a pressing one) -> far point pulled in; mu < MUMIN -> frictionless, lam = alpha n.
+// and IRRL_MD_NEWTON = 2 steps from there are converged to 2e-9 (f64) on the robot's own sliding problems.  An eccentric section
+// needs more: two steps leave 2e-6 of the impulse at mu |beta| = 0.86, 5e-4 at 0.92, 4 % at 0.97 and 20 % at the cap's onset
+// (|lam_t| up to 1.28 mu lam_n); six steps are converged to 4e-9 up to the cap.  A wave in which some lane has
+// mu^2 |beta|^2 > IRRL_MD_ECC (mu |beta| > 0.922: below it two steps keep the 5e-4 of the f32 solve) therefore takes
+// IRRL_MD_NEWTON_ECC = 4 steps more (ContactBlockMD::rare: one wave-uniform flag for this and for SCALE.  The rare
+// work sits in three small wave-uniform blocks of solve_contact_md: the shipped kernels unroll their sweeps, and the env step's
+// time follows the kernel's length even where the added code never runs -- a second whole copy of the slipping solve behind each
+// sweep made irrl_steps_persistent_kernel_flat_l16 22 % longer and the step 2 % slower, one called function 5 % slower.  As it
+// stands the kernel is 12 % longer and the step costs 1.7 % more than before, 28.73 against 28.26 us at 4096 envs on the MI355X.)
+// Caps (rare on the shipped configurations -- mu |beta| <= 0.86 for 99 % of their contacts; reached at will through
+// SetContactCoefficient and the friction sweep of the device evaluation, and EXERCISED by the friction_caps / fast_slide scenarios of tests/parity_lib.py -- host emulation
+// and MI355X, mixed with ordinary robots inside one wave -- and one by one in tests/test_contact_model_gap.py): eccentricity above
+// sqrt(1 - SMIN) (the conic turns into a parabola / hyperbola at the jamming corner) -> beta shortened in the cone section, and
+// the point found on the shortened section pulled back along its ray onto the TRUE cone where it lies outside (away from the
+// corner the shortened section is the wider one: |lam_t| reached 2 mu lam_n) -- the normal condition stays exact either way;
+// sigma > SIGMAX (a barely pressing contact sliding fast, impulse ~1e-4 of a pressing one) -> far point pulled in;
+// mu <= MUMIN -> frictionless, lam = alpha n.
+// SCALE.  P grows as 1 / mu^2 and the Newton step multiplies r^1.5 ~ (a^2 sigma / mu^2)^3 (a: size of A): in f32 that product
+// overflowed for mu below ~1e-3 (NaN impulses from the first sliding touchdown at mu = 1e-5).  In a wave where some lane has
+// mu < MUSCALE = 2^-5 the block therefore holds kappa^2 P and the solve works with gamma / kappa^2 and sigma / kappa,
+// kappa = 2^floor(log2 mu) (md_kappa): every intermediate is O(a^k (sigma / kappa)^k) however small mu is, and since kappa is a power of two
+// the scaling is EXACT -- the other lanes of such a wave, and every lane wherever the unscaled form stayed finite, get bit for bit
+// the unscaled results.  sigma / kappa (the far point's distance in units of the ellipse's size) has its own cap
+// SIGREL = SIGMAX / MUSCALE, which is beyond SIGMAX for mu >= MUSCALE and bounds r^1.5 sigma / kappa by ~1e26 a^6 below it.
 // Everything that depends only on (G, n, mu) is per-substep (ContactBlockMD); the CPU restatement the parity tests compare with
 // runs the same steps with the same constants.
 // ---------------------------------------------------------------------------------------------
 #define IRRL_MD_NEWTON 2
+#define IRRL_MD_NEWTON_ECC 4
+#define IRRL_MD_ECC 0.85f
 #define IRRL_MD_SMIN 0.04f
 #define IRRL_MD_SIGMAX 1.0e4f
+#define IRRL_MD_MUSCALE 0.03125f
+#define IRRL_MD_SIGREL (IRRL_MD_SIGMAX / IRRL_MD_MUSCALE)
 #define IRRL_MD_MUMIN 1.0e-6f
+// kappa of SCALE: 2^floor(log2 mu) for MUMIN <= mu < MUSCALE = 2^-5, 1 from there on (any power of two scales
+// exactly; from MUSCALE on SIGREL cannot bind).  Four halvings of the exponent's range with compare, select and exact products:
+// it runs once per block in `rare` waves only (ContactBlockMD::kap; 1 elsewhere) and needs nothing of the lane layer beyond that.
+IRRL_DEV vf md_kappa(vf mu) {
+  vf t = mu, kap = vsel(mu < IRRL_MD_MUSCALE, 0.015625f, 1.0f);  // t 2^shift ends in [2^-6, 2^-5)
+  vm b = t < 1.220703125e-4f;   /* 2^-13 */ t = vsel(b, t * 256.0f, t); kap = vsel(b, kap * 0.00390625f, kap);
+  b = t < 0.001953125f;         /* 2^-9  */ t = vsel(b, t * 16.0f, t);  kap = vsel(b, kap * 0.0625f, kap);
+  b = t < 0.0078125f;           /* 2^-7  */ t = vsel(b, t * 4.0f, t);   kap = vsel(b, kap * 0.25f, kap);
+  b = t < 0.015625f;            /* 2^-6  */                              kap = vsel(b, kap * 0.5f, kap);
+  return kap;
+}
 // The tangential plane's algebra is written on PAIRS (vf2: one v_pk_*_f32 per pair operation on the GPU): column pairs of the 2x2
 // matrices, so that M v = M_col1 v.x + M_col2 v.y is two packed instructions with the halves of v broadcast by op_sel.
 struct ContactBlockMD {
@@ -650,8 +685,9 @@ struct ContactBlockMD {
   vf2 g, be, zc;           // G_tn, beta = -G_tn / G_nn, centre of the cone section's ellipse
   vf2 AC1, AC2;            // columns of A = G_tt - G_tn G_tn^T / G_nn (symmetric)
   vf2 NI1, NI2;            // columns of -A^-1
-  vf2 PC1, PC2, QC1, QC2;  // columns of P and of adj(P)
-  vf mu2, ignn, detA, idetA2, detP, detP2, mix;
+  vf2 PC1, PC2, QC1, QC2;  // columns of P and of adj(P) (of kappa^2 P in a `rare` wave: SCALE, above)
+  vf mu2, ignn, detA, idetA2, detP, detP2, mix, kap;
+  bool rare;               // some lane of the wave has an eccentric cone section (mu^2 |beta|^2 > IRRL_MD_ECC) or mu < IRRL_MD_MUSCALE
 };
 IRRL_DEV ContactBlockMD make_contact_block_md(sym3 G, v3 n, vf mu_in) {
   ContactBlockMD B;
@@ -681,12 +717,17 @@ IRRL_DEV ContactBlockMD make_contact_block_md(sym3 G, v3 n, vf mu_in) {
   B.NI1 = (-idetA) * pk2(A22, -A12);
   B.NI2 = (-idetA) * pk2(-A12, A11);
   const vf mb2 = B.mu2 * pk_hsum(B.be * B.be);
-  vf shrink = mu;
-  if (IRRL_UNLIKELY(wave_any(mb2 > 1.0f - IRRL_MD_SMIN)))      // the jamming corner: not reached on the shipped configurations
+  vf shrink = mu, imu2 = v_rcp(B.mu2);
+  B.kap = 1.0f;
+  B.rare = wave_any((mb2 > IRRL_MD_ECC) | (mu < IRRL_MD_MUSCALE));
+  if (IRRL_UNLIKELY(B.rare)) {                                   // towards the jamming corner, or friction so small that P needs its scale
     shrink = vsel(mb2 <= 1.0f - IRRL_MD_SMIN, mu, mu * v_sqrt((1.0f - IRRL_MD_SMIN) * v_rcp(v_max(mb2, 1e-30f))));
+    B.kap = md_kappa(mu);
+    imu2 = imu2 * (B.kap * B.kap);
+  }
   const vf2 e = shrink * B.be;                                   // mu beta (capped)
   const vf e1 = pk_lo(e), e2 = pk_hi(e);
-  const vf s = 1.0f - pk_hsum(e * e), is = v_rcp(s), ims = s * v_rcp(B.mu2);
+  const vf s = 1.0f - pk_hsum(e * e), is = v_rcp(s), ims = s * imu2;
   const vf P11 = (1.0f - e1 * e1) * ims, P12 = -e1 * e2 * ims, P22 = (1.0f - e2 * e2) * ims;
   B.PC1 = pk2(P11, P12); B.PC2 = pk2(P12, P22);
   B.QC1 = pk2(P22, -P12); B.QC2 = pk2(-P12, P11);
@@ -714,7 +755,11 @@ IRRL_DEV v3 solve_contact_md(const ContactBlockMD &B, v3 c, v3 n, vf vstar, vf m
     vf2 d = ia * x - B.zc;
     const vf s2 = pk_hsum(d * d);
     const vf isg = v_rsqrt(v_max(s2, 1e-30f));
-    const vf sig = v_min(s2 * isg, IRRL_MD_SIGMAX);
+    vf sig = v_min(s2 * isg, IRRL_MD_SIGMAX), sgs = sig;
+    if (IRRL_UNLIKELY(B.rare)) {                                   // sgs = sigma / kappa, capped on its own (SCALE, above)
+      sgs = v_min(sig * v_rcp(B.kap), IRRL_MD_SIGREL);
+      sig = sgs * B.kap;
+    }
     d = isg * d;
     const vf2 w = pk_lo(d) * B.AC1 + pk_hi(d) * B.AC2;            // A d
     const vf2 u = B.detA * d;                                      // adj(A) A d
@@ -722,15 +767,26 @@ IRRL_DEV v3 solve_contact_md(const ContactBlockMD &B, v3 c, v3 n, vf vstar, vf m
     const vf2 Pu = pk_lo(u) * B.PC1 + pk_hi(u) * B.PC2, Pq = pk_lo(q) * B.PC1 + pk_hi(q) * B.PC2;
     const vf c0 = pk_hsum(u * Pu), c1 = 2.0f * pk_hsum(q * Pu), c2 = pk_hsum(q * Pq), c22 = 2.0f * c2;
     const vf rho = c0 * B.idetA2;
-    vf gam = v_max(pk_hsum(w * d) * (sig * v_sqrt(rho) - 1.0f) * v_rcp(rho), 0.0f);
+    vf gam = v_max(pk_hsum(w * d) * (sgs * v_sqrt(rho) - 1.0f) * v_rcp(rho), 0.0f);         // (gamma / kappa^2 where scaled)
+    const auto newton = [&](vf g) {
+      const vf p = (B.detP * g + B.mix) * g + B.detA, r = (c2 * g + c1) * g + c0;
+      const vf dp = B.detP2 * g + B.mix, dr = c22 * g + c1;
+      return g + r * (sgs * v_sqrt(r) - p) * v_rcp(dp * r - 0.5f * p * dr);
+    };
 #pragma unroll
-    for (int it = 0; it < IRRL_MD_NEWTON; it++) {
-      const vf p = (B.detP * gam + B.mix) * gam + B.detA, r = (c2 * gam + c1) * gam + c0;
-      const vf dp = B.detP2 * gam + B.mix, dr = c22 * gam + c1;
-      gam += r * (sig * v_sqrt(r) - p) * v_rcp(dp * r - 0.5f * p * dr);
+    for (int it = 0; it < IRRL_MD_NEWTON; it++) gam = newton(gam);
+    if (IRRL_UNLIKELY(B.rare)) {
+#pragma nounroll
+      for (int it = 0; it < IRRL_MD_NEWTON_ECC; it++) gam = newton(gam);
     }
     const vf kk = sig * v_rcp((B.detP * gam + B.mix) * gam + B.detA);
-    const vf2 Xs = alpha * (kk * (u + gam * q) + B.zc);
+    vf2 Xs = alpha * (kk * (u + gam * q) + B.zc);
+    if (IRRL_UNLIKELY(B.rare)) {                                   // beyond the jamming cap: back onto the true cone, t |Xs| <= mu (alpha + t beta . Xs)
+      const vf mu = v_max(mu_in, IRRL_MD_MUMIN), ma = mu * alpha;
+      const vf den = v_sqrt(pk_hsum(Xs * Xs)) - mu * pk_hsum(B.be * Xs);
+      const vm out = (B.mu2 * pk_hsum(B.be * B.be) > 1.0f - IRRL_MD_SMIN) & (den > ma);
+      Xs = pk_sel(out, (ma * v_rcp(v_max(den, 1e-30f))) * Xs, Xs);
+    }
     X = pk_sel(!sticking & !frictionless, Xs, X);
   }
   const vf lnn = vsel(sep, 0.0f, alpha + pk_hsum(B.be * X));   // normal velocity condition exact

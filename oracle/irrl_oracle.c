@@ -579,15 +579,23 @@ static void solve_contact_dir(const real *G, const real *c, const real *n, real 
  *   p = det(A + gamma P), r = quadratic in gamma, sigma = |xi* - xi_c|).  Start: the root of the isotropic problem along the
  *   direction d of the far point, gamma_0 = a (sigma sqrt(rho) - 1) / rho with a = d^T A d, rho = d^T P d; MD_NEWTON = 2 steps
  *   from there reach 2e-9 of the converged point on 1100 captured sliding problems (from gamma = 0 it takes 4).
- * Caps (never active on the shipped configurations, where mu |beta| <= 0.86 over 1.2e5 captured contact problems):
+ * Caps (rare on the shipped configurations: mu |beta| <= 0.86 for 99 % of their contacts, single ones reach 1.03 under random actions):
  *   mu |beta| > sqrt(1 - MD_SMIN): the conic is a parabola / hyperbola (jamming corner); beta is shortened in the cone section to
- *   the ellipse of eccentricity sqrt(1 - MD_SMIN);  sigma > MD_SIGMAX (a barely pressing contact sliding fast: alpha -> 0, the
- *   impulse is ~1e-4 of a pressing one): the far point is pulled in to MD_SIGMAX;  mu < MD_MUMIN: frictionless, lam = alpha n.
+ *   the ellipse of eccentricity sqrt(1 - MD_SMIN), and the point found there is pulled back onto the true cone where it lies outside;
+ *   sigma > MD_SIGMAX (a barely pressing contact sliding fast: alpha -> 0, the
+ *   impulse is ~1e-4 of a pressing one): the far point is pulled in to MD_SIGMAX;  mu <= MD_MUMIN: frictionless, lam = alpha n.
+ * Scale: P grows as 1 / mu^2, and the Newton step's r^1.5 overflowed the f32 build (and the kernels) for mu below ~1e-3.  P is held
+ *   as kappa^2 P, gamma as gamma / kappa^2, and sigma enters the root as sigma / kappa, kappa = 2^floor(log2 mu): an exact scaling (the
+ *   results are bit for bit those of the unscaled form wherever that stayed finite); sigma / kappa is capped at MD_SIGREL = 32 MD_SIGMAX,
+ *   which is beyond MD_SIGMAX for mu >= 2^-5.
  * The HIP kernels run this same algorithm (csrc/env_core.hpp solve_contact_md), step for step. */
 #define MD_NEWTON 2
+#define MD_NEWTON_ECC 4   /* further steps where mu^2 |beta|^2 > MD_ECC: two steps leave 5e-4 of the impulse at mu |beta| = 0.92, 4 % at 0.97, 20 % at the cap */
+#define MD_ECC 0.85
 #define MD_SMIN 0.04
 #define MD_SIGMAX 1.0e4
 #define MD_MUMIN 1.0e-6
+#define MD_SIGREL (32.0 * MD_SIGMAX)   /* == SIGMAX / 2^-5: the kernels scale only waves with some mu < 2^-5, which is the same thing */
 static void solve_contact_md(const real *G, const real *c, const real *n, real vstar, real mu_in, real *lam) {
   const real cn = v3_dot(c, n) - vstar;
   if (cn >= RC(0)) { v3_set(lam, RC(0), RC(0), RC(0)); return; }
@@ -617,7 +625,10 @@ static void solve_contact_md(const real *G, const real *c, const real *n, real v
   const real mb2 = mu * mu * (be1 * be1 + be2 * be2);
   const real shrink = mb2 <= RC(1.0 - MD_SMIN) ? RC(1) : R_SQRT(RC(1.0 - MD_SMIN) / mb2);
   const real e1 = shrink * mu * be1, e2 = shrink * mu * be2;       /* mu beta (capped) */
-  const real s = RC(1) - (e1 * e1 + e2 * e2), is = RC(1) / s, ims = s / (mu * mu);
+  int mu_exp;
+  (void)frexp(R_TO_DOUBLE(mu), &mu_exp);
+  const real kap = RC(ldexp(1.0, mu_exp - 1)), ikap = RC(ldexp(1.0, 1 - mu_exp));
+  const real s = RC(1) - (e1 * e1 + e2 * e2), is = RC(1) / s, ims = (s / (mu * mu)) * (kap * kap);
   const real P11 = (RC(1) - e1 * e1) * ims, P12 = -e1 * e2 * ims, P22 = (RC(1) - e2 * e2) * ims;
   const real detP = P11 * P22 - P12 * P12, mix = A22 * P11 - RC(2) * A12 * P12 + A11 * P22;
   const real zc1 = mu * e1 * is, zc2 = mu * e2 * is;
@@ -626,7 +637,9 @@ static void solve_contact_md(const real *G, const real *c, const real *n, real v
   real d1 = x1 * ia - zc1, d2 = x2 * ia - zc2;
   const real s2 = d1 * d1 + d2 * d2;
   const real isg = RC(1) / R_SQRT(s2 > RC(1e-30) ? s2 : RC(1e-30));
-  const real sig = s2 * isg < RC(MD_SIGMAX) ? s2 * isg : RC(MD_SIGMAX);
+  const real sig0 = s2 * isg < RC(MD_SIGMAX) ? s2 * isg : RC(MD_SIGMAX);
+  const real sgs = sig0 * ikap < RC(MD_SIGREL) ? sig0 * ikap : RC(MD_SIGREL);     /* sigma / kappa */
+  const real sig = sgs * kap;
   d1 *= isg; d2 *= isg;
   /* (A + gamma P)^-1 A d = (u + gamma q) / p(gamma):  u = adj(A) A d = detA d,  q = adj(P) A d */
   const real w1 = A11 * d1 + A12 * d2, w2 = A12 * d1 + A22 * d2;
@@ -634,15 +647,21 @@ static void solve_contact_md(const real *G, const real *c, const real *n, real v
   const real q1 = P22 * w1 - P12 * w2, q2 = P11 * w2 - P12 * w1;
   const real Pu1 = P11 * u1 + P12 * u2, Pu2 = P12 * u1 + P22 * u2, Pq1 = P11 * q1 + P12 * q2, Pq2 = P12 * q1 + P22 * q2;
   const real c0 = u1 * Pu1 + u2 * Pu2, c1 = RC(2) * (q1 * Pu1 + q2 * Pu2), c2 = q1 * Pq1 + q2 * Pq2;
-  const real rho = c0 * idetA * idetA, g0 = (w1 * d1 + w2 * d2) * (sig * R_SQRT(rho) - RC(1)) / rho;
+  const real rho = c0 * idetA * idetA, g0 = (w1 * d1 + w2 * d2) * (sgs * R_SQRT(rho) - RC(1)) / rho;
   real gam = g0 > RC(0) ? g0 : RC(0);
-  for (int it = 0; it < MD_NEWTON; it++) {
+  for (int it = 0; it < MD_NEWTON + (mb2 > RC(MD_ECC) ? MD_NEWTON_ECC : 0); it++) {
     const real p = (detP * gam + mix) * gam + detA, r = (c2 * gam + c1) * gam + c0;
     const real dp = RC(2) * detP * gam + mix, dr = RC(2) * c2 * gam + c1;
-    gam += r * (sig * R_SQRT(r) - p) / (dp * r - RC(0.5) * p * dr);
+    gam += r * (sgs * R_SQRT(r) - p) / (dp * r - RC(0.5) * p * dr);
   }
   const real kk = sig / ((detP * gam + mix) * gam + detA);
-  const real X1 = alpha * ((u1 + gam * q1) * kk + zc1), X2 = alpha * ((u2 + gam * q2) * kk + zc2);
+  real X1 = alpha * ((u1 + gam * q1) * kk + zc1), X2 = alpha * ((u2 + gam * q2) * kk + zc2);
+  if (mb2 > RC(1.0 - MD_SMIN)) {
+    /* away from the corner the shortened section is wider than the true cone (|lam_t| reached 2 mu lam_n): pull the point back along
+     * its ray, t |X| <= mu (alpha + t beta . X); the normal condition below stays exact, and t = 1 at the cap's onset (continuous) */
+    const real den = R_SQRT(X1 * X1 + X2 * X2) - mu * (be1 * X1 + be2 * X2);
+    if (den > mu * alpha) { const real t = mu * alpha / den; X1 *= t; X2 *= t; }
+  }
   const real lnn = alpha + be1 * X1 + be2 * X2;                      /* normal velocity condition exact */
   for (int i = 0; i < 3; i++) lam[i] = X1 * t1[i] + X2 * t2[i] + lnn * n[i];
 }

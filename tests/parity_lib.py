@@ -410,6 +410,334 @@ class other_terminations(object):
         assert self.seen.min() >= 4 and (self.done_both[[0, 2]] == self.seen[[0, 2]]).all() and (self.done_both[[1, 3]] == 0).all()
 
 
+# ---- contact regimes: the caps of the published per-contact rule, fast slides, bouncing landings ----
+# SetContactCoefficient installs any (mu, restitution, threshold) per env and the material is part of the flat state, so these hooks
+# write S["MATERIAL"] (in EVERY step: a pool with RandomizePerEpisode re-draws it at a reset).  Their witnesses read the ORACLE's own
+# contact problems: the probe of oracle/irrl_oracle.c captures one env's last substep per step, so _contact_witness keeps two pools of
+# ONE env over the same configuration and runs every env of the handed state through them --
+#   last(st, a):  a whole control step with the env's real action -> the problem (G, c_free, n, v*, lam) of the step's LAST substep, the
+#                 very one the oracle under test solves there (contact physics has no cross-env term; `same_as` asserts the identity);
+#   first(st, a): one substep (control_dt = simulation_dt) -> the problem of the step's FIRST substep: the position target is
+#                 filter(action + nominal pose), the same whatever control_dt is, so with the real action this too is the problem the
+#                 oracle under test solves; without one (zero action) the contact set, G, n and v* are still exact (functions of gc
+#                 and of J u before any torque acts).
+# The action of the coming step is the next draw of check_teacher_forced's own stream; the hooks read it from a copy of the stream's
+# state and draw nothing from it.
+MD_SMIN, MD_SIGMAX, MD_MUMIN = 0.04, 1.0e4, 1.0e-6          # oracle/irrl_oracle.c == csrc/env_core.hpp IRRL_MD_*
+
+
+def upcoming_actions(rng, n, scale):
+    peek = np.random.RandomState()
+    peek.set_state(rng.get_state())
+    return random_actions(peek, n, scale)
+
+
+def md_scalars(G, c, n, vstar, mu):
+    """numpy restatement (f64, own tangent basis) of the scalars the published rule decides by, for ONE contact with velocity c before
+    its own impulse: beta = -G_tn / G_nn, mb2 = mu^2 |beta|^2 (jamming cap above 1 - MD_SMIN), alpha, the sticking impulse x*,
+    whether it is admissible, and sigma = |x* / alpha - xi_c| (pull-in above MD_SIGMAX).  |beta| and sigma do not depend on the basis."""
+    n = np.asarray(n, float)
+    t1 = np.cross(n, [1.0, 0.0, 0.0] if abs(n[0]) < 0.9 else [0.0, 1.0, 0.0])
+    t1 /= np.linalg.norm(t1)
+    T = np.stack([t1, np.cross(n, t1)])
+    mu_c = max(float(mu), MD_MUMIN)
+    Gnn, g = n @ G @ n, T @ G @ n
+    beta = -g / Gnn
+    A = T @ G @ T.T - np.outer(g, g) / Gnn
+    cn = c @ n - vstar
+    alpha = -cn / Gnn
+    x = -np.linalg.solve(A, T @ c + alpha * g)
+    ln = alpha + beta @ x
+    mb2 = mu_c * mu_c * (beta @ beta)
+    e = mu_c * beta * (1.0 if mb2 <= 1.0 - MD_SMIN else np.sqrt((1.0 - MD_SMIN) / mb2))
+    zc = mu_c * e / (1.0 - e @ e)
+    sigma = np.linalg.norm(x / alpha - zc) if alpha > 0.0 else 0.0
+    # the first rule (solve_contact): slides along the sticking impulse's tangential direction; its cap is n.G w < 0.2 n.G n
+    lt = T.T @ x
+    w = n + mu * lt / max(np.linalg.norm(lt), 1e-15)
+    sticking_dir = bool(ln > 0.0 and x @ x <= mu * mu * ln * ln)
+    dir_ratio = (n @ G @ w) / Gnn if (cn < 0.0 and not sticking_dir) else np.inf
+    return dict(beta=beta, mb2=mb2, alpha=alpha, dir_ratio=dir_ratio, separating=cn >= 0.0, sticking=bool(ln > 0.0 and x @ x <= mu_c * mu_c * ln * ln), sigma=sigma,
+                dir_cap=bool(dir_ratio < 0.2))
+
+
+class _contact_witness(object):
+    def __init__(self, cfg):
+        one = dict(cfg, num_envs=1)
+        self.full = O.OracleVecEnv(one)
+        self.sub = O.OracleVecEnv(dict(one, control_dt=one["simulation_dt"]))
+        self.full.contact_probe(0)
+        self.sub.contact_probe(0)
+        self.after = None
+
+    def last(self, st, acts):
+        out, self.after = [], np.zeros_like(st)
+        for i in range(st.shape[0]):
+            self.full.set_state(st[i:i + 1])
+            self.full.step(acts[i:i + 1])
+            out.append(self.full.contact_problem())
+            self.after[i] = self.full.get_state()[0]
+        return out
+
+    def first_one(self, row, act=None):
+        self.sub.set_state(row[None, :])
+        self.sub.step(np.zeros((1, 12), np.float32) if act is None else act[None, :])
+        return self.sub.contact_problem()
+
+    def first(self, st, acts=None):
+        return [self.first_one(st[i], None if acts is None else acts[i]) for i in range(st.shape[0])]
+
+    def first_and_last(self, st, acts):
+        """-> [(env, problem)], the first-substep problems of all envs, then the last-substep ones"""
+        return [list(enumerate(self.first(st, acts))), list(enumerate(self.last(st, acts)))]
+
+    def same_as(self, orc, d_o):
+        """the one-env pools ran what `orc` ran: generalized coordinates and velocities after the step, bit for bit (envs that ended are
+        reset from their own env id's stream and are left out)"""
+        keep = ~np.asarray(d_o, bool)
+        np.testing.assert_array_equal(self.after[keep, 0:37], orc.get_state()[keep, 0:37])
+
+    def lift_to_touch(self, row, gap):
+        """-> base height at which the LOWEST toe's gap is `gap` (bisection on the first substep's contact set, down to 1e-8 m; a fresh
+        pool's robots hang 6 cm over the ground: the bracket is the state's height - 0.25 m .. + 0.03 m)"""
+        row = row.copy()
+        z = row[S["GC"] + 2]
+        lo, hi = z - 0.25, z + 0.03                       # touching at lo, free at hi
+        for z_try, want in ((lo, True), (hi, False)):
+            row[S["GC"] + 2] = z_try
+            if self.first_one(row)["active"].any() != want:
+                return None
+        for _ in range(25):
+            mid = 0.5 * (lo + hi)
+            row[S["GC"] + 2] = mid
+            if self.first_one(row)["active"].any():
+                lo = mid
+            else:
+                hi = mid
+        return hi + gap
+
+
+def _contact_velocity(prob, l):
+    """the velocity contact l sees before its own impulse: free velocity + the other contacts' captured impulses"""
+    c = prob["cfree"][l].copy()
+    for lb in np.nonzero(prob["active"])[0]:
+        if lb != l:
+            c += prob["G"][3 * l:3 * l + 3, 3 * lb:3 * lb + 3] @ prob["lam"][lb]
+    return c
+
+
+def _slides(prob, l, mu):
+    lam, n = prob["lam"][l], prob["n"][l]
+    ln = lam @ n
+    return bool(ln > 0.0 and np.linalg.norm(lam - ln * n) >= (1.0 - 1e-6) * mu * ln)
+
+
+class friction_caps(object):
+    """Friction by env index, mu = MUS[(i + 2) % 9] (so four and sixteen neighbouring robots -- one wave of the 16- and of the 4-lane layout --
+    mix frictionless, ordinary and jammed ones), and every step a horizontal base velocity of 0.3-1.5 m/s in a random direction: the
+    contacts slide.  In odd steps an env with mu >= 0.8 takes, of eight directions 45 degrees apart, the one in which the first
+    substep's problem (real action) has the sliding toe with the smallest n.G w / n.G n: friction then acts towards the jamming
+    corner, the side on which the caps of both rules change the answer.  A robot none of whose feet touches (a fresh or re-set pool hangs 6 cm over the ground) is put down, lowest toe
+    0.2-1 mm in the ground.  Witness, on the first- and last-substep problems of every env (_contact_witness): contact solves with
+    mu^2 |beta|^2 > 1 - MD_SMIN (the jamming cap of make_contact_block_md; with `first_rule` the solves that the first rule's own cap
+    bounds, n.G w < 0.2 n.G n on a contact it slides, are counted next to them and must be at least 5: at 0.3-1.5 m/s a toe with mu >= 0.8 mostly sticks), pressing ones with mu <= MD_MUMIN (frictionless path), ordinary sliding ones
+    (MD_MUMIN < mu, below the cap, |lam_t| >= (1 - 1e-6) mu lam_n) -- at least 30 each -- and at least one substep in which one aligned
+    group of four envs holds all three kinds."""
+    MUS = (0.0, 1e-7, 1e-6, 1e-5, 0.05, 0.8, 1.3, 2.0, 3.0)
+
+    def __init__(self, orc, cfg, action_scale=0.5, first_rule=False):
+        self.orc, self.wit, self.scale, self.first_rule = orc, _contact_witness(cfg), action_scale, first_rule
+        self.jam = self.jam_sliding = self.frictionless = self.ordinary = self.mixed_steps = self.solves = self.dir_cap = 0
+        self.mb_max = 0.0
+
+    def material(self, i):
+        return self.MUS[(i + 2) % len(self.MUS)]
+
+    def __call__(self, st, k, rng):
+        n = st.shape[0]
+        gv = S["GV"]
+        acts = upcoming_actions(rng, n, self.scale)
+        for i in range(n):
+            r = _draws(5, k, i)
+            st[i, S["MATERIAL"]] = self.material(i)
+            speed, phi, gap = r.uniform(0.3, 1.5), r.uniform(0.0, 2.0 * np.pi), r.uniform(-1e-3, -2e-4)
+            st[i, gv:gv + 2] = [speed * np.cos(phi), speed * np.sin(phi)]
+            if not st[i, S["INCONTACT"]:S["INCONTACT"] + 4].any():
+                z = self.wit.lift_to_touch(f32_round_state(st[i:i + 1])[0], gap)
+                if z is not None:
+                    st[i, S["GC"] + 2] = z
+            if k % 2 == 1 and self.material(i) >= 0.8:
+                best = (np.inf, phi)
+                for j in range(8):
+                    ang = phi + j * np.pi / 4.0
+                    st[i, gv:gv + 2] = [speed * np.cos(ang), speed * np.sin(ang)]
+                    row = f32_round_state(st[i:i + 1])[0]
+                    prob = self.wit.first_one(row, acts[i])
+                    ratio = min([md_scalars(prob["G"][3 * l:3 * l + 3, 3 * l:3 * l + 3], _contact_velocity(prob, l), prob["n"][l], prob["vstar"][l],
+                                            row[S["MATERIAL"]])["dir_ratio"] for l in np.nonzero(prob["active"])[0]] + [np.inf])
+                    best = min(best, (ratio, ang))
+                st[i, gv:gv + 2] = [speed * np.cos(best[1]), speed * np.sin(best[1])]
+        st = f32_round_state(st)
+        for probs in self.wit.first_and_last(st, acts):
+            self.count(st, probs)
+        return st
+
+    def count(self, st, probs):
+        n = st.shape[0]
+        kinds = np.zeros((n, 3), bool)                        # frictionless, ordinary sliding, jammed
+        for i, prob in probs:
+            mu = st[i, S["MATERIAL"]]
+            for l in np.nonzero(prob["active"])[0]:
+                G = prob["G"][3 * l:3 * l + 3, 3 * l:3 * l + 3]
+                m = md_scalars(G, _contact_velocity(prob, l), prob["n"][l], prob["vstar"][l], mu)
+                if m["separating"]:
+                    continue
+                self.solves += 1
+                slides = _slides(prob, l, mu)
+                jam = m["mb2"] > 1.0 - MD_SMIN
+                self.mb_max = max(self.mb_max, float(np.sqrt(m["mb2"])))
+                self.dir_cap += int(m["dir_cap"])
+                if mu <= MD_MUMIN:
+                    self.frictionless += 1
+                    kinds[i, 0] = True
+                elif jam:
+                    self.jam += 1
+                    self.jam_sliding += int(slides)
+                    kinds[i, 2] = True
+                elif slides:
+                    self.ordinary += 1
+                    kinds[i, 1] = True
+        self.mixed_steps += int(any(kinds[g:g + 4].any(0).all() for g in range(0, n - 3, 4)))
+
+    def after_step(self, k, d_o, d_c):
+        self.wit.same_as(self.orc, d_o)
+
+    def witness(self):
+        print("[friction_caps%s] %d pressing contact solves probed: %d beyond the jamming cap (%d of them sliding), %d frictionless, "
+              "%d ordinary sliding; substeps with all three kinds in one group of four envs: %d; largest mu |beta| %.2f; under the first rule's cap: %d"
+              % (" first rule" if self.first_rule else "", self.solves, self.jam, self.jam_sliding, self.frictionless, self.ordinary,
+                 self.mixed_steps, self.mb_max, self.dir_cap))
+        assert self.jam >= 30 and self.frictionless >= 30 and self.ordinary >= 30 and self.mixed_steps >= 1
+        assert self.dir_cap >= 5 or not self.first_rule
+
+
+class fast_slide(object):
+    """Every step sets the base velocity of every robot to x in U(3, 6), y in U(-1, 1), z in U(-0.3, 0) m/s -- the speed the trained policy
+    runs at -- and puts a robot none of whose feet touches down, lowest toe 0.2-1 mm in the ground.  Every fourth env is instead lifted so that its
+    lowest toe's gap is in (-2e-5, 0) m (_contact_witness.lift_to_touch) and given the vertical base speed that leaves that toe's
+    normal approach speed below 1e-3 m/s: a barely pressing contact that slides fast, the IRRL_MD_SIGMAX pull-in.
+    Witness (first- and last-substep problems of every env): at least half of the pressing contacts slide; `n_sigma`, the solves with
+    sigma > MD_SIGMAX, is printed and NOT asserted: sigma = |x* / alpha - xi_c| exceeds 1e4 only while the free normal velocity c.n - v*
+    is within 5e-4 m/s of zero, and c holds dt M^-1 tau of the step's joint torques (+-0.05 m/s over the actions drawn), which no
+    state fixes -- the construction above reaches it in the first substep only by chance.  The branch is covered at the function
+    level (test_contact_model_gap.py)."""
+
+    def __init__(self, orc, cfg, action_scale=0.5):
+        self.orc, self.wit, self.scale = orc, _contact_witness(cfg), action_scale
+        self.pressing = self.sliding = self.n_sigma = self.lifted = self.moved = 0
+        self.sigma_max = 0.0
+
+    def __call__(self, st, k, rng):
+        n = st.shape[0]
+        gc, gv, inc = S["GC"], S["GV"], S["INCONTACT"]
+        for i in range(n):
+            r = _draws(6, k, i)
+            st[i, gv:gv + 3] = [r.uniform(3.0, 6.0), r.uniform(-1.0, 1.0), r.uniform(-0.3, 0.0)]
+            gap, approach, down = r.uniform(-2e-5, 0.0), r.uniform(0.0, 1e-3), r.uniform(-1e-3, -2e-4)
+            self.moved += 1
+            if i % 4 != 3 and not st[i, inc:inc + 4].any():
+                z = self.wit.lift_to_touch(f32_round_state(st[i:i + 1])[0], down)
+                if z is not None:
+                    st[i, gc + 2] = z
+            if i % 4 == 3:
+                z = self.wit.lift_to_touch(f32_round_state(st[i:i + 1])[0], gap)
+                if z is None:
+                    continue
+                st[i, gc + 2] = z
+                st[i, gv + 2] = 0.0
+                pos, vel = O.toe_kinematics(st[i, 0:19], st[i, gv:gv + 18])
+                st[i, gv + 2] = -vel[np.argmin(pos[:, 2]), 2] - approach
+                self.lifted += 1
+        st = f32_round_state(st)
+        for probs in self.wit.first_and_last(st, upcoming_actions(rng, n, self.scale)):
+            for i, prob in probs:
+                mu = st[i, S["MATERIAL"]]
+                for l in np.nonzero(prob["active"])[0]:
+                    m = md_scalars(prob["G"][3 * l:3 * l + 3, 3 * l:3 * l + 3], _contact_velocity(prob, l), prob["n"][l], prob["vstar"][l], mu)
+                    if m["separating"]:
+                        continue
+                    self.pressing += 1
+                    self.sliding += int(_slides(prob, l, mu))
+                    self.n_sigma += int(m["sigma"] > MD_SIGMAX)
+                    self.sigma_max = max(self.sigma_max, float(m["sigma"]))
+        return st
+
+    def after_step(self, k, d_o, d_c):
+        self.wit.same_as(self.orc, d_o)
+
+    def witness(self):
+        print("[fast_slide] %d env-steps at 3-6 m/s, %d of them lifted to a gap in (-2e-5, 0) m; %d pressing contact solves probed, %d sliding; "
+              "sigma > 1e4 in %d (not asserted), largest sigma %.3g" % (self.moved, self.lifted, self.pressing, self.sliding, self.n_sigma, self.sigma_max))
+        assert self.pressing >= 100 and 2 * self.sliding >= self.pressing and self.lifted >= self.moved // 8
+
+
+class bouncing_landings(object):
+    """Material by env: restitution RESTS[i % 4], threshold THRS[i % 3] (all twelve pairs in a pool of 16; friction stays).  Every step drops every robot anew:
+    upright within 0.05 degrees, every leg at (0, -0.78 f, 1.57 f) + U(-0.002, 0.002) rad (the four toes within 1 mm of one plane) with f = 1 (the nominal stance) or, alternating by
+    step and env, f = 0.25 (legs nearly straight: the toes' impulses reach the base instead of folding the legs), at the height where
+    the lowest toe's gap is U(-0.5, 0.2) mm -- within 1 mm of the ground, and the free ones arrive inside the step -- with a base
+    velocity of U(-0.3, 0.3) m/s in x and y and U(-1.5, -0.2) m/s in z, base angular velocity and joint rates zero.
+    Witness: the FIRST substep's restitution targets (_contact_witness.first: v* = -e v_n where v_n < -threshold, a function of the state
+    alone) -- at least 40 touching toes with v* > 0 and at least 40 with v* == 0 on envs with e > 0 (approach slower than the threshold) -- and, from the oracle's state behind the step, a
+    base moving UP again in at least 10 env-steps with e >= 0.9 and in none with e = 0."""
+    RESTS = (0.0, 0.5, 0.9, 0.95)
+    THRS = (0.01, 0.05, 0.5)
+
+    def __init__(self, orc, cfg):
+        self.orc, self.wit = orc, _contact_witness(cfg)
+        self.bounce = self.dead = self.reversed = self.reversed_dead = self.placed = 0
+        self.vstar_max = 0.0
+        self.rest = None
+
+    def __call__(self, st, k, rng):
+        gc, gv = S["GC"], S["GV"]
+        for i in range(st.shape[0]):
+            r = _draws(7, k, i)
+            st[i, S["MATERIAL"] + 1:S["MATERIAL"] + 3] = [self.RESTS[i % 4], self.THRS[i % 3]]
+            st[i, gv:gv + 18] = 0.0
+            gap, v = r.uniform(-5e-4, 2e-4), [r.uniform(-0.3, 0.3), r.uniform(-0.3, 0.3), r.uniform(-1.5, -0.2)]
+            fold, phi, half = (1.0, 0.25)[(i + k) % 2], r.uniform(0.0, 2.0 * np.pi), 0.5 * np.radians(r.uniform(0.0, 0.05))
+            st[i, gc + 3:gc + 7] = [np.cos(half), np.sin(half) * np.cos(phi), np.sin(half) * np.sin(phi), 0.0]
+            st[i, gc + 7:gc + 19] = np.tile([0.0, -0.78 * fold, 1.57 * fold], 4) + r.uniform(-0.002, 0.002, 12)
+            st[i, gc + 2] = 0.45
+            z = self.wit.lift_to_touch(f32_round_state(st[i:i + 1])[0], gap)
+            if z is None:
+                continue
+            st[i, gc + 2] = z
+            st[i, gv:gv + 3] = v
+            self.placed += 1
+        st = f32_round_state(st)
+        self.rest = st[:, S["MATERIAL"] + 1].copy()
+        for i, prob in enumerate(self.wit.first(st)):
+            vs = prob["vstar"][prob["active"]]
+            self.bounce += int((vs > 0.0).sum())
+            if self.rest[i] > 0.0:                          # (e = 0 has v* == 0 at any speed)
+                self.dead += int((vs == 0.0).sum())
+            self.vstar_max = max(self.vstar_max, float(vs.max()) if len(vs) else 0.0)
+        return st
+
+    def after_step(self, k, d_o, d_c):
+        up = self.orc.get_state()[:, S["GV"] + 2] > 0.0
+        self.reversed += int((up & (self.rest >= 0.9) & ~np.asarray(d_o, bool)).sum())
+        self.reversed_dead += int((up & (self.rest == 0.0) & ~np.asarray(d_o, bool)).sum())
+
+    def witness(self):
+        print("[bouncing_landings] %d placements within 1 mm of the ground; touching toes of the first substep: %d with v* > 0 (largest %.2f m/s), "
+              "%d with v* == 0 (e > 0); env-steps that end with the base moving up: %d with e >= 0.9, %d with e = 0"
+              % (self.placed, self.bounce, self.vstar_max, self.dead, self.reversed, self.reversed_dead))
+        assert self.bounce >= 40 and self.dead >= 40 and self.reversed >= 10 and self.reversed_dead == 0
+
+
 def check_free_running(make_orc, make_cand, cfg, preroll=90):
     """1, 8 and 400 substeps of free running (no re-synchronisation) from a common state in which the robots
     already stand / hop on the ground (reached by `preroll` oracle steps), BASELINE.md section 3.

@@ -1,6 +1,6 @@
 """The edge scenarios of test_kernel_source_edges_emulated.py through the C-ABI on an MI355X: the HIP kernels against the f64 oracle at
-long episode clocks, on the rim of the height field, on the sloped and crossed parts of the motor envelope and at the z > 0.65 m and tilt
-terminations -- both lane layouts, and for the scenarios on flat ground also a ContactSolver 1 pool (the run-time-solver kernels, variant
+long episode clocks, on the rim of the height field, on the sloped and crossed parts of the motor envelope, at the z > 0.65 m and tilt
+terminations and in the contact regimes (friction caps mixed inside one wave, 3-6 m/s slides, bouncing landings) -- both lane layouts, and for the scenarios on flat ground also a ContactSolver 1 pool (the run-time-solver kernels, variant
 "md", instead of "shipped_flat").  Then the multi-step kernel's bit-identity with one launch per step, started FROM those states.
 Scenario hooks, witnesses and tolerances: parity_lib.py; nothing here is fitted to a GPU run."""
 import numpy as np
@@ -55,12 +55,44 @@ def test_height_and_tilt_terminations_on_gpu(monkeypatch, lanes, over, variant):
     EDGES.terminations_case(_maker(monkeypatch, lanes, variant), n=13, **over)
 
 
+@pytest.mark.parametrize("lanes,over,variant", POOLS, ids=POOL_IDS)
+def test_friction_caps_on_gpu(monkeypatch, lanes, over, variant):
+    """16 envs: one 4-lane wave holds all nine frictions, the 16-lane waves hold four robots each -- envs 4..7 with mu 1.3, 2, 3 and 0."""
+    EDGES.friction_caps_case(_maker(monkeypatch, lanes, variant), n=N, **over)
+
+
 @pytest.mark.parametrize("lanes", [16, 4])
-@pytest.mark.parametrize("scenario", ["clock", "corner", "motor"])
+@pytest.mark.parametrize("solver", [2, 0])
+def test_friction_caps_first_rule_on_gpu(monkeypatch, solver, lanes):
+    EDGES.friction_caps_case(_maker(monkeypatch, lanes, "dir"), n=N, ContactSolver=solver)
+
+
+@pytest.mark.parametrize("lanes", [16, 4])
+def test_friction_caps_on_rough_ground_on_gpu(monkeypatch, lanes):
+    EDGES.friction_caps_case(_maker(monkeypatch, lanes, "shipped"), n=N, terrain=True)
+
+
+@pytest.mark.parametrize("lanes,over,variant", POOLS, ids=POOL_IDS)
+def test_fast_slide_on_gpu(monkeypatch, lanes, over, variant):
+    EDGES.fast_slide_case(_maker(monkeypatch, lanes, variant), n=N, **over)
+
+
+@pytest.mark.parametrize("lanes", [16, 4])
+def test_fast_slide_on_rough_ground_on_gpu(monkeypatch, lanes):
+    EDGES.fast_slide_case(_maker(monkeypatch, lanes, "shipped"), n=N, terrain=True)
+
+
+@pytest.mark.parametrize("lanes,over,variant", POOLS, ids=POOL_IDS)
+def test_bouncing_landings_on_gpu(monkeypatch, lanes, over, variant):
+    EDGES.bouncing_landings_case(_maker(monkeypatch, lanes, variant), n=N, **over)
+
+
+@pytest.mark.parametrize("lanes", [16, 4])
+@pytest.mark.parametrize("scenario", ["clock", "corner", "motor"] + sorted(EDGES.CONTACT_SCENARIOS))
 def test_multi_step_kernel_equals_one_launch_per_step_from_edge_states(monkeypatch, scenario, lanes):
     """No new code runs here: the multi-step kernel's bit-identity with K step() calls (test_gpu_runtime_solver_persistent.py, from fresh
     pools) is started from states that claim has not seen -- frame 24 990, robots over the corner of the height field, joint rates beyond
-    the motor's no-load speed.  16 steps, every step's outputs and the final pool."""
+    the motor's no-load speed, and the step-0 states of the three contact scenarios.  16 steps, every step's outputs and the final pool."""
     import torch
     monkeypatch.setenv("IRRL_LANES_PER_ROBOT", str(lanes))
     n, K = (12 if scenario == "motor" else N), 16

@@ -1,7 +1,8 @@
 """The kernel source (csrc/env_core.hpp, through the host lane emulation, both lane layouts) against the f64 oracle in the regions
 that random actions from a fresh reset never reach -- long episode clocks, the rim of the height field, the sloped and crossed parts
-of the motor's torque-speed envelope, the z > 0.65 m and tilt terminations.  Scenario hooks and their witnesses: parity_lib.py
-("Edge scenarios"); the same scenarios through the C-ABI on an MI355X: test_gpu_parity_edges.py.  Tolerances: the unchanged TOL_STEP,
+of the motor's torque-speed envelope, the z > 0.65 m and tilt terminations, and the contact regimes: the caps of the per-contact
+rules (frictionless, jamming corner) mixed with ordinary robots in one wave, slides at 3-6 m/s, landings that bounce.  Scenario hooks
+and their witnesses: parity_lib.py ("Edge scenarios"); the same scenarios through the C-ABI on an MI355X: test_gpu_parity_edges.py.  Tolerances: the unchanged TOL_STEP,
 TERRAIN_MAX_FACTOR on rough ground, and the derived 4 f32 ulps on base x / y where robots are moved to x = +-250 m."""
 import numpy as np
 import pytest
@@ -62,8 +63,45 @@ def terminations_case(make_cand, n=13, **over):
     return worst
 
 
+def friction_caps_case(make_cand, n=16, terrain=False, **over):
+    cfg = load_env_cfg("bp5_terrain.yaml" if terrain else "bp5_imitation.yaml", num_envs=n, **over)
+    orc, cand = O.OracleVecEnv(cfg), make_cand(cfg)
+    hook = PL.friction_caps(orc, cfg, first_rule=not (cfg["ContactSolver"] & 1))
+    worst, n_done = PL.check_teacher_forced(orc, cand, steps=STEPS, seed=5, perturb=hook, after_step=hook.after_step,
+                                            max_factor=PL.TERRAIN_MAX_FACTOR if terrain else 10.0)
+    hook.witness()
+    return worst
+
+
+def fast_slide_case(make_cand, n=16, terrain=False, **over):
+    cfg = load_env_cfg("bp5_terrain.yaml" if terrain else "bp5_imitation.yaml", num_envs=n, **over)
+    orc, cand = O.OracleVecEnv(cfg), make_cand(cfg)
+    hook = PL.fast_slide(orc, cfg)
+    worst, n_done = PL.check_teacher_forced(orc, cand, steps=STEPS, seed=6, perturb=hook, after_step=hook.after_step,
+                                            max_factor=PL.TERRAIN_MAX_FACTOR if terrain else 10.0)
+    hook.witness()
+    return worst
+
+
+def bouncing_landings_case(make_cand, n=16, **over):
+    cfg = load_env_cfg("bp5_imitation.yaml", num_envs=n, **over)
+    orc, cand = O.OracleVecEnv(cfg), make_cand(cfg)
+    hook = PL.bouncing_landings(orc, cfg)
+    worst, n_done = PL.check_teacher_forced(orc, cand, steps=STEPS, seed=7, perturb=hook, after_step=hook.after_step)
+    hook.witness()
+    return worst
+
+
+CONTACT_SCENARIOS = {"friction_caps": PL.friction_caps, "fast_slide": PL.fast_slide, "bouncing_landings": PL.bouncing_landings}
+
+
 def edge_state(scenario, n):
     """-> (config, the f32-rounded state of an oracle pool after the scenario's step-0 perturbation): where the multi-step tests start"""
+    if scenario in CONTACT_SCENARIOS:
+        cfg = load_env_cfg("bp5_imitation.yaml", num_envs=n)
+        orc = O.OracleVecEnv(cfg)
+        hook = CONTACT_SCENARIOS[scenario](orc, cfg)
+        return cfg, PL.f32_round_state(hook(PL.f32_round_state(orc.get_state()), 0, np.random.RandomState(0)))
     if scenario == "clock":
         cfg = load_env_cfg("default_cfg.yaml", num_envs=n)
         orc = O.OracleVecEnv(cfg)
@@ -103,12 +141,38 @@ def test_height_and_tilt_terminations(emu):
     terminations_case(emu)
 
 
-@pytest.mark.parametrize("scenario", ["clock", "corner", "motor"])
+@pytest.mark.parametrize("emu", EMUS)
+@pytest.mark.parametrize("solver", [3, 1, 2, 0])
+def test_friction_caps_frictionless_ordinary_and_jammed_robots_side_by_side(emu, solver):
+    """ContactSolver 3 / 1: the published rule in both sweep orders (jamming cap, frictionless path, the wave-level skips around them);
+    2 / 0: the first rule and its own cap."""
+    friction_caps_case(emu, ContactSolver=solver)
+
+
+@pytest.mark.parametrize("emu", EMUS)
+def test_friction_caps_on_rough_ground(emu):
+    friction_caps_case(emu, terrain=True)
+
+
+@pytest.mark.parametrize("emu", EMUS)
+@pytest.mark.parametrize("terrain", [False, True], ids=["flat", "rough"])
+def test_fast_slide(emu, terrain):
+    fast_slide_case(emu, terrain=terrain)
+
+
+@pytest.mark.parametrize("emu", EMUS)
+@pytest.mark.parametrize("solver", [3, 2])
+def test_bouncing_landings(emu, solver):
+    bouncing_landings_case(emu, ContactSolver=solver)
+
+
+@pytest.mark.parametrize("scenario", ["clock", "corner", "motor"] + sorted(CONTACT_SCENARIOS))
 def test_carried_lane_context_equals_store_and_load_from_edge_states(scenario):
     """The host counterpart of test_multi_step_kernel_equals_one_launch_per_step_from_edge_states (test_gpu_parity_edges.py): 16 steps with
     the lane context carried in registers (sub-lanes 1-3 poisoned behind every step) == 16 step() calls, from frame 24 990, from over the
-    corner of the height field and from joint rates beyond the motor's no-load speed -- every step's outputs and the final pool, bit for bit."""
-    n, K = 12, 16
+    corner of the height field, from joint rates beyond the motor's no-load speed and from the step-0 states of the three contact
+    scenarios (mixed friction, 3-6 m/s slides, landings) -- every step's outputs and the final pool, bit for bit."""
+    n, K = (16 if scenario in CONTACT_SCENARIOS else 12), 16
     cfg, st = edge_state(scenario, n)
     a, b = E.EmuVecEnv16(cfg), E.EmuVecEnv16(cfg)
     a.set_state(st)
