@@ -194,6 +194,14 @@ IRRL_DEV vf pick4(vf a, vf b, vf c, vf d, vi leg) { return vsel(leg == 0, a, vse
 #define IRRL_L_HIP 0.085f               /* ENV:1949-1952 */
 #define IRRL_L_THIGH 0.209f
 #define IRRL_L_CALF 0.2175f
+// inverse_kinematics of a target beyond reach (ENV:1692-1698 rescales it to L = max_len - 1e-5, max_len = sqrt(l_hip^2 + (l_thigh + l_calf)^2)):
+//   LR      = sqrt(L^2 - l_hip^2)
+//   TH2     = -(3.1415926 - acos((l_thigh^2 + l_calf^2 - LR^2) / 2 / l_thigh / l_calf + 1e-5))
+//   ACOS_A2 = acos((LR^2 + l_thigh^2 - l_calf^2) / 2 / LR / l_thigh - 1e-5)
+// evaluated in f64 (tests/test_oracle_task_math.py recomputes them)
+#define IRRL_IK_REACH_LR 0.4264898033f
+#define IRRL_IK_REACH_TH2 (-0.01453747172f)
+#define IRRL_IK_REACH_ACOS_A2 0.008352283088f
 
 // per-lane (per-leg) model + the shared base body
 struct LegModel {
@@ -302,14 +310,18 @@ IRRL_DEV void inverse_kinematics(vf x, vf y, vf z, vf max_len, vm is_right, vf &
   th0 = vsel(ok0, v_asin(temp), th0);
   vf lr = v_sqrt(x * x + y * y + z * z - l_hip * l_hip);
   lr = vsel(lr > (l_thigh + l_calf), (l_thigh + l_calf - 1e-4f), lr);
+  // A rescaled target lies on the sphere of radius max_len - 1e-5, 1e-5 m inside the straight leg: lr, the knee angle and acos(a2) are
+  // then constants of the leg geometry, and acos at 1 - 3.5e-5 turns the f32 rounding of its argument into 6e-5 rad.  too_long lanes
+  // take the constants (IRRL_IK_REACH_*, f64); every other lane computes what it always did.
+  lr = vsel(too_long, IRRL_IK_REACH_LR, lr);
   vf t2 = (l_thigh * l_thigh + l_calf * l_calf - lr * lr) * (0.5f / (l_thigh * l_calf)) + 1e-5f;
   ok2 = v_abs(t2) <= 1.0f;
-  th2 = vsel(ok2, -(IRRL_PI_REF - v_acos(t2)), th2);
+  th2 = vsel(ok2, vsel(too_long, IRRL_IK_REACH_TH2, -(IRRL_PI_REF - v_acos(t2))), th2);
   vf ilr = v_rcp(lr);
   vf a1 = x * ilr;
   vf a2 = (lr * lr + l_thigh * l_thigh - l_calf * l_calf) * ((0.5f / l_thigh) * ilr) - 1e-5f;
   ok1 = (v_abs(a1) <= 1.0f) & (v_abs(a2) <= 1.0f);
-  th1 = vsel(ok1, v_acos(a2) - v_asin(a1), th1);
+  th1 = vsel(ok1, vsel(too_long, IRRL_IK_REACH_ACOS_A2, v_acos(a2)) - v_asin(a1), th1);
 }
 // ENV:1273-1312 for one joint; knee (k == 2) carries the 1.55f ratio
 IRRL_DEV vf torque_clamp1(vf tau, vf qd, int k, const EnvParams &P) {

@@ -738,6 +738,329 @@ class bouncing_landings(object):
         assert self.bounce >= 40 and self.dead >= 40 and self.reversed >= 10 and self.reversed_dead == 0
 
 
+# ------------------------------------------------------------------------------------------------------------------------
+# The task state.  check_teacher_forced copies the oracle's whole state into the candidate before EVERY step, and what the step's
+# closing task logic writes (command_obs_update -> gait_generator_manual -> inverse_kinematics: JR, JRL, JDR, EER, CMD, CMDF, UPH, T0)
+# is consumed only by the NEXT step -- by then the oracle's copy has replaced it.  A wrong joint reference on a non-reset step passes
+# every comparison of check_teacher_forced; task_state_check is the after_step hook that looks at these fields.
+#   CMD, CMDF, EER 1e-6 and T0 1e-7: check_init's bounds.
+#   UPH: UPH_ULPS f32 ulps of the configured up_height.  It is either up_height itself (the f32 rounding of the config value: half an
+#        ulp) or ratio * up_height with ratio = max(|cmdf_x| / Vx, |cmdf_y| / Vy, |cmdf_z / Omega|) <= 0.1: cmdf enters the step bit-equal
+#        and is filtered with two products and a sum (1.5 ulps), the f32 Vx / Vy / Omega and up_height are half an ulp each off, the
+#        division is 1 ulp on the GPU (reciprocal), the product half an ulp: 4.5 ulps of a value at most a tenth of up_height.  8 ulps
+#        of up_height itself is ten times that and still 6e-8 m.  An env-step whose ratio is within 1e-6 of the 0.1 threshold (the two
+#        branches are 0.9 up_height apart there) is marginal.
+#   CONTACT: equal.  JRL == JR behind the step in each pool, bit for bit.
+#   JR, per leg: 2e-6 + JR_K s.  2e-6 is check_init's bound; s is the REFERENCE's own sensitivity to f32 inputs: the largest change of
+#        any of the leg's three angles in O.inverse_kinematics (f64) over the 8 sign combinations of one f32 ulp on each coordinate of the
+#        leg's target (recomputed from the oracle's EER, the hip offsets and the lean).  A slot whose asin / acos failed holds another leg's
+#        value (the shared temp[3] of ENV:1766): it is held to the largest bound among the env's legs.
+#        JR_K is twice the worst (err - 2e-6) / s of the oracle's OWN f32 build over the in-reach legs of the committed scenarios
+#        (gait_reach, gait_low_stance, gait_lateral and the two base configurations, measured on the CPU: DESIGN.md section 5); the
+#        factor two is for reduction order and the GPU's 1-ulp rcp / rsq / sqrt.  It is not fitted to the kernels or to a GPU run.
+#   JDR: 2 x (JR bound) / control_dt -- a difference of two references.
+# A leg whose ok / fail decision sits within rounding distance of its threshold in the oracle (|arg| - 1 of an asin / acos slot,
+# y^2 + z^2 - l_hip^2 under the square root: IK_MARGIN, or a decision that one f32 ulp on the target flips) may decide differently in f32:
+# its env-step is left out of JR / JDR and counted; at most 1 % of a case's env-steps.
+# ------------------------------------------------------------------------------------------------------------------------
+L_HIP, L_THIGH, L_CALF = 0.085, 0.209, 0.2175                  # ENV:1949-1952
+MAX_LEN = float(np.sqrt(L_HIP * L_HIP + (L_THIGH + L_CALF) ** 2))
+EE_OFF = np.array([[0.19, -0.058, 0.0], [0.19, 0.058, 0.0], [-0.19, -0.058, 0.0], [-0.19, 0.058, 0.0]])    # ENV:331-334
+JR_ATOL = 2e-6
+JR_K = 59.1                  # 2 x 29.53, the f32 oracle's worst in-reach ratio (gait_low_stance, GaitType 2)
+UPH_ULPS = 8
+IK_MARGIN = 2e-6             # 16 f32 eps on an argument of magnitude 1
+_SIGNS = [(a, b, c) for a in (-1.0, 1.0) for b in (-1.0, 1.0) for c in (-1.0, 1.0)]
+
+
+def leg_targets(so, cfg):
+    """-> [n, 4, 3]: what the oracle handed to inverse_kinematics in its last gait pass: toe + (0, toff, 0), toe = EER - hip offset"""
+    n = so.shape[0]
+    tgt = so[:, S["EER"]:S["EER"] + 12].reshape(n, 4, 3) - EE_OFF
+    lf, lh = float(cfg["LeanFront"]), float(cfg["LeanHind"])
+    tgt[:, :, 1] += np.array([-L_HIP + lf, L_HIP - lf, -L_HIP + lh, L_HIP - lh])
+    return tgt
+
+
+def ik_margin(x, y, z):
+    """distance of the three ok / fail decisions of ENV:1687-1751 from their thresholds, in f64 on the (rescaled) target;
+    -> (margin, beyond): the smallest of | |arg| - 1 | over the asin / acos arguments that exist and |y^2 + z^2 - l_hip^2| / (y^2 + z^2)"""
+    ll = np.sqrt(x * x + y * y + z * z)
+    beyond = ll > MAX_LEN
+    if beyond:
+        x, y, z = [v * (MAX_LEN - 1e-5) / ll for v in (x, y, z)]
+    m = [abs(y * y + z * z - L_HIP * L_HIP) / (y * y + z * z)]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        root = np.sqrt(y * y * (z * z + y * y - L_HIP * L_HIP))
+        lr = np.sqrt(x * x + y * y + z * z - L_HIP * L_HIP)
+        lr = (L_THIGH + L_CALF - 1e-4) if lr > L_THIGH + L_CALF else lr
+        args = [(-z * L_HIP - root) / (z * z + y * y), (z * L_HIP + root) / (z * z + y * y),
+                (L_THIGH * L_THIGH + L_CALF * L_CALF - lr * lr) / 2 / L_THIGH / L_CALF + 1e-5, x / lr,
+                (lr * lr + L_THIGH * L_THIGH - L_CALF * L_CALF) / 2 / lr / L_THIGH - 1e-5]
+    m += [abs(abs(a) - 1.0) for a in args if np.isfinite(a)]
+    return min(m), bool(beyond)
+
+
+def ik_sensitivity(x, y, z, is_right):
+    """-> (s, err, flips): s = the largest change of an angle of O.inverse_kinematics (f64) over the 8 sign combinations of one f32 ulp on
+    each coordinate; err = the error mask at the target itself (1: abad, 2: knee, 4: hip slot stale); flips = a combination changes it"""
+    th0, err = O.inverse_kinematics(x, y, z, is_right)
+    ulp = [float(np.spacing(np.float32(abs(v)))) for v in (x, y, z)]
+    s, flips = 0.0, False
+    for sg in _SIGNS:
+        th, e = O.inverse_kinematics(x + sg[0] * ulp[0], y + sg[1] * ulp[1], z + sg[2] * ulp[2], is_right)
+        flips |= e != err
+        s = max(s, float(np.abs(th - th0).max()))
+    return s, err, flips
+
+
+def task_state_errors(so, sc, cfg, ok=None, K=JR_K):
+    """Post-step flat states of the oracle and of the candidate -> dict of per-env (per-leg where it says so) errors, bounds and masks.
+    ok: env-steps to look at (contact set and done flag agree); the others come back masked out of every `*_bad` entry."""
+    n = so.shape[0]
+    ok = np.ones(n, bool) if ok is None else np.asarray(ok, bool)
+    out = dict(ok=ok)
+    for key, w, tol in (("CMD", 3, 1e-6), ("CMDF", 3, 1e-6), ("EER", 12, 1e-6), ("T0", 1, 1e-7)):
+        e = np.abs(sc[:, S[key]:S[key] + w] - so[:, S[key]:S[key] + w]).max(1)
+        out[key] = e
+        out[key + "_bad"] = ok & ~(e <= tol)
+    uph = float(cfg["up_height"])
+    out["UPH"] = np.abs(sc[:, S["UPH"]] - so[:, S["UPH"]])
+    uph_marginal = np.zeros(n, bool)
+    if cfg["HeightVariable"]:
+        cf = np.abs(so[:, S["CMDF"]:S["CMDF"] + 3])
+        ratio = cf[:, 0] / float(cfg["Vx"])
+        if cfg["Vy"] > 0:
+            ratio = np.maximum(ratio, cf[:, 1] / float(cfg["Vy"]))
+        if cfg["Omega"] > 0:
+            ratio = np.maximum(ratio, cf[:, 2] / float(cfg["Omega"]))
+        uph_marginal = np.abs(ratio - 0.1) < 1e-6
+        out["uph_ratio"] = ratio
+    out["UPH_bad"] = ok & ~uph_marginal & ~(out["UPH"] <= UPH_ULPS * float(np.spacing(np.float32(uph))))
+    out["CONTACT_bad"] = ok & np.any(sc[:, S["CONTACT"]:S["CONTACT"] + 4] != so[:, S["CONTACT"]:S["CONTACT"] + 4], axis=1)
+    out["JRL_bad"] = (np.any(so[:, S["JRL"]:S["JRL"] + 12] != so[:, S["JR"]:S["JR"] + 12], axis=1) |
+                      np.any(sc[:, S["JRL"]:S["JRL"] + 12] != sc[:, S["JR"]:S["JR"] + 12], axis=1))
+    tgt = leg_targets(so, cfg)
+    s = np.zeros((n, 4))
+    err = np.zeros((n, 4), int)
+    beyond = np.zeros((n, 4), bool)
+    near = np.zeros((n, 4), bool)
+    dist = np.linalg.norm(tgt, axis=2) - MAX_LEN
+    for i in range(n):
+        for l in range(4):
+            x, y, z = tgt[i, l]
+            s[i, l], err[i, l], flips = ik_sensitivity(x, y, z, l % 2 == 0)
+            margin, beyond[i, l] = ik_margin(x, y, z)
+            near[i, l] = flips or margin < IK_MARGIN
+    own = JR_ATOL + K * s
+    bound = np.where(err != 0, own.max(1)[:, None], own)           # a leg with a stale slot holds another leg's angle
+    e_jr = np.abs(sc[:, S["JR"]:S["JR"] + 12] - so[:, S["JR"]:S["JR"] + 12]).reshape(n, 4, 3).max(2)
+    e_jdr = np.abs(sc[:, S["JDR"]:S["JDR"] + 12] - so[:, S["JDR"]:S["JDR"] + 12]).reshape(n, 4, 3).max(2)
+    marginal = near.any(1)
+    use = ok & ~marginal
+    out.update(targets=tgt, s=s, err=err, beyond=beyond, dist=dist, marginal=ok & marginal, JR=e_jr, JDR=e_jdr, JR_bound=bound,
+               JDR_bound=2.0 * bound / float(cfg["control_dt"]), ratio=(e_jr - JR_ATOL) / np.maximum(s, 1e-300))
+    out["JR_bad"] = use[:, None] & ~(e_jr <= bound)
+    out["JDR_bad"] = use[:, None] & ~(e_jdr <= out["JDR_bound"])
+    return out
+
+
+class task_state_check(object):
+    """after_step hook of check_teacher_forced: task_state_errors behind every step, asserted (assert_bounds=False only records: the
+    calibration of JR_K with the oracle's f32 build as the candidate).  report() prints the worst figures and holds the 1 % cap."""
+    FIELDS = ("CMD", "CMDF", "EER", "T0", "UPH", "CONTACT", "JRL", "JR", "JDR")
+
+    def __init__(self, orc, cand, cfg, assert_bounds=True, K=JR_K):
+        self.orc, self.cand, self.cfg, self.assert_bounds, self.K = orc, cand, cfg, assert_bounds, K
+        self.env_steps = self.left_out = self.legs_in = self.legs_beyond = self.stale = 0
+        self.worst = dict(CMD=0.0, CMDF=0.0, EER=0.0, T0=0.0, UPH=0.0, JR_in=0.0, JR_beyond=0.0, JDR_in=0.0, JDR_beyond=0.0,
+                          ratio_in=0.0, ratio_beyond=0.0, JR_over_bound=0.0, JDR_over_bound=0.0, s_max=0.0)
+        self.last = None
+
+    def after_step(self, k, d_o, d_c):
+        so, sc = self.orc.get_state(), self.cand.get_state()
+        ok = np.all(sc[:, S["INCONTACT"]:S["INCONTACT"] + 4] == so[:, S["INCONTACT"]:S["INCONTACT"] + 4], axis=1) & (np.asarray(d_o) == np.asarray(d_c))
+        r = self.last = task_state_errors(so, sc, self.cfg, ok, self.K)
+        self.env_steps += len(ok)
+        self.left_out += int(r["marginal"].sum())
+        w = self.worst
+        if ok.any():
+            for key in ("CMD", "CMDF", "EER", "T0", "UPH"):
+                w[key] = max(w[key], float(r[key][ok].max()))
+        use = (ok & ~r["marginal"])[:, None] & np.ones((1, 4), bool)
+        clean = use & (r["err"] == 0)
+        for name, sel in (("in", clean & ~r["beyond"]), ("beyond", clean & r["beyond"])):
+            if sel.any():
+                w["JR_" + name] = max(w["JR_" + name], float(r["JR"][sel].max()))
+                w["JDR_" + name] = max(w["JDR_" + name], float(r["JDR"][sel].max()))
+                w["ratio_" + name] = max(w["ratio_" + name], float(r["ratio"][sel].max()))
+        if use.any():
+            w["JR_over_bound"] = max(w["JR_over_bound"], float((r["JR"] / r["JR_bound"])[use].max()))
+            w["JDR_over_bound"] = max(w["JDR_over_bound"], float((r["JDR"] / r["JDR_bound"])[use].max()))
+            w["s_max"] = max(w["s_max"], float(r["s"][use].max()))
+        self.legs_in += int((use & ~r["beyond"]).sum())
+        self.legs_beyond += int((use & r["beyond"]).sum())
+        self.stale += int((use & (r["err"] != 0)).sum())
+        if self.assert_bounds:
+            for key in self.FIELDS:
+                bad = r[key + "_bad"]
+                assert not bad.any(), "step %d: %s outside its bound in env(s) %s: %s" % (
+                    k, key, np.nonzero(bad.reshape(len(ok), -1).any(1))[0].tolist(),
+                    {f: float(np.max(r[f])) for f in ("JR", "JDR", "CMD", "CMDF", "EER", "T0", "UPH")})
+
+    def report(self, name="task state"):
+        w = self.worst
+        print("[%s] %d env-steps, %d left out (a decision within rounding distance of its threshold; cap 1 %%); legs compared: %d in reach, "
+              "%d beyond, %d with a stale slot; worst CMD %.1e CMDF %.1e EER %.1e T0 %.1e UPH %.1e; JR in reach %.2e beyond %.2e rad, JDR in "
+              "reach %.2e beyond %.2e rad/s; (JR err - 2e-6) / s: in reach %.2f beyond %.2f (K = %g, largest s %.2e); worst error / bound: JR %.2f JDR %.2f"
+              % (name, self.env_steps, self.left_out, self.legs_in, self.legs_beyond, self.stale, w["CMD"], w["CMDF"], w["EER"], w["T0"], w["UPH"],
+                 w["JR_in"], w["JR_beyond"], w["JDR_in"], w["JDR_beyond"], w["ratio_in"], w["ratio_beyond"], self.K, w["s_max"],
+                 w["JR_over_bound"], w["JDR_over_bound"]))
+        assert self.env_steps > 0 and self.left_out <= 0.01 * self.env_steps, (self.left_out, self.env_steps)
+        return w
+
+
+class _gait_scenario(object):
+    """common part of the three gait-generator scenarios: the task-state comparison behind every step, and the oracle's own leg targets
+    and error masks (task_state_errors computes them from the oracle's state) handed to the scenario's `count`"""
+
+    def __init__(self, orc, cand, cfg, assert_bounds=True):
+        self.orc, self.cfg = orc, cfg
+        self.task = task_state_check(orc, cand, cfg, assert_bounds=assert_bounds) if cand is not None else None
+
+    def after_step(self, k, d_o, d_c):
+        self.task.after_step(k, d_o, d_c)
+        self.count(k, self.task.last, np.asarray(d_o, bool), self.orc.get_state())
+
+    def count(self, k, r, d_o, so):
+        pass
+
+
+class gait_reach(_gait_scenario):
+    """Legs beyond reach (default_cfg.yaml with Vx 7.5, or period 0.3: the step length Vx lam period / 2 puts the stance ends outside
+    max_len).  Every step pins CMD = CMDF of env i to (f Vx, 0, U(-Omega, Omega)), f in 0.6 .. 1.0 -- U(0.98, 1) in three env-steps of
+    four (at full speed a leg is beyond reach for a third of its cycle, and not at all below 0.86 Vx), U(0.6, 0.95) in the fourth; pinned
+    equal, the command filter leaves them alone -- so that a pool holds rescaled and ordinary legs side by side.  Witness, from the oracle's targets behind every step: at least
+    a quarter of the env-steps have a leg beyond max_len, at least a quarter have every leg in reach, and legs lie within 1 mm on
+    either side of the limit."""
+
+    def __init__(self, orc, cand, cfg, assert_bounds=True):
+        _gait_scenario.__init__(self, orc, cand, cfg, assert_bounds)
+        self.n_beyond = self.n_all_in = self.total = self.just_in = self.just_out = 0
+
+    def __call__(self, st, k, rng):
+        for i in range(st.shape[0]):
+            r = _draws(8, k, i)
+            frac = r.uniform(0.6, 0.95) if (k + i) % 4 == 0 else r.uniform(0.98, 1.0)
+            cmd = [frac * self.cfg["Vx"], 0.0, r.uniform(-1.0, 1.0) * self.cfg["Omega"]]
+            st[i, S["CMD"]:S["CMD"] + 3] = cmd
+            st[i, S["CMDF"]:S["CMDF"] + 3] = cmd
+        return st
+
+    def count(self, k, r, d_o, so):
+        self.total += len(d_o)
+        self.n_beyond += int(r["beyond"].any(1).sum())
+        self.n_all_in += int((~r["beyond"]).all(1).sum())
+        self.just_in += int(((r["dist"] <= 0.0) & (r["dist"] > -1e-3)).sum())
+        self.just_out += int(((r["dist"] > 0.0) & (r["dist"] < 1e-3)).sum())
+
+    def witness(self):
+        print("[gait_reach] %d env-steps: %d with a leg beyond max_len, %d with every leg in reach; legs within 1 mm of the limit: %d inside, %d outside"
+              % (self.total, self.n_beyond, self.n_all_in, self.just_in, self.just_out))
+        assert 4 * self.n_beyond >= self.total and 4 * self.n_all_in >= self.total and self.just_in >= 1 and self.just_out >= 1
+
+
+class gait_low_stance(_gait_scenario):
+    """stand_height 0.11-0.12 m with 0.025-0.03 m of lean: around the swing apex the target comes closer to the hip axis than l_hip (the
+    square root of the abad slot is of a negative number) and closer to the hip than |l_thigh - l_calf| (knee and hip slots), so slots FAIL and
+    keep the shared temp[3] of ENV:1766 -- the previous leg's angle, across legs and across the two passes of a reset; in the kernels the
+    chain is three legs_bcast hand-offs.  Every step pins CMD = CMDF to (U(0, 1) Vx, 0, U(-Omega, Omega)).  Witness, from the oracle's
+    error mask per leg (O.inverse_kinematics on its targets): every slot fails on every leg; `chain` = the longest run of consecutive legs
+    failing one slot reaches `want_chain` (2 for GaitType 0 and 1, 4 for GaitType 3: all phases equal, all four legs at the apex together);
+    on a reset step leg 0 fails in the second pass and holds leg 3's first-pass value (recomputed: the oracle's gait generator at
+    t0 - control_dt, one pass from temp = 0, against its two-pass call at t0; that two-pass reference reaches the state as the new
+    episode's joint angles and rates, which check_teacher_forced compares); on an ordinary step -- one pass, temp starts at 0 -- leg 0
+    fails and holds 0."""
+
+    def __init__(self, orc, cand, cfg, want_chain, assert_bounds=True):
+        _gait_scenario.__init__(self, orc, cand, cfg, assert_bounds)
+        self.want_chain = want_chain
+        self.fails = np.zeros((4, 3), int)
+        self.chain = 0
+        self.inherits_first_pass = self.falls_back_to_zero = 0
+
+    def __call__(self, st, k, rng):
+        for i in range(st.shape[0]):
+            r = _draws(9, k, i)
+            cmd = [r.uniform(0.0, 1.0) * self.cfg["Vx"], 0.0, r.uniform(-1.0, 1.0) * self.cfg["Omega"]]
+            st[i, S["CMD"]:S["CMD"] + 3] = cmd
+            st[i, S["CMDF"]:S["CMDF"] + 3] = cmd
+        return st
+
+    def count(self, k, r, d_o, so):
+        sign = np.array([1.0, -1.0, -1.0])                         # jointRef = (temp[0], -temp[1], -temp[2])
+        slot_of_bit = ((1, 0), (4, 1), (2, 2))                     # error bit -> temp[] slot
+        jr = so[:, S["JR"]:S["JR"] + 12].reshape(-1, 4, 3)
+        for i in range(len(d_o)):
+            for bit, j in slot_of_bit:
+                f = (r["err"][i] & bit) != 0
+                self.fails[:, j] += f
+                run = best = 0
+                for l in range(4):
+                    run = run + 1 if f[l] else 0
+                    best = max(best, run)
+                self.chain = max(self.chain, best)
+                if not f[0]:
+                    continue
+                if not d_o[i]:
+                    self.falls_back_to_zero += int(jr[i, 0, j] == 0.0)
+                    continue
+                # A reset (ENV:547-635) calls the gait generator twice at t0: with both passes -- the joints of the new state are that
+                # reference times 1 + 0.3 n, one shared draw n -- and once more with one pass (the JR of the state).  Both are recomputed
+                # here; `same` = the recomputed two-pass reference is the one the oracle's new joint angles were drawn around.
+                t0, cmdf, uph, dt = so[i, S["T0"]], so[i, S["CMDF"]:S["CMDF"] + 3], so[i, S["UPH"]], self.cfg["control_dt"]
+                two = O.gait_reference(self.cfg, cmdf, t0, True, up_height=uph)["jointRef"].reshape(4, 3)
+                first = O.gait_reference(self.cfg, cmdf, t0 - dt, False, up_height=uph)["jointRef"].reshape(4, 3)
+                q = so[i, S["GC"] + 7:S["GC"] + 19].reshape(4, 3)
+                big = np.abs(two) > 0.1
+                same = big.any() and np.ptp(q[big] / two[big]) < 1e-6
+                self.inherits_first_pass += int(same and first[3, j] != 0.0 and abs(two[0, j] - first[3, j]) < 1e-9)
+
+    def witness(self):
+        print("[gait_low_stance] failing slots per (leg, slot): %s; longest chain of consecutive legs failing one slot: %d (wanted %d); reset steps "
+              "in which leg 0 fails in the second pass and holds leg 3's first-pass value: %d; ordinary steps in which leg 0 fails and holds 0: %d"
+              % (self.fails.tolist(), self.chain, self.want_chain, self.inherits_first_pass, self.falls_back_to_zero))
+        assert self.fails.min() >= 1 and self.chain >= self.want_chain and self.inherits_first_pass >= 1 and self.falls_back_to_zero >= 1
+
+
+class gait_lateral(_gait_scenario):
+    """Vy 1.0, LeanFront 0.03, LeanHind -0.02, HeightVariable on, WILDCAT off: side_step, the `by` branch of the command draw, different
+    lean offsets front and hind and both branches of the variable swing height -- all dead in the shipped configurations.  The commands are
+    left to the envs' own draws.  Witness (oracle): a lateral command was drawn (CMD y != 0: only the `by` branch writes it), UPH took
+    up_height itself and ratio * up_height, and the EER y of a front and of the hind leg on the same side differ (the yaw step enters them
+    with opposite signs)."""
+
+    def __init__(self, orc, cand, cfg, assert_bounds=True):
+        _gait_scenario.__init__(self, orc, cand, cfg, assert_bounds)
+        self.by = self.uph_full = self.uph_scaled = self.front_hind = 0
+
+    def __call__(self, st, k, rng):
+        return st
+
+    def count(self, k, r, d_o, so):
+        self.by += int((so[:, S["CMD"] + 1] != 0.0).sum())
+        full = so[:, S["UPH"]] == float(self.cfg["up_height"])
+        self.uph_full += int(full.sum())
+        self.uph_scaled += int((~full & (so[:, S["UPH"]] < 0.1 * self.cfg["up_height"] * (1 + 1e-9))).sum())
+        eer = so[:, S["EER"]:S["EER"] + 12].reshape(-1, 4, 3)
+        self.front_hind += int((np.abs(eer[:, 0, 1] - eer[:, 2, 1]) > 1e-3).sum())
+
+    def witness(self):
+        print("[gait_lateral] env-steps with a lateral command: %d; with UPH = up_height: %d, = ratio * up_height: %d; with EER y of FR and HR more than 1 mm apart: %d"
+              % (self.by, self.uph_full, self.uph_scaled, self.front_hind))
+        assert self.by >= 1 and self.uph_full >= 1 and self.uph_scaled >= 1 and self.front_hind >= 1
+
+
 def check_free_running(make_orc, make_cand, cfg, preroll=90):
     """1, 8 and 400 substeps of free running (no re-synchronisation) from a common state in which the robots
     already stand / hop on the ground (reached by `preroll` oracle steps), BASELINE.md section 3.

@@ -47,8 +47,11 @@ def test_dynamics_probe_matches_oracle():
 
 
 def test_teacher_forced_train_cfg_with_noise_randomisation_and_resets():
-    orc, cand = _pair(load_env_cfg("default_cfg.yaml", num_envs=64))
-    worst, n_done = PL.check_teacher_forced(orc, cand, steps=150, force_terminal_every=5)
+    cfg = load_env_cfg("default_cfg.yaml", num_envs=64)
+    orc, cand = _pair(cfg)
+    task = PL.task_state_check(orc, cand, cfg)        # what the step's closing task logic leaves for the NEXT step
+    worst, n_done = PL.check_teacher_forced(orc, cand, steps=150, force_terminal_every=5, after_step=task.after_step)
+    task.report("train config")
     assert n_done >= 20
     print("teacher-forced worst errors:", worst)
 
@@ -58,7 +61,9 @@ def test_teacher_forced_eval_style_cfg():
                        MotorCriticalSpeed=14.2, MotorMaxSpeed=40, stand_height=0.30, ObsFilter=True, Filter=True,
                        TimeBasedContact=True, ActionNoise=0.1, SharedNoiseScalar=False)
     orc, cand = _pair(cfg)
-    PL.check_teacher_forced(orc, cand, steps=60, seed=2, force_terminal_every=9)
+    task = PL.task_state_check(orc, cand, cfg)
+    PL.check_teacher_forced(orc, cand, steps=60, seed=2, force_terminal_every=9, after_step=task.after_step)
+    task.report("eval-style config")
 
 
 def test_free_running_horizons_1_8_400_substeps():

@@ -1,6 +1,7 @@
 """The edge scenarios of test_kernel_source_edges_emulated.py through the C-ABI on an MI355X: the HIP kernels against the f64 oracle at
 long episode clocks, on the rim of the height field, on the sloped and crossed parts of the motor envelope, at the z > 0.65 m and tilt
-terminations and in the contact regimes (friction caps mixed inside one wave, 3-6 m/s slides, bouncing landings) -- both lane layouts, and for the scenarios on flat ground also a ContactSolver 1 pool (the run-time-solver kernels, variant
+terminations, in the contact regimes (friction caps mixed inside one wave, 3-6 m/s slides, bouncing landings) and in the gait generator's
+regimes (legs beyond reach, failing IK slots chained across legs and passes, lateral commands with lean) -- both lane layouts, and for the scenarios on flat ground also a ContactSolver 1 pool (the run-time-solver kernels, variant
 "md", instead of "shipped_flat").  Then the multi-step kernel's bit-identity with one launch per step, started FROM those states.
 Scenario hooks, witnesses and tolerances: parity_lib.py; nothing here is fitted to a GPU run."""
 import numpy as np
@@ -87,8 +88,28 @@ def test_bouncing_landings_on_gpu(monkeypatch, lanes, over, variant):
     EDGES.bouncing_landings_case(_maker(monkeypatch, lanes, variant), n=N, **over)
 
 
+@pytest.mark.parametrize("lanes,over,variant", POOLS, ids=POOL_IDS)
+@pytest.mark.parametrize("wildcat", [True, False], ids=["wildcat", "forward"])
+@pytest.mark.parametrize("key", sorted(EDGES.GAIT_REACH_CFGS))
+def test_gait_reach_on_gpu(monkeypatch, key, wildcat, lanes, over, variant):
+    """The task state (JR, JRL, JDR, EER, CMD, CMDF, UPH, T0, CONTACT) behind every step, legs beyond max_len in a quarter of the env-steps."""
+    EDGES.gait_reach_case(_maker(monkeypatch, lanes, variant), key, wildcat, n=N, **over)
+
+
+@pytest.mark.parametrize("lanes,over,variant", POOLS, ids=POOL_IDS)
+@pytest.mark.parametrize("gait_type", sorted(EDGES.LOW_STANCE_CFGS))
+def test_gait_low_stance_on_gpu(monkeypatch, gait_type, lanes, over, variant):
+    """Failing asin / acos slots: the shared temp[3] chain is three legs_bcast hand-offs (DPP) in the kernels."""
+    EDGES.gait_low_stance_case(_maker(monkeypatch, lanes, variant), gait_type, n=N, **over)
+
+
+@pytest.mark.parametrize("lanes,over,variant", POOLS, ids=POOL_IDS)
+def test_gait_lateral_on_gpu(monkeypatch, lanes, over, variant):
+    EDGES.gait_lateral_case(_maker(monkeypatch, lanes, variant), n=N, **over)
+
+
 @pytest.mark.parametrize("lanes", [16, 4])
-@pytest.mark.parametrize("scenario", ["clock", "corner", "motor"] + sorted(EDGES.CONTACT_SCENARIOS))
+@pytest.mark.parametrize("scenario", ["clock", "corner", "motor"] + sorted(EDGES.CONTACT_SCENARIOS) + sorted(EDGES.GAIT_SCENARIOS))
 def test_multi_step_kernel_equals_one_launch_per_step_from_edge_states(monkeypatch, scenario, lanes):
     """No new code runs here: the multi-step kernel's bit-identity with K step() calls (test_gpu_runtime_solver_persistent.py, from fresh
     pools) is started from states that claim has not seen -- frame 24 990, robots over the corner of the height field, joint rates beyond

@@ -1,7 +1,9 @@
 """The kernel source (csrc/env_core.hpp, through the host lane emulation, both lane layouts) against the f64 oracle in the regions
 that random actions from a fresh reset never reach -- long episode clocks, the rim of the height field, the sloped and crossed parts
 of the motor's torque-speed envelope, the z > 0.65 m and tilt terminations, and the contact regimes: the caps of the per-contact
-rules (frictionless, jamming corner) mixed with ordinary robots in one wave, slides at 3-6 m/s, landings that bounce.  Scenario hooks
+rules (frictionless, jamming corner) mixed with ordinary robots in one wave, slides at 3-6 m/s, landings that bounce, and the gait
+generator's regimes (legs beyond reach, failing IK slots chained across legs, lateral commands with lean), where the task state the step
+leaves for the next one is compared too.  Scenario hooks
 and their witnesses: parity_lib.py ("Edge scenarios"); the same scenarios through the C-ABI on an MI355X: test_gpu_parity_edges.py.  Tolerances: the unchanged TOL_STEP,
 TERRAIN_MAX_FACTOR on rough ground, and the derived 4 f32 ulps on base x / y where robots are moved to x = +-250 m."""
 import numpy as np
@@ -92,11 +94,70 @@ def bouncing_landings_case(make_cand, n=16, **over):
     return worst
 
 
+# ---- the gait generator's regimes (parity_lib.py "The task state"): n = 16, 40 steps, a forced reset every third step so that the
+# reset's two-pass call -- temp[] carried from the pass at t - control_dt into the pass at t -- is in every case ----
+GAIT_REACH_CFGS = {"Vx7.5": {"Vx": 7.5}, "period0.3": {"period": 0.3}}
+# GaitType -> (stand_height, lean front and hind, the chain length its witness asks for)
+LOW_STANCE_CFGS = {0: (0.11, 0.03, 2), 1: (0.12, 0.025, 2), 2: (0.115, 0.03, 1), 3: (0.11, 0.025, 4)}
+GAIT_LATERAL_CFG = dict(Vy=1.0, LeanFront=0.03, LeanHind=-0.02, HeightVariable=True, WILDCAT=False, Manual=False)
+
+
+def gait_reach_cfg(key, wildcat, n, **over):
+    return load_env_cfg("default_cfg.yaml", num_envs=n, **dict(GAIT_REACH_CFGS[key], WILDCAT=wildcat, **over))
+
+
+def gait_low_stance_cfg(gait_type, n, **over):
+    stand, lean, _ = LOW_STANCE_CFGS[gait_type]
+    return load_env_cfg("default_cfg.yaml", num_envs=n, **dict(dict(stand_height=stand, LeanFront=lean, LeanHind=lean, GaitType=gait_type), **over))
+
+
+def _gait_case(make_cand, cfg, hook_of, seed, name):
+    orc, cand = O.OracleVecEnv(cfg), make_cand(cfg)
+    hook = hook_of(orc, cand, cfg)
+    try:
+        worst, n_done = PL.check_teacher_forced(orc, cand, steps=STEPS, seed=seed, force_terminal_every=3, perturb=hook, after_step=hook.after_step)
+    finally:
+        if hook.task.env_steps:
+            hook.task.report(name)
+    hook.witness()
+    assert n_done >= STEPS // 3
+    return hook
+
+
+def gait_reach_case(make_cand, key, wildcat, n=16, assert_bounds=True, **over):
+    cfg = gait_reach_cfg(key, wildcat, n, **over)
+    return _gait_case(make_cand, cfg, lambda o, c, g: PL.gait_reach(o, c, g, assert_bounds), 8, "gait_reach %s WILDCAT %s" % (key, wildcat))
+
+
+def gait_low_stance_case(make_cand, gait_type, n=16, assert_bounds=True, **over):
+    cfg = gait_low_stance_cfg(gait_type, n, **over)
+    return _gait_case(make_cand, cfg, lambda o, c, g: PL.gait_low_stance(o, c, g, LOW_STANCE_CFGS[gait_type][2], assert_bounds), 9,
+                      "gait_low_stance GaitType %d" % gait_type)
+
+
+def gait_lateral_case(make_cand, n=16, assert_bounds=True, **over):
+    cfg = load_env_cfg("default_cfg.yaml", num_envs=n, **dict(GAIT_LATERAL_CFG, **over))
+    return _gait_case(make_cand, cfg, lambda o, c, g: PL.gait_lateral(o, c, g, assert_bounds), 10, "gait_lateral")
+
+
 CONTACT_SCENARIOS = {"friction_caps": PL.friction_caps, "fast_slide": PL.fast_slide, "bouncing_landings": PL.bouncing_landings}
+GAIT_SCENARIOS = ("gait_lateral", "gait_low_stance", "gait_reach")
 
 
 def edge_state(scenario, n):
     """-> (config, the f32-rounded state of an oracle pool after the scenario's step-0 perturbation): where the multi-step tests start"""
+    if scenario in GAIT_SCENARIOS:
+        if scenario == "gait_reach":
+            cfg = gait_reach_cfg("Vx7.5", True, n)
+            hook = PL.gait_reach(None, None, cfg)
+        elif scenario == "gait_low_stance":
+            cfg = gait_low_stance_cfg(3, n)
+            hook = PL.gait_low_stance(None, None, cfg, 4)
+        else:
+            cfg = load_env_cfg("default_cfg.yaml", num_envs=n, **GAIT_LATERAL_CFG)
+            hook = PL.gait_lateral(None, None, cfg)
+        orc = O.OracleVecEnv(cfg)
+        return cfg, PL.f32_round_state(hook(PL.f32_round_state(orc.get_state()), 0, None))
     if scenario in CONTACT_SCENARIOS:
         cfg = load_env_cfg("bp5_imitation.yaml", num_envs=n)
         orc = O.OracleVecEnv(cfg)
@@ -166,13 +227,34 @@ def test_bouncing_landings(emu, solver):
     bouncing_landings_case(emu, ContactSolver=solver)
 
 
-@pytest.mark.parametrize("scenario", ["clock", "corner", "motor"] + sorted(CONTACT_SCENARIOS))
+@pytest.mark.parametrize("emu", EMUS)
+@pytest.mark.parametrize("wildcat", [True, False], ids=["wildcat", "forward"])
+@pytest.mark.parametrize("key", sorted(GAIT_REACH_CFGS))
+def test_gait_reach_legs_beyond_max_len(emu, key, wildcat):
+    """Targets beyond reach are rescaled to max_len - 1e-5: JR and JDR there are held to the same bound as in reach.  Before the
+    constants of the straight leg (csrc/env_core.hpp IRRL_IK_REACH_*) the kernel source missed it several times over: JR 4.6e-5 to
+    6.6e-5 rad against a bound near 8e-6 there, from acos at 1 - 3.5e-5 in f32 (the oracle's own f32 build: 5.7e-5 rad); now 6.4e-7 rad."""
+    gait_reach_case(emu, key, wildcat)
+
+
+@pytest.mark.parametrize("emu", EMUS)
+@pytest.mark.parametrize("gait_type", sorted(LOW_STANCE_CFGS))
+def test_gait_low_stance_failing_slots_inherit_the_previous_leg(emu, gait_type):
+    gait_low_stance_case(emu, gait_type)
+
+
+@pytest.mark.parametrize("emu", EMUS)
+def test_gait_lateral_commands_lean_and_variable_swing_height(emu):
+    gait_lateral_case(emu)
+
+
+@pytest.mark.parametrize("scenario", ["clock", "corner", "motor"] + sorted(CONTACT_SCENARIOS) + sorted(GAIT_SCENARIOS))
 def test_carried_lane_context_equals_store_and_load_from_edge_states(scenario):
     """The host counterpart of test_multi_step_kernel_equals_one_launch_per_step_from_edge_states (test_gpu_parity_edges.py): 16 steps with
     the lane context carried in registers (sub-lanes 1-3 poisoned behind every step) == 16 step() calls, from frame 24 990, from over the
     corner of the height field, from joint rates beyond the motor's no-load speed and from the step-0 states of the three contact
     scenarios (mixed friction, 3-6 m/s slides, landings) -- every step's outputs and the final pool, bit for bit."""
-    n, K = (16 if scenario in CONTACT_SCENARIOS else 12), 16
+    n, K = (16 if scenario in CONTACT_SCENARIOS or scenario in GAIT_SCENARIOS else 12), 16
     cfg, st = edge_state(scenario, n)
     a, b = E.EmuVecEnv16(cfg), E.EmuVecEnv16(cfg)
     a.set_state(st)

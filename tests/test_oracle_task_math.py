@@ -90,6 +90,65 @@ def test_ik_stale_value_and_rescale():
     assert err & 1 and th[0] == 0.123
 
 
+LH, LT, LC = 0.085, 0.209, 0.2175
+MAX_LEN = math.sqrt(LH * LH + (LT + LC) ** 2)
+REACH_DIRECTIONS = [(0.33, -0.085, -0.27, True), (-0.33, 0.085, -0.27, False), (0.2, -0.12, -0.36, True), (0.0, 0.085, -0.42, False),
+                    (-0.38, -0.06, -0.2, True), (0.3, 0.15, -0.25, False)]
+
+
+def _on_sphere(d, r):
+    s = r / math.sqrt(d[0] ** 2 + d[1] ** 2 + d[2] ** 2)
+    return d[0] * s, d[1] * s, d[2] * s
+
+
+def test_ik_is_continuous_across_max_len():
+    """A target just beyond max_len gets the angles of the in-reach target 1e-5 m inside the limit on the same ray (that is what the rescale
+    is), and those differ from the angles AT the limit by no more than 1e-5 m times the conditioning there: the knee is acos of
+    t2 = -1 + 1e-5 and the hip acos of a2 = 1 - 1e-5 at the straight leg, so d angle / d r = (d arg / d r) / sqrt(1 - arg^2)."""
+    dlr = MAX_LEN / (LT + LC)                                             # d lr / d r at lr = l_thigh + l_calf
+    d_t2 = (LT + LC) / (LT * LC) * dlr
+    d_a2 = (1.0 / (2 * LT) - (LT * LT - LC * LC) / (2 * LT * (LT + LC) ** 2)) * dlr
+    cond = [0.0, d_a2 / math.sqrt(1 - (1 - 1e-5) ** 2) + 1.0 / LT, d_t2 / math.sqrt(1 - (1 - 1e-5) ** 2)]     # (asin(x / lr): below 1 / l_thigh here)
+    for d in REACH_DIRECTIONS:
+        right = d[3]
+        out, e0 = O.inverse_kinematics(*_on_sphere(d, MAX_LEN * (1 + 1e-9)), right)
+        same, e1 = O.inverse_kinematics(*_on_sphere(d, MAX_LEN - 1e-5), right)
+        at, e2 = O.inverse_kinematics(*_on_sphere(d, MAX_LEN * (1 - 1e-12)), right)
+        assert e0 == e1 == e2 == 0
+        np.testing.assert_allclose(out, same, atol=1e-9)
+        x, y, z = _on_sphere(d, MAX_LEN)
+        rho = math.hypot(y, z)                                             # abad: d theta0 / d rho = l_hip / (rho sqrt(rho^2 - l_hip^2)), d rho / d r <= 1
+        assert abs(out[0] - at[0]) <= 1e-5 * LH / (rho * math.sqrt(rho * rho - LH * LH)) * 1.01
+        for j in (1, 2):
+            jump = abs(out[j] - at[j])
+            assert 1e-4 < jump <= 1e-5 * cond[j], (d, j, jump, 1e-5 * cond[j])
+
+
+def test_ik_knee_is_constant_beyond_max_len_and_the_kernel_constants_are_its_values():
+    """Beyond reach the rescaled target lies on the sphere of radius max_len - 1e-5: lr, the knee angle and acos(a2) are constants of the
+    leg geometry.  csrc/env_core.hpp holds them as IRRL_IK_REACH_* (f32 conditioning of acos at 1 - 3.5e-5 costs 6e-5 rad otherwise):
+    recomputed here in f64 from their formulas and compared with the oracle's IK."""
+    import re
+    L = MAX_LEN - 1e-5
+    lr = math.sqrt(L * L - LH * LH)
+    th2 = -(3.1415926 - math.acos((LT * LT + LC * LC - lr * lr) / 2 / LT / LC + 1e-5))
+    acos_a2 = math.acos((lr * lr + LT * LT - LC * LC) / 2 / lr / LT - 1e-5)
+    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "high_speed_quadrupedal_locomotion_by_irrl_amd", "csrc", "env_core.hpp")).read()
+    for name, want in (("LR", lr), ("TH2", th2), ("ACOS_A2", acos_a2)):
+        m = re.search(r"#define IRRL_IK_REACH_%s \(?(-?[0-9.]+(?:e-?[0-9]+)?)f\)?" % name, src)
+        assert m, name
+        assert abs(float(m.group(1)) - want) < 1e-10, (name, m.group(1), want)
+        assert float(np.float32(float(m.group(1)))) == float(np.float32(want))
+    rng = np.random.RandomState(5)
+    for d in REACH_DIRECTIONS:
+        for r in [MAX_LEN * (1 + 1e-9), 0.44, 0.5] + list(rng.uniform(MAX_LEN, 1.0, 5)):
+            x, y, z = _on_sphere(d, r)
+            th, err = O.inverse_kinematics(x, y, z, d[3])
+            assert err == 0
+            assert abs(th[2] - th2) < 1e-9, (d, r, th[2], th2)
+            assert abs(th[1] + math.asin(x * L / r / lr) - acos_a2) < 1e-9, (d, r)
+
+
 def test_smooth_functions():
     lam = 0.5
     for ph in np.linspace(0, 0.999, 37):
