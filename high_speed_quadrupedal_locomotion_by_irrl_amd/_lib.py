@@ -102,7 +102,19 @@ SIGNATURES = {
     "irrl_lstm_eval_rollout_persistent": (C.c_int, [vp, C.c_int, C.c_longlong] + [C.c_int] * 3 + [vp] * 6 + [C.c_int] + [vp] * 8 + [vp] * 2 + [C.c_float] * 3
                                           + [fp, fp, C.c_int] + [vp] * 9 + [vp]),
     "irrl_lstm_eval_rollout_supports": (C.c_int, [vp, C.c_int]),
+    # both forms with a scenario: the same argument list with `const irrl_eval_scenario *` (EvalScenario below; None = NULL = the old call) in
+    # front of the stream
+    "irrl_lstm_eval_scenario": (C.c_int, [vp, C.c_int, C.c_longlong] + [C.c_int] * 3 + [vp] * 6 + [C.c_int] + [vp] * 8 + [vp] * 2 + [C.c_float] * 3
+                                + [fp, fp, C.c_int] + [vp] * 9 + [vp, vp]),
+    "irrl_lstm_eval_scenario_persistent": (C.c_int, [vp, C.c_int, C.c_longlong] + [C.c_int] * 3 + [vp] * 6 + [C.c_int] + [vp] * 8 + [vp] * 2 + [C.c_float] * 3
+                                           + [fp, fp, C.c_int] + [vp] * 9 + [vp, vp]),
 }
+
+
+class EvalScenario(C.Structure):
+    """struct irrl_eval_scenario of include/irrl_env.h (a HOST struct of scalars and device pointers); pass C.byref(...) or None"""
+    _fields_ = [("t0", C.c_longlong), ("cmd_rows", C.c_int), ("cmd_every", C.c_int), ("cmd_table", vp), ("stat_buckets", C.c_int), ("stat_every", C.c_int),
+                ("heading_ref", vp), ("heading_kp", vp), ("heading_ki", vp), ("heading_int", vp), ("heading_windup", C.c_float), ("heading_dt", C.c_float)]
 
 
 def load():

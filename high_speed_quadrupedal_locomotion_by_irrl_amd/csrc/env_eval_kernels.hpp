@@ -22,6 +22,13 @@
 //      statistics by the robot's lead lane (the sequence of additions per slot is the five-launch form's: the accumulators START from the
 //      caller's column),
 //   5. the raw-observation recorder out of X.
+// A scenario (irrl_lstm_eval_scenario_persistent; eval_elements.hpp) adds, in front of the conditioning: a new command row into EV_TG where the
+// row index changes and at k = 0; at a bucket boundary the accumulators go back to stats[b] and stats[b'] comes in (both conditions uniform for
+// the whole grid, so "start from the caller's column, same sequence of additions" holds per bucket); the heading hold of the wave's robots by
+// lanes 0 .. 3 out of a scratch of its own (hdl: quaternion | I | ref | kp | ki | element 2).  The pool's gc in memory is stale inside the loop
+// (the lane context lives in registers), so the robot's lead lane writes the FINAL lane's quaternion -- post-reset on a `done` -- into that scratch
+// in the Tail hook; in front of step 0 it is filled from the pool.  I is read once and written back once.  LDS: 158 080 B of 163 840 (157 504
+// before the scenario).
 // The critic is NOT run: the critic's half of lstm_state [N, 4 hid : 8 hid] and the `value` column of the work array are left untouched (the
 // actor never reads them, so calls of either form may follow each other).  HID 48, ob 35, act 12.
 __global__ void IRRL_ENV_BOUNDS
@@ -34,10 +41,14 @@ IRRL_RK(irrl_eval_persistent_kernel)(EnvParams P_, EnvState S_, float *ob, float
   typedef LstmWaveLds<HID> LAY;
   // the evaluator's part of a wave's scratch (floats)
   constexpr int EV_VH = 0, EV_AH = 140, EV_CM = 188, EV_DL = 200, EV_TG = 204, EV_FLOATS = 216;
+  // the scenario's heading hold, a wave's scratch of its own (an array of its own, so that the arrays above keep the LDS offsets they had):
+  // base quaternion [4][4] | I [4] | ref [4] | kp [4] | ki [4] | the actor's element 2 [4]
+  constexpr int EV_Q = 0, EV_HI = 16, EV_HR = 20, EV_HP = 24, EV_HK = 28, EV_HO = 32, HD_FLOATS = 36;
   __shared__ __attribute__((aligned(16))) float wsl[4][LAY::FLOATS];
   __shared__ __attribute__((aligned(16))) float evl[4][EV_FLOATS];
   __shared__ double stl[4][4 * NS];
   __shared__ float head_w[HID * 16];
+  __shared__ float hdl[4][HD_FLOATS];
   __shared__ __attribute__((aligned(16))) float lds_w[LstmWaveImage<HID>::FLOATS];      // the ACTOR's operands, [gate column][K] (policy_step.hpp)
   lstm_wave_image_stage<HID, 256>(a, lds_w);
   for (int i = (int)threadIdx.x; i < HID * a.act_dim; i += 256) head_w[i] = a.pi_w[i];
@@ -54,6 +65,7 @@ IRRL_RK(irrl_eval_persistent_kernel)(EnvParams P_, EnvState S_, float *ob, float
   irrl_plain::load_lane(P, S, env0_, leg0_, L, true);
   float *ws = wsl[wave_];
   float *es = evl[wave_];
+  float *hs = hdl[wave_];
   double *st = stl[wave_];
   // policy part: this lane's robot is l & 3, its unit inside a column group l >> 2
   const int pr_ = lane0_ & 3, pq_ = lane0_ >> 2;
@@ -100,12 +112,33 @@ IRRL_RK(irrl_eval_persistent_kernel)(EnvParams P_, EnvState S_, float *ob, float
       ws[LAY::REW + lane0_] = 0.0f;
       es[EV_DL + lane0_] = __int_as_float(ev.delay[e]);
     }
-    if (ev.stats)
-      for (int i = lane0_; i < 4 * NS; i += 64) {
-        const int r = i / NS, s = i - r * NS;
-        st[i] = (r < nrob_) ? ev.stats[(size_t)s * (size_t)a.N + (size_t)(e4_ + r)] : 0.0;
+    if (ev.heading_kp) {   // the heading hold's state and parameters; the base quaternion as the pool holds it in front of step 0
+      if (lane0_ < 16) {
+        const int e = (e4_ + (lane0_ >> 2) < a.N) ? e4_ + (lane0_ >> 2) : a.N - 1;
+        hs[EV_Q + lane0_] = ev.gc[(size_t)e * 19 + 3 + (lane0_ & 3)];
       }
+      if (lane0_ < 4) {
+        const int e = (e4_ + lane0_ < a.N) ? e4_ + lane0_ : a.N - 1;
+        hs[EV_HI + lane0_] = ev.heading_int[e]; hs[EV_HR + lane0_] = ev.heading_ref[e];
+        hs[EV_HP + lane0_] = ev.heading_kp[e]; hs[EV_HK + lane0_] = ev.heading_ki[e];
+      }
+    }
   }
+  // the statistics bucket of step 0: the accumulators start from the caller's column of THAT bucket (a bucket boundary inside the loop writes
+  // them back and loads the next bucket's, so the sequence of additions per bucket is the five-launch form's)
+  if (ev.stats) {
+    const int bucket0 = irrl_eval_stat_bucket(ev, irrl_eval_tau(ev, ev.t));
+    for (int i = lane0_; i < 4 * NS; i += 64) {
+      const int r = i / NS, s = i - r * NS;
+      st[i] = (r < nrob_) ? ev.stats[((size_t)bucket0 * NS + (size_t)s) * (size_t)a.N + (size_t)(e4_ + r)] : 0.0;
+    }
+  }
+  // which parts of a scenario the call has, in ONE scalar register for the whole loop: a step without a scenario then tests this word and loads
+  // none of the scenario's kernel arguments (a wave alone on its SIMD waits out every scalar load it cannot batch with others).  The row in EV_TG
+  // and the bucket in `st` are NOT carried from step to step: a step of a call with a scenario recomputes the previous step's from the kernel
+  // arguments, so that nothing but this word stays live across the env step for the scenario.  The scenario's
+  // blocks are marked unlikely: block placement and the register allocator's spill weights then favour the step without one.
+  const int scn_ = __builtin_amdgcn_readfirstlane((ev.cmd_table ? 1 : 0) | (ev.stat_buckets > 1 ? 2 : 0) | (ev.heading_kp ? 4 : 0));
   int slot_ = ev.slot;
   __syncthreads();   // the LDS image, the head weights and the wave's scratch have landed
   for (int k = 0; k < steps; k++) {
@@ -113,6 +146,40 @@ IRRL_RK(irrl_eval_persistent_kernel)(EnvParams P_, EnvState S_, float *ob, float
     asm volatile("" : "+v"(lane));     // (see irrl_rollout_persistent_kernel_l16: keeps the per-lane addresses inside the loop)
     const EvalArgs &ek = IRRL_PARAMS_REFRESH(ev);
     const size_t rowk = (size_t)ek.row + (size_t)k;
+    // ---- 0. the scenario, uniform for the whole grid: a new command row into EV_TG where the row index changes (and at k = 0); at a bucket
+    //         boundary the accumulators go back to their bucket and the next bucket's columns come in; the heading hold of the wave's robots ----
+    if (__builtin_expect((scn_ & 3) != 0, 0)) {
+      const long long tk = ek.t + (long long)k;
+      const long long tau = irrl_eval_tau(ek, tk), tau_before = irrl_eval_tau(ek, tk - 1);     // (tau_before is read for k > 0 only)
+      if (scn_ & 1) {
+        const int r = irrl_eval_cmd_row(ek, tau);
+        if (k == 0 || r != irrl_eval_cmd_row(ek, tau_before)) {
+          if (lane < nrob_ * 3) es[EV_TG + lane] = ek.cmd_table[((size_t)r * (size_t)ek.N + (size_t)e4_) * 3 + (size_t)lane];
+          PS_WAVE_SYNC();
+        }
+      }
+      if (k > 0 && ek.stats) {
+        const int b = irrl_eval_stat_bucket(ek, tau), b_before = irrl_eval_stat_bucket(ek, tau_before);
+        if (b != b_before) {
+          for (int i = lane; i < nrob_ * NS; i += 64) {
+            const int r = i / NS, s = i - r * NS;
+            const size_t col = (size_t)s * (size_t)ek.N + (size_t)(e4_ + r);
+            ek.stats[(size_t)b_before * NS * (size_t)ek.N + col] = st[i];
+            st[i] = ek.stats[(size_t)b * NS * (size_t)ek.N + col];
+          }
+          PS_WAVE_SYNC();
+        }
+      }
+    }
+    if (__builtin_expect((scn_ & 4) != 0, 0)) {
+      if (lane < nrob_) {
+        const float kp = hs[EV_HP + lane], ki = hs[EV_HK + lane];
+        if (irrl_eval_heading_on(kp, ki))
+          hs[EV_HO + lane] = irrl_eval_heading_element(ek, hs[EV_HR + lane], kp, ki, hs[EV_Q + lane * 4], hs[EV_Q + lane * 4 + 1], hs[EV_Q + lane * 4 + 2],
+                                                       hs[EV_Q + lane * 4 + 3], hs + EV_HI + lane);
+      }
+      PS_WAVE_SYNC();
+    }
     // ---- 1. conditioning: this lane's elements lane, lane + 64, lane + 128 of the wave's [4][35] ----
     {
       const size_t plane = (size_t)ek.N * 35;
@@ -122,8 +189,9 @@ IRRL_RK(irrl_eval_persistent_kernel)(EnvParams P_, EnvState S_, float *ob, float
         if (i < nrob_ * 35) {
           const int r = i / 35, j = i - r * 35;
           const size_t gi = (size_t)e4_ * 35 + (size_t)i;
-          const float o = irrl_eval_condition_element(ek, slot_, j, ws[LAY::X + i], ek.ring + gi, plane, __float_as_int(es[EV_DL + r]), es + EV_VH + i,
-                                                      es + EV_CM + r * 3 + j, es + EV_TG + r * 3 + j);
+          float o = irrl_eval_condition_element(ek, slot_, j, ws[LAY::X + i], ek.ring + gi, plane, __float_as_int(es[EV_DL + r]), es + EV_VH + i,
+                                                es + EV_CM + r * 3 + j, es + EV_TG + r * 3 + j);
+          if (__builtin_expect((scn_ & 4) != 0, 0) && j == 2 && irrl_eval_heading_on(hs[EV_HP + r], hs[EV_HK + r])) o = hs[EV_HO + r];   // the heading hold's element 2
           ws[LAY::X + i] = o;
           ek.obs_cond[gi] = o;
           if (ek.rec_obs_cond) ek.rec_obs_cond[rowk * plane + gi] = o;
@@ -180,6 +248,11 @@ IRRL_RK(irrl_eval_persistent_kernel)(EnvParams P_, EnvState S_, float *ob, float
                 if (ek.rec_done) ek.rec_done[rowk * N + e] = dn ? 1 : 0;
                 irrl_eval_env_epilogue(dn, es + EV_CM + rl_ * 3, ek.stats ? st + rl_ * NS : nullptr, (size_t)1, Lf.pos.z, Lf.qw, Lf.qx, Lf.qy, Lf.qz, Lf.vw.x,
                                        Lf.vw.y, Lf.vw.z, Lf.ww.x, Lf.ww.y, Lf.ww.z);
+                if (__builtin_expect((scn_ & 4) != 0, 0)) {   // the pool's gc in memory is stale inside the loop: the next step's heading hold reads the FINAL lane's quaternion here
+                  float *q = hs + EV_Q + rl_ * 4;
+                  q[0] = Lf.qw; q[1] = Lf.qx; q[2] = Lf.qy; q[3] = Lf.qz;
+                  irrl_eval_heading_epilogue(dn, hs + EV_HI + rl_);
+                }
               }
             }
           });
@@ -203,11 +276,14 @@ IRRL_RK(irrl_eval_persistent_kernel)(EnvParams P_, EnvState S_, float *ob, float
     for (int i = lane0_; i < nrob_ * 35; i += 64) ev.vel_his[(size_t)e4_ * 35 + i] = es[EV_VH + i];
     if (lane0_ < nrob_ * 12) ev.act_his[(size_t)e4_ * 12 + lane0_] = es[EV_AH + lane0_];
     if (lane0_ < nrob_ * 3) ev.cmd[(size_t)e4_ * 3 + lane0_] = es[EV_CM + lane0_];
-    if (ev.stats)
+    if (ev.heading_kp && lane0_ < nrob_) ev.heading_int[e4_ + lane0_] = hs[EV_HI + lane0_];
+    if (ev.stats) {
+      const int bucket1 = irrl_eval_stat_bucket(ev, irrl_eval_tau(ev, ev.t + (long long)(steps - 1)));     // the last step's bucket
       for (int i = lane0_; i < nrob_ * NS; i += 64) {
         const int r = i / NS, s = i - r * NS;
-        ev.stats[(size_t)s * (size_t)a.N + (size_t)(e4_ + r)] = st[i];
+        ev.stats[((size_t)bucket1 * NS + (size_t)s) * (size_t)a.N + (size_t)(e4_ + r)] = st[i];
       }
+    }
     if (pok_) {      // the actor's LSTM state behind the last step (the critic's half is not touched)
 #pragma unroll
       for (int G = 0; G < NG; G++) {

@@ -43,7 +43,16 @@ struct EvalArgs {
   // recorders, each may be NULL
   float *rec_obs_cond, *rec_act_clipped, *rec_act_applied, *rec_body, *rec_torque, *rec_obs_raw, *rec_reward;
   uint8_t *rec_done;
-  double *stats;     // [IRRL_EVAL_STAT_COUNT, N] or NULL
+  double *stats;     // [IRRL_EVAL_STAT_COUNT, N] or NULL; with a scenario [stat_buckets, IRRL_EVAL_STAT_COUNT, N]
+  // the scenario (irrl_eval_scenario, include/irrl_env.h); all zero / NULL = none: a value-initialised EvalArgs is the loop without one
+  long long t;       // global control step of this step (the persistent kernel: of its first step)
+  long long t0;      // the scenario's origin: tau = max(t - t0, 0)
+  int cmd_rows, cmd_every;          // the command schedule; read only where cmd_table is set
+  const float *cmd_table;           // [cmd_rows, N, 3] or NULL: cmd_target is the target
+  int stat_buckets, stat_every;     // stat_buckets < 1: one bucket
+  const float *heading_ref, *heading_kp, *heading_ki;   // [N] each, or all NULL: heading hold off
+  float *heading_int;               // [N] the integrator I
+  float heading_windup, heading_dt;
 };
 
 // steps 1-6 of a control step for ONE element (env e, component j) of the observation: ring[slot] = raw, the delayed read, the rate low-pass,
@@ -108,4 +117,41 @@ static inline IRRL_EVAL_FN void irrl_eval_env_epilogue(bool dn, float *cmd_e, do
   s[IRRL_EVAL_STAT_VY * n] += vy;
   s[IRRL_EVAL_STAT_WZ * n] += o2;
   s[IRRL_EVAL_STAT_FALLS * n] += dn ? 1.0 : 0.0;
+}
+
+// ---- the scenario: command schedule, heading hold, statistics buckets ----
+// tau of control step t: steps since the scenario's origin, 0 in front of it
+static inline IRRL_EVAL_FN long long irrl_eval_tau(const EvalArgs &a, long long t) { return t > a.t0 ? t - a.t0 : 0; }
+// the row of cmd_table that step tau reads: min(tau / cmd_every, cmd_rows - 1) -- the last row holds once the table runs out
+static inline IRRL_EVAL_FN int irrl_eval_cmd_row(const EvalArgs &a, long long tau) {
+  const long long r = tau / (long long)a.cmd_every;
+  return r < (long long)(a.cmd_rows - 1) ? (int)r : a.cmd_rows - 1;
+}
+// the bucket of `stats` the frame of step tau is added to: min(tau / stat_every, stat_buckets - 1); no buckets (< 1): 0
+static inline IRRL_EVAL_FN int irrl_eval_stat_bucket(const EvalArgs &a, long long tau) {
+  if (a.stat_buckets < 1) return 0;
+  const long long b = tau / (long long)a.stat_every;
+  return b < (long long)(a.stat_buckets - 1) ? (int)b : a.stat_buckets - 1;
+}
+// is the heading hold on for an env with these gains
+static inline IRRL_EVAL_FN bool irrl_eval_heading_on(float kp, float ki) { return kp != 0.0f || ki != 0.0f; }
+// Heading hold for ONE env (run_bp_v5.py:308-315, 400-406: a PI loop on the base yaw of utils/Rotation.py:8 whose output replaces the yaw-rate
+// command the actor sees).  The reference's utils/PID.py is not in its tree; the rule here is the common positional PID with Kd = 0 and an
+// integrator clamp: err = wrap(ref - yaw) into [-pi, pi), I = clamp(I + err dt, -W, W), out = kp err + ki I.  w x y z: the base quaternion as the
+// pool holds it at conditioning time (the state after the previous step, or after the reset; not delayed).  *I_e is updated.
+// -> the actor's element 2, (out - mean2) / std2.  f32, every statement ONE expression (see the note on -ffp-contract at the top).
+static inline IRRL_EVAL_FN float irrl_eval_heading_element(const EvalArgs &a, float ref, float kp, float ki, float w, float x, float y, float z, float *I_e) {
+  const float pi = 3.14159265358979323846f, two_pi = 6.28318530717958647692f;
+  const float yaw = atan2f(2.0f * (w * z + x * y), 1.0f - 2.0f * (y * y + z * z));
+  const float d = ref - yaw;
+  float err = d - two_pi * floorf((d + pi) / two_pi);
+  err = err >= pi ? err - two_pi : err < -pi ? err + two_pi : err;       // (the rounding of the line above can leave the interval by an ulp)
+  const float I = fminf(fmaxf(*I_e + err * a.heading_dt, -a.heading_windup), a.heading_windup);
+  *I_e = I;
+  const float out = kp * err + ki * I;
+  return (out - a.mean2) / a.std2;
+}
+// after the env step: the env restarted from rest, so does its integrator
+static inline IRRL_EVAL_FN void irrl_eval_heading_epilogue(bool dn, float *I_e) {
+  if (dn) *I_e = 0.0f;
 }

@@ -8,6 +8,9 @@
 //   3. irrl_eval_action_kernel      action low-pass, act_his, the action buffer the env step reads
 //   4. the env step                 (launch_step of irrl_env_abi.hip: whatever kernel variant and lane layout the pool runs)
 //   5. irrl_eval_record_kernel      recorders, cmd = 0 on done, per-env f64 statistics
+// With a scenario (irrl_lstm_eval_scenario: the <true> instantiations of kernels 1 and 5) kernel 1 takes the command target from the step's row of
+// the command table and runs the heading hold in lane (e, 2), which owns I_e and reads the base quaternion from the pool's gc; kernel 5 zeroes I_e
+// on done and adds the frame into the step's statistics bucket.
 // A filter coefficient of exactly 1.0f switches that filter OFF (the value passes through bit for bit).  The ring and the two filter histories
 // survive an in-episode `done`, as they do in the reference script.
 // The per-element arithmetic lives in eval_elements.hpp, ONE text shared with the persistent single-launch form of the same loop
@@ -20,13 +23,26 @@
 #include "eval_elements.hpp"   // struct EvalArgs and the per-element functions
 
 // steps 1-6 of a control step: a lane per (env, element), so every access to the [D][N][35] ring and to the [N, 35] arrays is coalesced; a lane
-// only ever touches its own column of the ring
+// only ever touches its own column of the ring.  SCN: the call has a scenario (irrl_lstm_eval_scenario); the instantiation without one is the loop
+// as it was, instruction for instruction
+template <bool SCN>
 __global__ void __launch_bounds__(256) irrl_eval_condition_kernel(const EvalArgs a) {
   const int i = (int)(blockIdx.x * 256u + threadIdx.x);
   if (i >= a.N * 35) return;
   const int e = i / 35, j = i - e * 35;
   const size_t plane = (size_t)a.N * 35;
-  const float o = irrl_eval_condition_element(a, a.slot, j, a.obs[i], a.ring + i, plane, a.delay[e], a.vel_his + i, a.cmd + e * 3 + j, a.cmd_target + e * 3 + j);
+  // the scenario's command schedule: lane (e, j < 3) reads its word of this step's table row in place of cmd_target
+  const float *target = a.cmd_target + e * 3 + j;
+  if (SCN && a.cmd_table && j < 3) target = a.cmd_table + ((size_t)irrl_eval_cmd_row(a, irrl_eval_tau(a, a.t)) * (size_t)a.N + (size_t)e) * 3 + j;
+  float o = irrl_eval_condition_element(a, a.slot, j, a.obs[i], a.ring + i, plane, a.delay[e], a.vel_his + i, a.cmd + e * 3 + j, target);
+  // the heading hold: lane (e, 2) owns I_e; the base quaternion is the pool's (the state after the previous step or the reset)
+  if (SCN && a.heading_kp && j == 2) {
+    const float kp = a.heading_kp[e], ki = a.heading_ki[e];
+    if (irrl_eval_heading_on(kp, ki)) {
+      const float *q = a.gc + e * 19 + 3;
+      o = irrl_eval_heading_element(a, a.heading_ref[e], kp, ki, q[0], q[1], q[2], q[3], a.heading_int + e);
+    }
+  }
   a.obs_cond[i] = o;
   if (a.rec_obs_cond) a.rec_obs_cond[(size_t)a.row * plane + (size_t)i] = o;
 }
@@ -45,6 +61,7 @@ __global__ void __launch_bounds__(256) irrl_eval_action_kernel(const EvalArgs a)
 
 // steps 12-13, after the env step: the recorders (a lane per element of the widest one), and in the lanes e < N the command reset and the
 // statistics -- one lane owns env e's column of `stats`, no atomics
+template <bool SCN>
 __global__ void __launch_bounds__(256) irrl_eval_record_kernel(const EvalArgs a) {
   const int i = (int)(blockIdx.x * 256u + threadIdx.x);
   const int N = a.N;
@@ -62,7 +79,10 @@ __global__ void __launch_bounds__(256) irrl_eval_record_kernel(const EvalArgs a)
   if (a.rec_reward) a.rec_reward[row * (size_t)N + (size_t)e] = a.reward[e];
   if (a.rec_done) a.rec_done[row * (size_t)N + (size_t)e] = dn;
   const float *gc = a.gc + e * 19, *gv = a.gv + e * 18;
-  irrl_eval_env_epilogue(dn != 0, a.cmd + e * 3, a.stats ? a.stats + e : nullptr, (size_t)N, gc[2], gc[3], gc[4], gc[5], gc[6], gv[0], gv[1], gv[2], gv[3], gv[4], gv[5]);
+  if (SCN && a.heading_int) irrl_eval_heading_epilogue(dn != 0, a.heading_int + e);
+  // the frame goes to this step's bucket of the statistics (no scenario: bucket 0, the whole buffer)
+  const size_t bucket = SCN ? (size_t)irrl_eval_stat_bucket(a, irrl_eval_tau(a, a.t)) * (size_t)IRRL_EVAL_STAT_COUNT * (size_t)N : (size_t)0;
+  irrl_eval_env_epilogue(dn != 0, a.cmd + e * 3, a.stats ? a.stats + bucket + e : nullptr, (size_t)N, gc[2], gc[3], gc[4], gc[5], gc[6], gv[0], gv[1], gv[2], gv[3], gv[4], gv[5]);
 }
 
 static inline dim3 eval_grid(int n_elems) { return dim3((unsigned)((n_elems + 255) / 256)); }

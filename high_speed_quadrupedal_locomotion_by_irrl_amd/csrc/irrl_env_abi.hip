@@ -527,7 +527,7 @@ static EvalArgs eval_args(const irrl_env *h, const EvalWork &w, int depth, float
                           const int *delay, const float *cmd_target, float a_cmd, float a_vel, float a_act, const float *cmd_mean, const float *cmd_std, int clip,
                           float *rec_obs_cond, float *rec_act_clipped, float *rec_act_applied, float *rec_body, float *rec_torque, float *rec_obs_raw,
                           float *rec_reward, uint8_t *rec_done, double *stats) {
-  EvalArgs a;
+  EvalArgs a = EvalArgs();     // (the scenario's fields: none)
   a.N = h->P.n_envs; a.D = depth; a.slot = 0; a.steps = 0; a.clip = clip; a.row = 0;
   a.ring = ring; a.cmd = cmd; a.vel_his = vel_his; a.act_his = act_his; a.obs = obs; a.done = done;
   a.delay = delay; a.cmd_target = cmd_target;
@@ -539,14 +539,48 @@ static EvalArgs eval_args(const irrl_env *h, const EvalWork &w, int depth, float
   a.rec_torque = rec_torque; a.rec_obs_raw = rec_obs_raw; a.rec_reward = rec_reward; a.rec_done = rec_done; a.stats = stats;
   return a;
 }
-int irrl_lstm_eval_rollout(irrl_env *h, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *lstm_w, const float *pi_w,
-                           const float *pi_b, const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring, float *cmd, float *vel_his,
-                           float *act_his, float *lstm_state, uint8_t *done, float *obs, float *work, const int *delay, const float *cmd_target, float a_cmd,
-                           float a_vel, float a_act, const float *cmd_mean, const float *cmd_std, int clip, float *rec_obs_cond, float *rec_act_clipped,
-                           float *rec_act_applied, float *rec_body, float *rec_torque, float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats,
-                           void *hip_stream) {
-  if (eval_rollout_check("irrl_lstm_eval_rollout", h, steps, step0, hid, ob_dim, act_dim, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, depth, ring, cmd, vel_his, act_his,
+// the scenario of irrl_lstm_eval_scenario[_persistent] (include/irrl_env.h): refused before any HIP call; NULL = none
+static int eval_scenario_check(const char *who, const irrl_eval_scenario *sc) {
+  if (!sc) return 0;
+  const std::string w = std::string(who) + ": scenario: ";
+  if (sc->cmd_rows < 1 || sc->cmd_every < 1) { g_err = w + "cmd_rows >= 1, cmd_every >= 1"; return 1; }
+  if (!sc->cmd_table) { g_err = w + "NULL cmd_table"; return 1; }
+  if (sc->stat_buckets < 1 || sc->stat_every < 1) { g_err = w + "stat_buckets >= 1, stat_every >= 1"; return 1; }
+  const int given = (sc->heading_ref ? 1 : 0) + (sc->heading_kp ? 1 : 0) + (sc->heading_ki ? 1 : 0);
+  if (given != 0 && given != 3) { g_err = w + "heading_ref, heading_kp, heading_ki are all given or all NULL"; return 1; }
+  if (given == 3) {
+    if (!sc->heading_int) { g_err = w + "the heading hold needs its integrator state heading_int"; return 1; }
+    if (!(sc->heading_windup >= 0.0f)) { g_err = w + "heading_windup >= 0"; return 1; }
+    if (!(sc->heading_dt > 0.0f)) { g_err = w + "heading_dt > 0"; return 1; }
+  }
+  return 0;
+}
+static void eval_scenario_args(EvalArgs &a, const irrl_eval_scenario *sc, long long step0) {
+  a.t = step0;
+  if (!sc) return;
+  a.t0 = sc->t0;
+  a.cmd_rows = sc->cmd_rows; a.cmd_every = sc->cmd_every; a.cmd_table = sc->cmd_table;
+  a.stat_buckets = sc->stat_buckets; a.stat_every = sc->stat_every;
+  if (sc->heading_kp) {
+    a.heading_ref = sc->heading_ref; a.heading_kp = sc->heading_kp; a.heading_ki = sc->heading_ki; a.heading_int = sc->heading_int;
+    a.heading_windup = sc->heading_windup; a.heading_dt = sc->heading_dt;
+  }
+}
+// the argument list the four evaluation entry points share, and its forwarding
+#define IRRL_EVAL_PARAMS                                                                                                                              \
+  irrl_env *h, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *lstm_w, const float *pi_w, const float *pi_b,        \
+      const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring, float *cmd, float *vel_his, float *act_his, float *lstm_state, \
+      uint8_t *done, float *obs, float *work, const int *delay, const float *cmd_target, float a_cmd, float a_vel, float a_act, const float *cmd_mean,  \
+      const float *cmd_std, int clip, float *rec_obs_cond, float *rec_act_clipped, float *rec_act_applied, float *rec_body, float *rec_torque,         \
+      float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats
+#define IRRL_EVAL_FORWARD                                                                                                                              \
+  h, steps, step0, hid, ob_dim, act_dim, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, depth, ring, cmd, vel_his, act_his, lstm_state, done, obs, work, delay, \
+      cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std, clip, rec_obs_cond, rec_act_clipped, rec_act_applied, rec_body, rec_torque, rec_obs_raw,       \
+      rec_reward, rec_done, stats
+static int eval_rollout_steps(const char *who, IRRL_EVAL_PARAMS, const irrl_eval_scenario *sc, void *hip_stream) {
+  if (eval_rollout_check(who, h, steps, step0, hid, ob_dim, act_dim, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, depth, ring, cmd, vel_his, act_his,
                          lstm_state, done, obs, work, delay, cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std)) return 1;
+  if (eval_scenario_check(who, sc)) return 1;
   if (need_init(h)) return 1;
   HIP_TRY(hipSetDevice(h->device));
   h->stream = (hipStream_t)hip_stream;
@@ -554,20 +588,28 @@ int irrl_lstm_eval_rollout(irrl_env *h, int steps, long long step0, int hid, int
   const EvalWork w = eval_work(work, (size_t)n);
   EvalArgs a = eval_args(h, w, depth, ring, cmd, vel_his, act_his, done, obs, delay, cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std, clip, rec_obs_cond,
                          rec_act_clipped, rec_act_applied, rec_body, rec_torque, rec_obs_raw, rec_reward, rec_done, stats);
+  eval_scenario_args(a, sc, step0);
   for (int k = 0; k < steps; k++) {
     a.slot = (int)((step0 + k) % depth);
     a.row = k;
-    hipLaunchKernelGGL(irrl_eval_condition_kernel, eval_grid(n * 35), dim3(256), 0, h->stream, a);
+    a.t = step0 + k;
+    hipLaunchKernelGGL(sc ? irrl_eval_condition_kernel<true> : irrl_eval_condition_kernel<false>, eval_grid(n * 35), dim3(256), 0, h->stream, a);
     if (irrl_lstm_policy_step(hid, ob_dim, act_dim, n, w.obs_cond, done, lstm_state, lstm_state, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, nullptr, 0, 0u, 0, nullptr, 0,
                               w.action, w.clipped, w.value, w.neglogp, -1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, hip_stream) != 0) {
-      g_err = "irrl_lstm_eval_rollout: policy step refused its arguments"; return 1;
+      g_err = std::string(who) + ": policy step refused its arguments"; return 1;
     }
     hipLaunchKernelGGL(irrl_eval_action_kernel, eval_grid(n * 12), dim3(256), 0, h->stream, a);
     launch_step(h, h->P, (const float *)w.applied, obs, w.reward, done, w.extra);
-    hipLaunchKernelGGL(irrl_eval_record_kernel, eval_grid(n * 35), dim3(256), 0, h->stream, a);
+    hipLaunchKernelGGL(sc ? irrl_eval_record_kernel<true> : irrl_eval_record_kernel<false>, eval_grid(n * 35), dim3(256), 0, h->stream, a);
   }
   HIP_TRY(hipGetLastError());
   return 0;
+}
+int irrl_lstm_eval_rollout(IRRL_EVAL_PARAMS, void *hip_stream) {
+  return eval_rollout_steps("irrl_lstm_eval_rollout", IRRL_EVAL_FORWARD, nullptr, hip_stream);
+}
+int irrl_lstm_eval_scenario(IRRL_EVAL_PARAMS, const irrl_eval_scenario *scenario, void *hip_stream) {
+  return eval_rollout_steps("irrl_lstm_eval_scenario", IRRL_EVAL_FORWARD, scenario, hip_stream);
 }
 
 // THE SAME LOOP AS ONE PERSISTENT LAUNCH (csrc/env_eval_kernels.hpp: a wave keeps its four robots for all `steps`): exists where the actor-wave
@@ -578,15 +620,10 @@ int irrl_lstm_eval_rollout_supports(irrl_env *h, int hid) {
   if (!h) { g_err = "irrl_lstm_eval_rollout_supports: NULL handle"; return -1; }
   return rollout_one_tile(h, hid) ? 1 : 0;
 }
-int irrl_lstm_eval_rollout_persistent(irrl_env *h, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *lstm_w, const float *pi_w,
-                                      const float *pi_b, const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring, float *cmd,
-                                      float *vel_his, float *act_his, float *lstm_state, uint8_t *done, float *obs, float *work, const int *delay,
-                                      const float *cmd_target, float a_cmd, float a_vel, float a_act, const float *cmd_mean, const float *cmd_std, int clip,
-                                      float *rec_obs_cond, float *rec_act_clipped, float *rec_act_applied, float *rec_body, float *rec_torque, float *rec_obs_raw,
-                                      float *rec_reward, uint8_t *rec_done, double *stats, void *hip_stream) {
-  static const char *const who = "irrl_lstm_eval_rollout_persistent";
+static int eval_rollout_one_launch(const char *who, IRRL_EVAL_PARAMS, const irrl_eval_scenario *sc, void *hip_stream) {
   if (eval_rollout_check(who, h, steps, step0, hid, ob_dim, act_dim, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, depth, ring, cmd, vel_his, act_his, lstm_state, done,
                          obs, work, delay, cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std)) return 1;
+  if (eval_scenario_check(who, sc)) return 1;
   if (need_init(h)) return 1;
   // which condition keeps the kernel from this pool / network (settings only: nothing is launched)
   if (hid != 48) { g_err = std::string(who) + ": the persistent kernel exists for hid 48 only (this policy has hid " + std::to_string(hid) + ")"; return 1; }
@@ -604,6 +641,7 @@ int irrl_lstm_eval_rollout_persistent(irrl_env *h, int steps, long long step0, i
   const EvalWork w = eval_work(work, (size_t)n);
   EvalArgs a = eval_args(h, w, depth, ring, cmd, vel_his, act_his, done, obs, delay, cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std, clip, rec_obs_cond,
                          rec_act_clipped, rec_act_applied, rec_body, rec_torque, rec_obs_raw, rec_reward, rec_done, stats);
+  eval_scenario_args(a, sc, step0);
   a.slot = (int)(step0 % depth);
   a.steps = steps;
   // the actor alone, deterministic, no rollout rows: `value` and the critic's half of lstm_state are not written
@@ -612,6 +650,12 @@ int irrl_lstm_eval_rollout_persistent(irrl_env *h, int steps, long long step0, i
   hipLaunchKernelGGL(kEvalKernels[rk == &kRolloutKernels[0] ? 0 : 1], dim3((n + 15) / 16), dim3(256), 0, h->stream, h->P, h->S, obs, w.reward, done, w.extra, pa, a);
   HIP_TRY(hipGetLastError());
   return 0;
+}
+int irrl_lstm_eval_rollout_persistent(IRRL_EVAL_PARAMS, void *hip_stream) {
+  return eval_rollout_one_launch("irrl_lstm_eval_rollout_persistent", IRRL_EVAL_FORWARD, nullptr, hip_stream);
+}
+int irrl_lstm_eval_scenario_persistent(IRRL_EVAL_PARAMS, const irrl_eval_scenario *scenario, void *hip_stream) {
+  return eval_rollout_one_launch("irrl_lstm_eval_scenario_persistent", IRRL_EVAL_FORWARD, scenario, hip_stream);
 }
 
 // irrl_mlp_rollout_supports: which `fuse` modes exist for this pool (the twin of irrl_lstm_rollout_supports; fuse 2 falls back inside the call)

@@ -16,6 +16,12 @@ Semantics of control step t (global counter, carried across `run` calls), per en
    a = actor(o) (deterministic, clipped; LSTM state reset where `done`);  a = (1 - a_act) act_his + a_act a;  act_his = a;
    env.step(a);  record;  cmd = 0 where done.
 a = 2 pi dt f / (2 pi dt f + 1); f None or <= 0 means "filter off" (a = 1 exactly, the value passes unchanged).
+
+A scenario (PolicyEvaluator.set_scenario; the keywords of condition / reference_rollout; robustness_sweep's levels / heading), with
+tau = max(t - t0, 0): cmd_target of step t is row min(tau // cmd_every, S - 1) of a command table (staircase_schedule: the script's `--step`);
+the heading hold (heading_hold: the script's `--dir_fd`) replaces o[2] by the scaled output of a PI loop on the base yaw in front of the step,
+err = wrap(ref - yaw), I = clip(I + err dt, -W, W), out = kp err + ki I, I = 0 where done; the frame of step t goes to statistics bucket
+min(tau // stat_every, B - 1).
 """
 import ctypes as C
 import math
@@ -81,18 +87,83 @@ def _delay_rows(delay, n, depth=None):
     return d, depth
 
 
+# ---- the scenario: command schedule, heading hold (run_bp_v5.py:383-388 `--step`, :308-315 / :400-406 `--dir_fd`) ----
+def _schedule_rows(cmd_schedule, n):
+    """[S, n] forward-velocity commands or [S, n, 3] -> [S, n, 3] float64"""
+    c = np.asarray(cmd_schedule, np.float64)
+    if c.ndim == 2:
+        c = np.stack([c, np.zeros_like(c), np.zeros_like(c)], 2)
+    if c.ndim != 3 or c.shape[0] < 1 or c.shape[1:] != (n, 3):
+        raise ValueError("cmd_schedule must have shape (S, %d) or (S, %d, 3) with S >= 1" % (n, n))
+    return c
+
+
+def staircase_schedule(cmds, levels=4):
+    """the script's command staircase (run_bp_v5.py:383-388: `(t // 5000 + 1) / 4 * cmd`): cmds [n] or [n, 3] -> [levels, n, 3], row l =
+    (l + 1) / levels * cmd; held `cmd_every` control steps per row by the caller"""
+    levels = int(levels)
+    if levels < 1:
+        raise ValueError("levels >= 1")
+    c = np.asarray(cmds, np.float64)
+    c = _cmd_rows(c, c.shape[0] if c.ndim else 1)
+    return np.stack([(l + 1) / levels * c for l in range(levels)], 0)
+
+
+def yaw_from_quaternion(q):
+    """q [..., 4] = w x y z -> yaw (utils/Rotation.py:8): atan2(2 (w z + x y), 1 - 2 (y^2 + z^2))"""
+    q = np.asarray(q, np.float64)
+    w, x, y, z = q[..., 0], q[..., 1], q[..., 2], q[..., 3]
+    return np.arctan2(2 * (w * z + x * y), 1 - 2 * (y * y + z * z))
+
+
+def wrap_angle(a):
+    """into [-pi, pi)"""
+    a = np.asarray(a, np.float64)
+    return a - 2 * np.pi * np.floor((a + np.pi) / (2 * np.pi))
+
+
+def heading_hold(n, ref=0.0, kp=1.0, ki=0.1, windup=None):
+    """the heading hold of `n` envs: ref / kp / ki a scalar or [n] each (the reference's gains, run_bp_v5.py:311-313), windup the integrator's
+    clamp (None: the config's Omega).  An env with kp == ki == 0 runs without it."""
+    return dict(ref=np.broadcast_to(np.asarray(ref, np.float64), (n,)).copy(), kp=np.broadcast_to(np.asarray(kp, np.float64), (n,)).copy(),
+                ki=np.broadcast_to(np.asarray(ki, np.float64), (n,)).copy(), windup=windup)
+
+
+def heading_parameters(heading, n, omega, dt):
+    """a `heading` dict (ref, kp, ki scalars or [n]; windup, dt optional) -> the same with [n] float64 arrays, windup and dt filled in"""
+    if heading is None:
+        return None
+    h = heading_hold(n, heading.get("ref", 0.0), heading.get("kp", 1.0), heading.get("ki", 0.1), heading.get("windup"))
+    h["windup"] = float(omega if h["windup"] is None else h["windup"])
+    h["dt"] = float(heading.get("dt") or dt)
+    if h["windup"] < 0 or not h["dt"] > 0:
+        raise ValueError("heading: windup >= 0 and dt > 0")
+    return h
+
+
+def schedule_row(t, t0, every, rows):
+    """min(max(t - t0, 0) // every, rows - 1): the row of a command table / the statistics bucket of control step t"""
+    return min(max(int(t) - int(t0), 0) // int(every), int(rows) - 1)
+
+
 # ---- numpy float64 twin ----
 def condition_state(ob0, depth):
-    """state of `condition` after a reset: the reset observation fills the whole delay line, command and history are zero"""
+    """state of `condition` after a reset: the reset observation fills the whole delay line, command, history and heading integrator are zero"""
     ob0 = np.asarray(ob0, np.float64)
-    return dict(ring=np.repeat(ob0[None], int(depth), 0), cmd=np.zeros((ob0.shape[0], 3)), vel_his=np.zeros_like(ob0))
+    return dict(ring=np.repeat(ob0[None], int(depth), 0), cmd=np.zeros((ob0.shape[0], 3)), vel_his=np.zeros_like(ob0), heading_int=np.zeros(ob0.shape[0]),
+                heading_out=np.zeros(ob0.shape[0]))
 
 
-def condition(state, t, obs, delay, cmd_target, a_cmd, a_vel, mean3, std3):
-    """steps 1-6 of control step `t` for a batch: obs [n, 35] raw observation -> what the actor sees.  Updates `state` in place."""
+def condition(state, t, obs, delay, cmd_target, a_cmd, a_vel, mean3, std3, *, cmd_schedule=None, cmd_every=1, heading=None, t0=0, yaw=None):
+    """steps 1-6 of control step `t` for a batch: obs [n, 35] raw observation -> what the actor sees.  Updates `state` in place.
+    cmd_schedule [S, n, 3] / cmd_every / t0: the target is the schedule's row schedule_row(t, t0, cmd_every, S) in place of cmd_target.
+    heading (a dict of [n] ref, kp, ki and windup, dt) with yaw [n], the base yaw in front of the step: element 2 of the envs with a non-zero gain
+    is the scaled PI output, state["heading_int"] the integrator, state["heading_out"] the output (0 where off)."""
     ring = state["ring"]
     depth = ring.shape[0]
     rows = np.arange(ring.shape[1])
+    if cmd_schedule is not None:
+        cmd_target = np.asarray(cmd_schedule, np.float64)[schedule_row(t, t0, cmd_every, len(cmd_schedule))]
     state["cmd"] = (1 - a_cmd) * state["cmd"] + a_cmd * cmd_target if a_cmd != 1.0 else np.array(cmd_target, np.float64)
     ring[t % depth] = np.asarray(obs, np.float64)
     o = ring[(t - np.asarray(delay)) % depth, rows].copy()
@@ -101,22 +172,36 @@ def condition(state, t, obs, delay, cmd_target, a_cmd, a_vel, mean3, std3):
         o[:, 17:29] = (1 - a_vel) * state["vel_his"][:, 17:29] + a_vel * o[:, 17:29]
     state["vel_his"] = o.copy()
     o[:, 0:3] = (state["cmd"] - mean3) / std3
+    if heading is not None:
+        on = (heading["kp"] != 0) | (heading["ki"] != 0)
+        err = wrap_angle(heading["ref"] - np.asarray(yaw, np.float64))
+        integ = np.clip(state["heading_int"] + err * heading["dt"], -heading["windup"], heading["windup"])
+        out = heading["kp"] * err + heading["ki"] * integ
+        state["heading_int"] = np.where(on, integ, state["heading_int"])
+        state["heading_out"] = np.where(on, out, 0.0)
+        o[on, 2] = (out[on] - mean3[2]) / std3[2]
     return o
 
 
-def reference_rollout(env, actor, env_cfg, delay, cmd, steps, cmd_hz=1.0, vel_hz=None, act_hz=None, mu=None, warm=0, mu_warm=0.8, depth=None):
+def reference_rollout(env, actor, env_cfg, delay, cmd, steps, cmd_hz=1.0, vel_hz=None, act_hz=None, mu=None, warm=0, mu_warm=0.8, depth=None, *,
+                      cmd_schedule=None, cmd_every=1, heading=None, t0=0):
     """The evaluation loop in numpy float64 around `env` (reset() -> ob, step(a) -> ob, reward, done, extra, get_state() -> [n, 288],
     set_contact_coeff([n, 3])) and `actor` (act(o [n, 35], done [n]) -> [n, 12], already clipped if it clips).
     mu [n]: friction per env (contact_material); env i runs on mu_warm until step warm[i] (a scalar or [n]) and on mu[i] from then on, warm[i] = 0:
     from the start.  set_contact_coeff is called before the reset and at the steps where some env switches.  None leaves the env's material alone.
     The actor's float64 action goes through the action low-pass as it is and becomes float32 once, at env.step.
     -> dict of per-step records body [steps, n, 13], torque, obs_raw, obs_cond, act_clipped, act_applied, reward, done, and falls [n]; a window
-    warm[i] : warm[i] + frames is the caller's slice."""
+    warm[i] : warm[i] + frames is the caller's slice.
+    cmd_schedule [S, n] or [S, n, 3] with cmd_every and t0: the command schedule of PolicyEvaluator.set_scenario in place of `cmd`; heading: a
+    heading_hold dict -- the yaw comes from env.get_state() in front of the step, in float64; the record gains heading_out [steps, n] (the PI
+    output, 0 where the hold is off)."""
     n = env.n
     delay, depth = _delay_rows(delay, n, depth)
     target = _cmd_rows(cmd, n)
     mean, std, _, _ = obs_normalisation(env_cfg)
     dt = float(env_cfg["control_dt"])
+    schedule = None if cmd_schedule is None else _schedule_rows(cmd_schedule, n)
+    heading = heading_parameters(heading, n, float(env_cfg["Omega"]) if heading is not None else 0.0, dt)
     a_cmd, a_vel, a_act = lowpass_alpha(dt, cmd_hz), lowpass_alpha(dt, vel_hz), lowpass_alpha(dt, act_hz)
     warm = _step_rows(warm, n, "warm")
     if mu is not None:
@@ -128,13 +213,16 @@ def reference_rollout(env, actor, env_cfg, delay, cmd, steps, cmd_hz=1.0, vel_hz
     act_his = np.zeros((n, 12))
     done = np.zeros(n, bool)
     rec = dict(body=np.zeros((steps, n, 13)), torque=np.zeros((steps, n, 12)), obs_raw=np.zeros((steps, n, 35)), obs_cond=np.zeros((steps, n, 35)),
-               act_clipped=np.zeros((steps, n, 12)), act_applied=np.zeros((steps, n, 12)), reward=np.zeros((steps, n)), done=np.zeros((steps, n), bool))
+               act_clipped=np.zeros((steps, n, 12)), act_applied=np.zeros((steps, n, 12)), reward=np.zeros((steps, n)), done=np.zeros((steps, n), bool),
+               heading_out=np.zeros((steps, n)))
     for t in range(steps):
         switch = (warm == t) & (warm > 0)
         if mu is not None and switch.any():
             coeff[switch, 0] = mu[switch]
             env.set_contact_coeff(coeff)
-        o = condition(st, t, ob, delay, target, a_cmd, a_vel, mean[0:3], std[0:3])
+        yaw = yaw_from_quaternion(np.asarray(env.get_state(), np.float64)[:, _S_GC + 3:_S_GC + 7]) if heading is not None else None
+        o = condition(st, t, ob, delay, target, a_cmd, a_vel, mean[0:3], std[0:3], cmd_schedule=schedule, cmd_every=cmd_every, heading=heading, t0=t0, yaw=yaw)
+        rec["heading_out"][t] = st["heading_out"]
         a = actor.act(o, done)
         rec["obs_cond"][t] = o
         rec["act_clipped"][t] = a
@@ -151,6 +239,7 @@ def reference_rollout(env, actor, env_cfg, delay, cmd, steps, cmd_hz=1.0, vel_hz
         rec["reward"][t] = rew
         rec["done"][t] = done
         st["cmd"][np.asarray(done, bool)] = 0.0              # the env restarted from rest
+        st["heading_int"][np.asarray(done, bool)] = 0.0
     rec["falls"] = rec["done"].sum(0).astype(int)
     return rec
 
@@ -243,17 +332,61 @@ class PolicyEvaluator(object):
         self.obs = torch.zeros(n, 35, **f32)
         self.work = torch.zeros(n, WORK_DIM, **f32)
         self.stats = torch.zeros(len(STAT_SLOTS), n, device=dev, dtype=torch.float64)
+        self.heading_int = torch.zeros(n, **f32)               # the heading hold's integrator I (evaluator state, like cmd)
+        self._omega, self._dt = float(cfg["Omega"]), float(dt)
+        self.scenario = None
         self.t = 0
         self.reset()
 
     def reset(self):
-        """reset every env; the reset observation fills the delay line, command / histories / LSTM state / done are zeroed, t = 0"""
+        """reset every env; the reset observation fills the delay line, command / histories / LSTM state / done / the heading integrator are
+        zeroed, t = 0.  An installed scenario stays and its origin is re-based with the counter: t0 becomes what it was relative to the counter
+        when the scenario was installed (installed at t = 100 with the default t0: 0 again; installed with t0 = t + 1000: 1000)"""
         self.env.reset(self.obs)
         self.ring.copy_(self.obs.unsqueeze(0).expand_as(self.ring))
-        for b in (self.cmd, self.vel_his, self.act_his, self.lstm_state):
+        for b in (self.cmd, self.vel_his, self.act_his, self.lstm_state, self.heading_int):
             b.zero_()
         self.done.zero_()
         self.t = 0
+        if self.scenario is not None:
+            self.scenario["t0"] = self.scenario["t0_rel"]
+
+    def set_scenario(self, cmd_schedule=None, cmd_every=1, heading=None, stat_buckets=1, stat_every=1, t0=None):
+        """Install a scenario (include/irrl_env.h irrl_eval_scenario) for the following `run` calls; with tau = max(t - t0, 0):
+        cmd_schedule [S, N] (v_x) or [S, N, 3]: the command target of step t is row min(tau // cmd_every, S - 1) (None: the constructor's cmd);
+        heading: a dict of ref, kp, ki (a scalar or [N] each) and windup (None: the config's Omega) -- heading_hold(...) --, the PI loop on the base
+        yaw whose output the actor sees as element 2, for the envs with a non-zero gain (None: off);
+        stat_buckets B, stat_every: the frame of step t goes to bucket min(tau // stat_every, B - 1) of `stats`, which becomes [B, 18, N] and starts
+        from zero; t0: the origin on the global step counter (default: the current self.t).  The heading integrator keeps its value."""
+        import torch
+        f32 = dict(device=self.dev, dtype=torch.float32)
+        table = self.cmd_target.unsqueeze(0) if cmd_schedule is None else torch.from_numpy(_schedule_rows(cmd_schedule, self.n).astype(np.float32)).to(self.dev)
+        cmd_every, stat_buckets, stat_every = int(cmd_every), int(stat_buckets), int(stat_every)
+        if cmd_every < 1 or stat_buckets < 1 or stat_every < 1:
+            raise ValueError("cmd_every, stat_buckets and stat_every are at least 1")
+        h = heading_parameters(heading, self.n, self._omega, self._dt)
+        t0 = int(self.t if t0 is None else t0)
+        self.scenario = dict(t0=t0, t0_rel=t0 - self.t, cmd_table=table.contiguous(), cmd_every=cmd_every, stat_buckets=stat_buckets,
+                             stat_every=stat_every, heading=None if h is None else dict(
+                                 {k: torch.from_numpy(h[k].astype(np.float32)).to(self.dev) for k in ("ref", "kp", "ki")},
+                                 windup=float(np.float32(h["windup"])), dt=float(np.float32(h["dt"]))))
+        self.stats = torch.zeros(stat_buckets, len(STAT_SLOTS), self.n, device=self.dev, dtype=torch.float64)
+
+    def clear_scenario(self):
+        """back to the constructor's constant command, no heading hold, one statistics window [18, N] (zeroed)"""
+        import torch
+        self.scenario = None
+        self.stats = torch.zeros(len(STAT_SLOTS), self.n, device=self.dev, dtype=torch.float64)
+
+    def _scenario_struct(self):
+        from ._lib import EvalScenario, ptr
+        s = self.scenario
+        h = s["heading"]
+        raw = lambda t: None if t is None else ptr(t).value
+        return EvalScenario(t0=s["t0"], cmd_rows=int(s["cmd_table"].shape[0]), cmd_every=s["cmd_every"], cmd_table=raw(s["cmd_table"]),
+                            stat_buckets=s["stat_buckets"], stat_every=s["stat_every"], heading_ref=raw(h and h["ref"]), heading_kp=raw(h and h["kp"]),
+                            heading_ki=raw(h and h["ki"]), heading_int=raw(self.heading_int), heading_windup=h["windup"] if h else 0.0,
+                            heading_dt=h["dt"] if h else 0.0)
 
     @property
     def persistent_supported(self):
@@ -288,12 +421,18 @@ class PolicyEvaluator(object):
             self.policy.prepare()                              # the kernels' permuted weight copies follow the parameters (a learner may have stepped)
             warr = _lstm_weight_table(self.policy, self.dev)
             lib = _lib.load()
-            fn = lib.irrl_lstm_eval_rollout_persistent if resolve_persistent(persistent, lambda: self.persistent_supported) else lib.irrl_lstm_eval_rollout
+            one_launch = resolve_persistent(persistent, lambda: self.persistent_supported)
+            if self.scenario is None:
+                fn, scenario = (lib.irrl_lstm_eval_rollout_persistent if one_launch else lib.irrl_lstm_eval_rollout), ()
+            else:                                              # the scenario entry points: the same list with the host struct in front of the stream
+                fn = lib.irrl_lstm_eval_scenario_persistent if one_launch else lib.irrl_lstm_eval_scenario
+                struct = self._scenario_struct()
+                scenario = (C.cast(C.pointer(struct), C.c_void_p),)
             _lib.check(fn(
                 self.env._h, steps, self.t, self.hid, 35, 12, warr, *_head_ptrs(self.policy), self.depth, ptr(self.ring), ptr(self.cmd), ptr(self.vel_his),
                 ptr(self.act_his), ptr(self.lstm_state), ptr(self.done), ptr(self.obs), ptr(self.work), ptr(self.delay), ptr(self.cmd_target),
                 self.a_cmd, self.a_vel, self.a_act, self.cmd_mean, self.cmd_std, int(self.clip), *[ptr(out.get(k)) for k in RECORDERS],
-                ptr(self.stats) if accumulate else None, _lib.stream_ptr(self.dev)))
+                ptr(self.stats) if accumulate else None, *scenario, _lib.stream_ptr(self.dev)))
         self.t += steps
         return out
 
@@ -302,7 +441,14 @@ class PolicyEvaluator(object):
 
     def statistics(self):
         """per-env statistics over the frames accumulated since zero_statistics() (synchronises): dict of [N] numpy arrays, see statistics_from_sums"""
-        return statistics_from_sums(self.stats.cpu().numpy())
+        sums = self.stats.cpu().numpy()
+        return statistics_from_sums(sums.sum(0) if sums.ndim == 3 else sums)   # a scenario's buckets: the whole window, from the sums added
+
+    def bucket_statistics(self):
+        """the statistics per bucket of the installed scenario (synchronises): dict of [B, N] numpy arrays (B = 1 without a scenario)"""
+        sums = self.stats.cpu().numpy()
+        per = [statistics_from_sums(s) for s in (sums if sums.ndim == 3 else sums[None])]
+        return {k: np.stack([p[k] for p in per], 0) for k in per[0]}
 
 
 def load_policy(model_or_policy, device):
@@ -335,11 +481,16 @@ def load_policy(model_or_policy, device):
 
 
 def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=1000, steps=2000, cmd_hz=1.0, vel_hz=None, act_hz=None, clip=True,
-                     mu_warm=0.8, device=None, persistent=PERSISTENT_DEFAULT):
+                     mu_warm=0.8, device=None, persistent=PERSISTENT_DEFAULT, levels=None, level_steps=None, heading=None):
     """The reference's robustness grid in one pool: len(mus) x len(delays) x len(cmds) Manual-mode envs (condition index = (i_mu * len(delays) +
     i_delay) * len(cmds) + i_cmd), `warm_steps` control steps on friction mu_warm, then `steps` on the condition's own friction over which the
     statistics are taken.  env_cfg: the `environment:` mapping of a config.  persistent: PolicyEvaluator.run's keyword (same statistics bit for bit
-    either way).  -> list of rows dict(mu, delay, cmd, falls, frames, <statistics>)."""
+    either way).  -> list of rows dict(mu, delay, cmd, falls, frames, <statistics>).
+    heading: a heading_hold dict (a scalar or one value per condition), the script's `--dir_fd`, on from the first step.
+    levels (with an even level_steps): the script's `--step` staircase in place of `steps` at the full command -- level l = 1 .. levels commands
+    l / levels * cmd for level_steps control steps (the warm-up runs at level 1), the run is levels * level_steps steps, still ONE call, with two
+    statistics buckets per level; -> one row per (condition, level), taken over the SECOND half of the level, with the keys `level` and
+    `cmd_level` (the commanded v_x of that level)."""
     import torch
     import yaml
     from . import __BLACKPANTHER_V55_RESOURCE_DIRECTORY__ as rsc
@@ -357,19 +508,38 @@ def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=100
     coeff = contact_material([mu_warm if warm_steps > 0 else g[0] for g in grid])
     env.SetContactCoefficient(coeff)
     ev = PolicyEvaluator(env, policy, [g[1] for g in grid], [g[2] for g in grid], cmd_hz=cmd_hz, vel_hz=vel_hz, act_hz=act_hz, clip=clip)
+    if levels is not None:
+        levels = int(levels)
+        if levels < 1 or level_steps is None or int(level_steps) < 2 or int(level_steps) % 2:
+            raise ValueError("a staircase needs levels >= 1 and an even level_steps >= 2")
+        level_steps = int(level_steps)
+        steps = levels * level_steps
+        # the origin behind the warm-up: tau = 0 until then, so the warm-up runs at level 1 (and with the heading hold on)
+        ev.set_scenario(cmd_schedule=staircase_schedule([g[2] for g in grid], levels), cmd_every=level_steps, heading=heading, stat_buckets=2 * levels,
+                        stat_every=level_steps // 2, t0=max(int(warm_steps), 0))
+    elif heading is not None:
+        ev.set_scenario(heading=heading)
     if warm_steps > 0:
         ev.run(warm_steps, accumulate=False, persistent=persistent)
         coeff[:, 0] = [g[0] for g in grid]                     # (the setter's copy is ordered on the pool's stream, behind the warm-up)
         env.SetContactCoefficient(coeff)
     ev.zero_statistics()
     ev.run(steps, persistent=persistent)
-    st = ev.statistics()
-    return [dict(mu=m, delay=d, cmd=c, **{k: (int(v[i]) if k in ("falls", "frames") else float(v[i])) for k, v in st.items()}) for i, (m, d, c) in enumerate(grid)]
+    number = lambda k, x: int(x) if k in ("falls", "frames") else float(x)
+    if levels is None:
+        st = ev.statistics()
+        return [dict(mu=m, delay=d, cmd=c, **{k: number(k, v[i]) for k, v in st.items()}) for i, (m, d, c) in enumerate(grid)]
+    st = ev.bucket_statistics()
+    return [dict(mu=m, delay=d, cmd=c, level=l + 1, cmd_level=(l + 1) / levels * c, **{k: number(k, v[2 * l + 1, i]) for k, v in st.items()})
+            for i, (m, d, c) in enumerate(grid) for l in range(levels)]
 
 
 def sweep_table(rows):
     keys = ("vx_body_mean", "vx_body_std", "z_mean", "z_std", "roll_std", "pitch_mean", "pitch_std", "yaw_rate_mean")
-    out = ["%-6s %-5s %-5s %-5s " % ("mu", "delay", "cmd", "falls") + " ".join("%-12s" % k for k in keys)]
+    staircase = bool(rows) and "level" in rows[0]              # one row per (condition, level): the level and its commanded v_x as well
+    lead = ("mu", "delay", "cmd") + (("level", "cmd_level") if staircase else ()) + ("falls",)
+    out = [" ".join("%-*s" % (9 if k == "cmd_level" else 6 if k == "mu" else 5, k) for k in lead) + " " + " ".join("%-12s" % k for k in keys)]
     for r in rows:
-        out.append("%-6g %-5d %-5g %-5d " % (r["mu"], r["delay"], r["cmd"], r["falls"]) + " ".join("%+12.4f" % r[k] for k in keys))
+        lvl = "%-5d %-9g " % (r["level"], r["cmd_level"]) if staircase else ""
+        out.append("%-6g %-5d %-5g %s%-5d " % (r["mu"], r["delay"], r["cmd"], lvl, r["falls"]) + " ".join("%+12.4f" % r[k] for k in keys))
     return "\n".join(out)

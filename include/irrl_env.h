@@ -462,6 +462,48 @@ int irrl_lstm_eval_rollout_persistent(irrl_env *env, int steps, long long step0,
                                       float *rec_obs_cond, float *rec_act_clipped, float *rec_act_applied, float *rec_body, float *rec_torque,
                                       float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats, void *hip_stream);
 
+/* THE EVALUATION LOOP WITH A SCENARIO: a command schedule, a heading hold and statistics per time segment, the three ingredients of the reference's
+ * evaluation loop that need the loop's own step counter or the robot's state at every control step (run_bp_v5.py:383-388 `--step`, :308-315 and
+ * :400-406 `--dir_fd`).  Semantics in ONE text, csrc/eval_elements.hpp.  With tau = max(t - t0, 0) for control step t (t = step0 + k, the
+ * evaluator's global counter) and env e:
+ *   command schedule   cmd_target of step 1 above becomes cmd_table[min(tau / cmd_every, cmd_rows - 1), e, 0:3] (device f32 [cmd_rows, N, 3]); the
+ *                      last row holds once the table runs out; cmd_every = 1: one row per step.  Filters, delay line, scaling unchanged.
+ *   heading hold       on for env e where heading_kp[e] != 0 || heading_ki[e] != 0 (device f32 [N] each; all three NULL = off for everyone).  With
+ *                      q the base quaternion as the pool holds it at conditioning time (after step t - 1, or after the reset; not delayed), in f32:
+ *                      yaw = atan2f(2 (w z + x y), 1 - 2 (y y + z z)); err = heading_ref[e] - yaw wrapped into [-pi, pi);
+ *                      I_e = clamp(I_e + err heading_dt, -heading_windup, +heading_windup); out = kp_e err + ki_e I_e; the actor's element 2 is
+ *                      (out - cmd_mean[2]) / cmd_std[2] in place of the scaled low-passed command (cmd[e, 2] keeps evolving unseen).  I_e lives
+ *                      in heading_int (device f32 [N], caller-owned state like cmd) and is zeroed where the env step ends in `done`.  The common
+ *                      positional PID with Kd = 0 and an integrator clamp (the reference's utils/PID.py is not in its tree).
+ *   statistics buckets the frame of step t is added to stats[min(tau / stat_every, stat_buckets - 1)]: stats is [stat_buckets,
+ *                      IRRL_EVAL_STAT_COUNT, N]; stat_buckets = 1 is the plain buffer.
+ * scenario == NULL is exactly irrl_lstm_eval_rollout[_persistent], which are calls of these with NULL.  Both forms leave bit-identical buffers
+ * (heading_int included); the persistent one exists exactly where irrl_lstm_eval_rollout_supports says so, with no fallback inside the call.
+ * Refused before any HIP call, with the entry point's name in the text: cmd_rows / cmd_every / stat_buckets / stat_every < 1, a NULL cmd_table,
+ * a partly NULL heading set, heading on without heading_int, heading_windup < 0, heading_dt <= 0 (the last two where the heading set is given). */
+typedef struct irrl_eval_scenario {
+  long long t0;
+  int cmd_rows, cmd_every;
+  const float *cmd_table;
+  int stat_buckets, stat_every;
+  const float *heading_ref, *heading_kp, *heading_ki;
+  float *heading_int;
+  float heading_windup, heading_dt;
+} irrl_eval_scenario;
+int irrl_lstm_eval_scenario(irrl_env *env, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *lstm_w, const float *pi_w,
+                            const float *pi_b, const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring, float *cmd, float *vel_his,
+                            float *act_his, float *lstm_state, uint8_t *done, float *obs, float *work, const int *delay, const float *cmd_target, float a_cmd,
+                            float a_vel, float a_act, const float *cmd_mean, const float *cmd_std, int clip, float *rec_obs_cond, float *rec_act_clipped,
+                            float *rec_act_applied, float *rec_body, float *rec_torque, float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats,
+                            const irrl_eval_scenario *scenario, void *hip_stream);
+int irrl_lstm_eval_scenario_persistent(irrl_env *env, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *lstm_w,
+                                       const float *pi_w, const float *pi_b, const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring,
+                                       float *cmd, float *vel_his, float *act_his, float *lstm_state, uint8_t *done, float *obs, float *work, const int *delay,
+                                       const float *cmd_target, float a_cmd, float a_vel, float a_act, const float *cmd_mean, const float *cmd_std, int clip,
+                                       float *rec_obs_cond, float *rec_act_clipped, float *rec_act_applied, float *rec_body, float *rec_torque,
+                                       float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats, const irrl_eval_scenario *scenario,
+                                       void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,6 +70,13 @@ def parse_args(argv):
                    help="--sweep: the whole run as one persistent launch (on; refused where the kernel does not exist), where it exists (auto), or five "
                         "launches per control step (off); same table bit for bit.  Default: evaluate.PERSISTENT_DEFAULT")
     p.add_argument("--warm", type=int, default=1000, help="--sweep: control steps on friction 0.8 before the condition's own friction is installed")
+    # the reference's own names (run_bp_v5.py:383-388 and :308-315 / :400-406), for --test and --test --sweep
+    p.add_argument("--step", dest="flag_step", action="store_true", default=False,
+                   help="--test: the command staircase, (t // step_steps + 1) / 4 of the command, four levels (--sweep: --steps is replaced by 4 x "
+                        "--step_steps and the table has one row per condition and level, over the second half of the level)")
+    p.add_argument("--step_steps", type=int, default=5000, help="--step: control steps per level (even)")
+    p.add_argument("--dir_fd", dest="flag_dir_fd", action="store_true", default=False,
+                   help="--test: direction feedback, a PI loop (kp 1, ki 0.1, clamp Omega) on the base yaw replaces the yaw-rate command")
     return p.parse_args(argv)
 
 
@@ -79,7 +86,8 @@ def run_test(args, cfg):
     import numpy as np
     from flex_gym.env.RaisimGymVecEnv import RaisimGymVecEnv
     from high_speed_quadrupedal_locomotion_by_irrl_amd.checkpoint import NumpyLstmActor, read_checkpoint
-    from high_speed_quadrupedal_locomotion_by_irrl_amd.evaluate import condition, condition_state, contact_material, lowpass_alpha
+    from high_speed_quadrupedal_locomotion_by_irrl_amd.evaluate import (condition, condition_state, contact_material, heading_hold, heading_parameters,
+                                                                        lowpass_alpha, staircase_schedule, yaw_from_quaternion)
     from high_speed_quadrupedal_locomotion_by_irrl_amd.helper import obs_normalisation
     if args.trained_model is None:
         raise SystemExit("model path can't be ignored during test mode (--model)")
@@ -105,14 +113,19 @@ def run_test(args, cfg):
     rec = {k: [] for k in ("joint", "joint_dot", "posture", "omega", "phase", "act", "oss", "contact", "joint_effort", "cmd", "reward")}
     cmd_target = np.array([[args.flag_fix_cmd, 0.0, 0.0]])
     n_done = 0
+    # --step: the command staircase, four levels of --step_steps control steps; --dir_fd: the PI loop on the base yaw (the evaluator's scenario)
+    schedule = staircase_schedule(cmd_target, 4) if args.flag_step else None
+    heading = heading_parameters(heading_hold(1), 1, float(ecfg["Omega"]), dt) if args.flag_dir_fd else None
     for t in range(args.steps):
-        o = condition(st, t, obs, [args.delay], cmd_target, a_cmd, a_vel, obs_mean[0:3], obs_std[0:3])[0]    # Manual: the script owns obs[0:3]
+        state = env.OriginState()[0, :]
+        yaw = yaw_from_quaternion(state[None, 3:7]) if heading is not None else None
+        o = condition(st, t, obs, [args.delay], cmd_target, a_cmd, a_vel, obs_mean[0:3], obs_std[0:3], cmd_schedule=schedule, cmd_every=args.step_steps,
+                      heading=heading, yaw=yaw)[0]                                              # Manual: the script owns obs[0:3]
         action = ctrl.predict(o)
         action = (1 - a_act) * act_his + a_act * action
         act_his = action
         action_total[0, :] = action
         ob_double = o * obs_std + obs_mean
-        state = env.OriginState()[0, :]
         rec["joint"].append(ob_double[5:17]); rec["joint_dot"].append(ob_double[17:29]); rec["posture"].append(ob_double[29:32])
         rec["omega"].append(ob_double[32:35]); rec["phase"].append(ob_double[3:5]); rec["act"].append(action * action_std + action_mean)
         rec["oss"].append(state[0:37]); rec["contact"].append(state[37:41]); rec["joint_effort"].append(env.GetJointEffort()[0, :])
@@ -123,6 +136,7 @@ def run_test(args, cfg):
             n_done += 1
             ctrl.reset()
             st["cmd"][:] = 0.0                  # the env restarted from rest
+            st["heading_int"][:] = 0.0
     out = {k: np.asarray(v) for k, v in rec.items()}
     vx = out["oss"][:, 19]
     print("test: %d steps (%.2f s), command %.2f m/s, mean forward velocity %.3f m/s (last half %.3f), falls %d, mean reward %.4f"
@@ -139,13 +153,18 @@ def run_sweep(args, cfg):
     (evaluate.PolicyEvaluator), `--warm` steps on the script's default material, then `--steps` on the condition's own over which the
     statistics are taken.  Prints the table, writes it to --out as JSON."""
     import json
-    from high_speed_quadrupedal_locomotion_by_irrl_amd.evaluate import PERSISTENT_DEFAULT, robustness_sweep, sweep_table
+    from high_speed_quadrupedal_locomotion_by_irrl_amd.evaluate import PERSISTENT_DEFAULT, heading_hold, robustness_sweep, sweep_table
     if args.trained_model is None:
         raise SystemExit("model path can't be ignored during test mode (--model)")
     none_if_off = lambda f: None if f >= 1.0e6 else f
+    n = len(args.sweep_mu) * len(args.sweep_delay) * len(args.sweep_cmd)
+    # --step: four levels of --step_steps steps in place of --steps, one row per condition and level; --dir_fd: the heading hold on every env.
+    # Still one pool and one call per run: with --persistent on, one launch (two with a warm-up).
     rows = robustness_sweep(args.trained_model, cfg["environment"], args.sweep_mu, args.sweep_delay, args.sweep_cmd, warm_steps=args.warm, steps=args.steps,
                             cmd_hz=args.cmd_filter_freq, vel_hz=none_if_off(args.vel_filter_freq), act_hz=none_if_off(args.act_filter_freq),
-                            persistent=PERSISTENT_DEFAULT if args.persistent is None else args.persistent)
+                            persistent=PERSISTENT_DEFAULT if args.persistent is None else args.persistent,
+                            levels=4 if args.flag_step else None, level_steps=args.step_steps if args.flag_step else None,
+                            heading=heading_hold(n) if args.flag_dir_fd else None)
     print(sweep_table(rows))
     if args.out:
         with open(args.out, "w") as f:

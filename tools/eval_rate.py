@@ -8,7 +8,10 @@ clock around work that ends in a device synchronise.
 --ab: the persistent single-launch form (PolicyEvaluator.run(persistent=True), kernel csrc/env_eval_kernels.hpp) against the five-launch form, same
 process, same pool, interleaved A, B, A, B (A = five launches per step), statistics only and all recorders; the host-driven leg is skipped.
 
-    python tools/eval_rate.py --ab [--envs 4096 | --envs 90] [--steps 2000]
+    python tools/eval_rate.py --ab [--envs 4096 | --envs 90] [--steps 2000] [--scenario]
+
+--scenario (with --ab): every leg runs with a scenario installed (PolicyEvaluator.set_scenario: a 5-row command staircase over the timed steps, the
+heading hold on every env, 4 statistics buckets) through irrl_lstm_eval_scenario[_persistent].
 """
 import argparse
 import json
@@ -37,6 +40,9 @@ def ab(args, env, pol, delays, cmds, out):
         legs = {False: [], True: []}
         for persistent in (False, True, False, True):
             ev = EV.PolicyEvaluator(env, pol, delays, cmds, cmd_hz=1.0, vel_hz=50.0, act_hz=30.0)
+            if args.scenario:
+                ev.set_scenario(cmd_schedule=EV.staircase_schedule(cmds, 5), cmd_every=max(args.steps // 5, 1), heading=EV.heading_hold(n), stat_buckets=4,
+                                stat_every=max(args.steps // 4, 1), t0=50)
             ev.run(50, record=record, accumulate=acc, persistent=persistent)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -58,6 +64,7 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--host-steps", type=int, default=200)
     ap.add_argument("--no-statistics", action="store_true", help="--ab: one more pair of legs with neither recorders nor statistics (accumulate=False)")
+    ap.add_argument("--scenario", action="store_true", help="--ab: a 5-row command schedule, the heading hold and 4 statistics buckets on every leg")
     ap.add_argument("--ab", action="store_true", help="five launches per step (A) against the persistent launch (B), interleaved A, B, A, B")
     args = ap.parse_args()
     n = args.envs
@@ -68,7 +75,7 @@ def main():
     env = FlexibleGymEnv(pkg.__BLACKPANTHER_V55_RESOURCE_DIRECTORY__, yaml.safe_dump(cfg, default_flow_style=False, width=float("inf")))
     env.init()
     env.SetContactCoefficient(EV.contact_material(mus))
-    out = {"envs": n}
+    out = {"envs": n, "scenario": bool(args.scenario)}
     if args.ab:
         return ab(args, env, pol, delays, cmds, out)
     for name, record in (("statistics only", ()), ("all recorders", tuple(EV.RECORDERS))):
