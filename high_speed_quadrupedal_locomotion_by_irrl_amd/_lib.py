@@ -108,6 +108,15 @@ SIGNATURES = {
                                 + [fp, fp, C.c_int] + [vp] * 9 + [vp, vp]),
     "irrl_lstm_eval_scenario_persistent": (C.c_int, [vp, C.c_int, C.c_longlong] + [C.c_int] * 3 + [vp] * 6 + [C.c_int] + [vp] * 8 + [vp] * 2 + [C.c_float] * 3
                                            + [fp, fp, C.c_int] + [vp] * 9 + [vp, vp]),
+    # both forms with a kick table: the scenario's list with `const irrl_eval_kicks *` (EvalKicks below; None = NULL = the scenario call) behind
+    # the scenario
+    "irrl_lstm_eval_perturbed": (C.c_int, [vp, C.c_int, C.c_longlong] + [C.c_int] * 3 + [vp] * 6 + [C.c_int] + [vp] * 8 + [vp] * 2 + [C.c_float] * 3
+                                 + [fp, fp, C.c_int] + [vp] * 9 + [vp, vp, vp]),
+    "irrl_lstm_eval_perturbed_persistent": (C.c_int, [vp, C.c_int, C.c_longlong] + [C.c_int] * 3 + [vp] * 6 + [C.c_int] + [vp] * 8 + [vp] * 2 + [C.c_float] * 3
+                                            + [fp, fp, C.c_int] + [vp] * 9 + [vp, vp, vp]),
+    # one kick row per env on the pool now: device rows [N, 11] / host rows
+    "irrl_env_perturb_base": (C.c_int, [vp, vp]),
+    "irrl_env_perturb_base_host": (C.c_int, [vp, fp]),
 }
 
 
@@ -115,6 +124,11 @@ class EvalScenario(C.Structure):
     """struct irrl_eval_scenario of include/irrl_env.h (a HOST struct of scalars and device pointers); pass C.byref(...) or None"""
     _fields_ = [("t0", C.c_longlong), ("cmd_rows", C.c_int), ("cmd_every", C.c_int), ("cmd_table", vp), ("stat_buckets", C.c_int), ("stat_every", C.c_int),
                 ("heading_ref", vp), ("heading_kp", vp), ("heading_ki", vp), ("heading_int", vp), ("heading_windup", C.c_float), ("heading_dt", C.c_float)]
+
+
+class EvalKicks(C.Structure):
+    """struct irrl_eval_kicks of include/irrl_env.h (a HOST struct; kick_table a device pointer to [kick_rows, N, 11] f32); C.byref(...) or None"""
+    _fields_ = [("kick_rows", C.c_int), ("kick_first", C.c_longlong), ("kick_every", C.c_int), ("kick_table", vp)]
 
 
 def load():

@@ -29,6 +29,8 @@
 // (the lane context lives in registers), so the robot's lead lane writes the FINAL lane's quaternion -- post-reset on a `done` -- into that scratch
 // in the Tail hook; in front of step 0 it is filled from the pool.  I is read once and written back once.  LDS: 158 080 B of 163 840 (157 504
 // before the scenario).
+// A kick table (irrl_lstm_eval_perturbed_persistent) adds, at the top of a step whose row fires, the kick on the lane context in every lane of
+// the robot (the env step's lane_carry then hands on the lead lane's kicked words); no LDS of its own.
 // The critic is NOT run: the critic's half of lstm_state [N, 4 hid : 8 hid] and the `value` column of the work array are left untouched (the
 // actor never reads them, so calls of either form may follow each other).  HID 48, ob 35, act 12.
 __global__ void IRRL_ENV_BOUNDS
@@ -138,7 +140,7 @@ IRRL_RK(irrl_eval_persistent_kernel)(EnvParams P_, EnvState S_, float *ob, float
   // and the bucket in `st` are NOT carried from step to step: a step of a call with a scenario recomputes the previous step's from the kernel
   // arguments, so that nothing but this word stays live across the env step for the scenario.  The scenario's
   // blocks are marked unlikely: block placement and the register allocator's spill weights then favour the step without one.
-  const int scn_ = __builtin_amdgcn_readfirstlane((ev.cmd_table ? 1 : 0) | (ev.stat_buckets > 1 ? 2 : 0) | (ev.heading_kp ? 4 : 0));
+  const int scn_ = __builtin_amdgcn_readfirstlane((ev.cmd_table ? 1 : 0) | (ev.stat_buckets > 1 ? 2 : 0) | (ev.heading_kp ? 4 : 0) | (ev.kick_table ? 8 : 0));
   int slot_ = ev.slot;
   __syncthreads();   // the LDS image, the head weights and the wave's scratch have landed
   for (int k = 0; k < steps; k++) {
@@ -170,6 +172,20 @@ IRRL_RK(irrl_eval_persistent_kernel)(EnvParams P_, EnvState S_, float *ob, float
           PS_WAVE_SYNC();
         }
       }
+    }
+    // the kick of a step whose row fires (uniform for the whole grid), on the state the previous step or the reset left.  EVERY lane applies it
+    // to its own copy of the robot's base state: in front of step 0 load_lane has put the same words into each of the robot's 16 lanes, and
+    // behind a step lane_carry (below, in front of step_compute) broadcasts the lead lane's words, so that what the env step starts from is the
+    // kick of the lead lane's copy either way -- the kick commutes with the broadcast.  It stands HERE, with the scenario's other blocks, and not
+    // between lane_carry and step_compute: there the step WITHOUT kicks measured 0.15-0.25 us slower than the parent's, here it measures the same
+    // (DESIGN.md section 3.7).  The heading hold below reads the quaternion the Tail hook left in its scratch: pre-kick, as in the five-launch form.
+    // The row is the lane's clamped env's, as the step kernel reads actions: an idle row of the pool's last wave takes the last robot's kick and
+    // stays its exact twin.  Read from global memory at the kick step; nothing of it is live across the env step.
+    if (__builtin_expect((scn_ & 8) != 0, 0)) {
+      const int r = irrl_eval_kick_row(ek, ek.t + (long long)k);
+      if (r >= 0)
+        irrl_eval_kick_apply(ek.kick_table + ((size_t)r * (size_t)ek.N + (size_t)env0_) * IRRL_EVAL_KICK_DIM, L.pos.z, L.qw, L.qx, L.qy, L.qz, L.vw.x, L.vw.y,
+                             L.vw.z, L.ww.x, L.ww.y, L.ww.z);
     }
     if (__builtin_expect((scn_ & 4) != 0, 0)) {
       if (lane < nrob_) {

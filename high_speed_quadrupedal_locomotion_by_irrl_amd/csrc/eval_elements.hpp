@@ -53,6 +53,10 @@ struct EvalArgs {
   const float *heading_ref, *heading_kp, *heading_ki;   // [N] each, or all NULL: heading hold off
   float *heading_int;               // [N] the integrator I
   float heading_windup, heading_dt;
+  // the kick table (irrl_eval_kicks, include/irrl_env.h); kick_table NULL = none.  Its schedule counts from t0 above (0 without a scenario)
+  int kick_rows, kick_every;        // read only where kick_table is set
+  long long kick_first;
+  const float *kick_table;          // [kick_rows, N, IRRL_EVAL_KICK_DIM] or NULL
 };
 
 // steps 1-6 of a control step for ONE element (env e, component j) of the observation: ring[slot] = raw, the delayed read, the rate low-pass,
@@ -154,4 +158,53 @@ static inline IRRL_EVAL_FN float irrl_eval_heading_element(const EvalArgs &a, fl
 // after the env step: the env restarted from rest, so does its integrator
 static inline IRRL_EVAL_FN void irrl_eval_heading_epilogue(bool dn, float *I_e) {
   if (dn) *I_e = 0.0f;
+}
+
+// ---- the kick table: caller-specified base-state displacements at chosen control steps (irrl_eval_kicks, include/irrl_env.h) ----
+// the row of kick_table that fires at control step t, or -1: row r fires where t >= t0 + kick_first and t - t0 - kick_first = r kick_every with
+// 0 <= r < kick_rows.  Written in t, not in tau: tau is clamped to 0 in front of t0, where a rule in tau would fire at every step.
+static inline IRRL_EVAL_FN int irrl_eval_kick_row(const EvalArgs &a, long long t) {
+  const long long d = t - a.t0 - a.kick_first;
+  if (d < 0) return -1;
+  const long long r = d / (long long)a.kick_every;
+  if (r * (long long)a.kick_every != d || r >= (long long)a.kick_rows) return -1;
+  return (int)r;
+}
+// does the row displace its env: a row whose four dq words are all zero is "no kick for this env", whatever its other seven words are
+static inline IRRL_EVAL_FN bool irrl_eval_kick_on(const float *k) { return k[1] != 0.0f || k[2] != 0.0f || k[3] != 0.0f || k[4] != 0.0f; }
+// One kick row k = dz | dq_w dq_x dq_y dq_z | dv_x dv_y dv_z | dw_x dw_y dw_z on ONE env's base state, body-frame: with R(q) the rotation matrix
+// of the base quaternion BEFORE the kick,  z += dz,  v_w += R(q) dv,  w_w += R(q) dw,  q = (q (x) dq) / |q (x) dq|.  pz: base height; w x y z: the
+// base quaternion; v0 v1 v2 / o0 o1 o2: world linear / angular velocity (gc[2], gc[3:7], gv[0:3], gv[3:6]); nothing else of the env is touched,
+// and an env whose row is off (irrl_eval_kick_on) keeps its ten words bit for bit.  No trigonometry: dq comes from the host.
+// f32, every statement ONE expression (see the note on -ffp-contract at the top); the norm as 1.0f / sqrtf(n).
+static inline IRRL_EVAL_FN void irrl_eval_kick_apply(const float *k, float &pz, float &w, float &x, float &y, float &z, float &v0, float &v1, float &v2,
+                                                     float &o0, float &o1, float &o2) {
+  if (!irrl_eval_kick_on(k)) return;
+  const float dz = k[0], dw = k[1], dx = k[2], dy = k[3], dq = k[4];
+  const float r00 = 1.0f - 2.0f * (y * y + z * z);
+  const float r01 = 2.0f * (x * y - w * z);
+  const float r02 = 2.0f * (x * z + w * y);
+  const float r10 = 2.0f * (x * y + w * z);
+  const float r11 = 1.0f - 2.0f * (x * x + z * z);
+  const float r12 = 2.0f * (y * z - w * x);
+  const float r20 = 2.0f * (x * z - w * y);
+  const float r21 = 2.0f * (y * z + w * x);
+  const float r22 = 1.0f - 2.0f * (x * x + y * y);
+  pz = pz + dz;
+  v0 = v0 + (r00 * k[5] + r01 * k[6] + r02 * k[7]);
+  v1 = v1 + (r10 * k[5] + r11 * k[6] + r12 * k[7]);
+  v2 = v2 + (r20 * k[5] + r21 * k[6] + r22 * k[7]);
+  o0 = o0 + (r00 * k[8] + r01 * k[9] + r02 * k[10]);
+  o1 = o1 + (r10 * k[8] + r11 * k[9] + r12 * k[10]);
+  o2 = o2 + (r20 * k[8] + r21 * k[9] + r22 * k[10]);
+  const float qw = w * dw - x * dx - y * dy - z * dq;
+  const float qx = w * dx + x * dw + y * dq - z * dy;
+  const float qy = w * dy - x * dq + y * dw + z * dx;
+  const float qz = w * dq + x * dy - y * dx + z * dw;
+  const float n = qw * qw + qx * qx + qy * qy + qz * qz;
+  const float s = 1.0f / sqrtf(n);
+  w = qw * s;
+  x = qx * s;
+  y = qy * s;
+  z = qz * s;
 }

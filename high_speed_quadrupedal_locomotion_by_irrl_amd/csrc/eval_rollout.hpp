@@ -11,6 +11,8 @@
 // With a scenario (irrl_lstm_eval_scenario: the <true> instantiations of kernels 1 and 5) kernel 1 takes the command target from the step's row of
 // the command table and runs the heading hold in lane (e, 2), which owns I_e and reads the base quaternion from the pool's gc; kernel 5 zeroes I_e
 // on done and adds the frame into the step's statistics bucket.
+// With a kick table (irrl_lstm_eval_perturbed) a step whose row fires gets ONE extra launch, irrl_eval_perturb_kernel, between kernels 3 and 4; a
+// step without a kick issues the five launches above.
 // A filter coefficient of exactly 1.0f switches that filter OFF (the value passes through bit for bit).  The ring and the two filter histories
 // survive an in-episode `done`, as they do in the reference script.
 // The per-element arithmetic lives in eval_elements.hpp, ONE text shared with the persistent single-launch form of the same loop
@@ -83,6 +85,21 @@ __global__ void __launch_bounds__(256) irrl_eval_record_kernel(const EvalArgs a)
   // the frame goes to this step's bucket of the statistics (no scenario: bucket 0, the whole buffer)
   const size_t bucket = SCN ? (size_t)irrl_eval_stat_bucket(a, irrl_eval_tau(a, a.t)) * (size_t)IRRL_EVAL_STAT_COUNT * (size_t)N : (size_t)0;
   irrl_eval_env_epilogue(dn != 0, a.cmd + e * 3, a.stats ? a.stats + bucket + e : nullptr, (size_t)N, gc[2], gc[3], gc[4], gc[5], gc[6], gv[0], gv[1], gv[2], gv[3], gv[4], gv[5]);
+}
+
+// a kick row per env on the pool's base state (irrl_env_perturb_base; the extra launch of irrl_lstm_eval_perturbed at a step whose row fires,
+// between the action filter and the env step): a lane per env, which owns that env's gc[2:7] and gv[0:6].  Any pool kind and lane layout:
+// gc / gv are [N, 19] / [N, 18] in every one.  An env whose row is off is not written.
+__global__ void __launch_bounds__(256) irrl_eval_perturb_kernel(int N, const float *rows, float *gc_, float *gv_) {
+  const int e = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (e >= N) return;
+  const float *k = rows + (size_t)e * IRRL_EVAL_KICK_DIM;
+  if (!irrl_eval_kick_on(k)) return;
+  float *gc = gc_ + (size_t)e * 19, *gv = gv_ + (size_t)e * 18;
+  float pz = gc[2], w = gc[3], x = gc[4], y = gc[5], z = gc[6], v0 = gv[0], v1 = gv[1], v2 = gv[2], o0 = gv[3], o1 = gv[4], o2 = gv[5];
+  irrl_eval_kick_apply(k, pz, w, x, y, z, v0, v1, v2, o0, o1, o2);
+  gc[2] = pz; gc[3] = w; gc[4] = x; gc[5] = y; gc[6] = z;
+  gv[0] = v0; gv[1] = v1; gv[2] = v2; gv[3] = o0; gv[4] = o1; gv[5] = o2;
 }
 
 static inline dim3 eval_grid(int n_elems) { return dim3((unsigned)((n_elems + 255) / 256)); }

@@ -566,7 +566,20 @@ static void eval_scenario_args(EvalArgs &a, const irrl_eval_scenario *sc, long l
     a.heading_windup = sc->heading_windup; a.heading_dt = sc->heading_dt;
   }
 }
-// the argument list the four evaluation entry points share, and its forwarding
+// the kick table of irrl_lstm_eval_perturbed[_persistent] (include/irrl_env.h): refused before any HIP call; NULL = none
+static int eval_kicks_check(const char *who, const irrl_eval_kicks *kk) {
+  if (!kk) return 0;
+  const std::string w = std::string(who) + ": kicks: ";
+  if (kk->kick_rows < 1 || kk->kick_every < 1) { g_err = w + "kick_rows >= 1, kick_every >= 1"; return 1; }
+  if (kk->kick_first < 0) { g_err = w + "kick_first >= 0"; return 1; }
+  if (!kk->kick_table) { g_err = w + "NULL kick_table"; return 1; }
+  return 0;
+}
+static void eval_kicks_args(EvalArgs &a, const irrl_eval_kicks *kk) {
+  if (!kk) return;
+  a.kick_rows = kk->kick_rows; a.kick_every = kk->kick_every; a.kick_first = kk->kick_first; a.kick_table = kk->kick_table;
+}
+// the argument list the six evaluation entry points share, and its forwarding
 #define IRRL_EVAL_PARAMS                                                                                                                              \
   irrl_env *h, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *lstm_w, const float *pi_w, const float *pi_b,        \
       const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring, float *cmd, float *vel_his, float *act_his, float *lstm_state, \
@@ -577,10 +590,11 @@ static void eval_scenario_args(EvalArgs &a, const irrl_eval_scenario *sc, long l
   h, steps, step0, hid, ob_dim, act_dim, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, depth, ring, cmd, vel_his, act_his, lstm_state, done, obs, work, delay, \
       cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std, clip, rec_obs_cond, rec_act_clipped, rec_act_applied, rec_body, rec_torque, rec_obs_raw,       \
       rec_reward, rec_done, stats
-static int eval_rollout_steps(const char *who, IRRL_EVAL_PARAMS, const irrl_eval_scenario *sc, void *hip_stream) {
+static int eval_rollout_steps(const char *who, IRRL_EVAL_PARAMS, const irrl_eval_scenario *sc, const irrl_eval_kicks *kk, void *hip_stream) {
   if (eval_rollout_check(who, h, steps, step0, hid, ob_dim, act_dim, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, depth, ring, cmd, vel_his, act_his,
                          lstm_state, done, obs, work, delay, cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std)) return 1;
   if (eval_scenario_check(who, sc)) return 1;
+  if (eval_kicks_check(who, kk)) return 1;
   if (need_init(h)) return 1;
   HIP_TRY(hipSetDevice(h->device));
   h->stream = (hipStream_t)hip_stream;
@@ -589,6 +603,7 @@ static int eval_rollout_steps(const char *who, IRRL_EVAL_PARAMS, const irrl_eval
   EvalArgs a = eval_args(h, w, depth, ring, cmd, vel_his, act_his, done, obs, delay, cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std, clip, rec_obs_cond,
                          rec_act_clipped, rec_act_applied, rec_body, rec_torque, rec_obs_raw, rec_reward, rec_done, stats);
   eval_scenario_args(a, sc, step0);
+  eval_kicks_args(a, kk);
   for (int k = 0; k < steps; k++) {
     a.slot = (int)((step0 + k) % depth);
     a.row = k;
@@ -599,6 +614,12 @@ static int eval_rollout_steps(const char *who, IRRL_EVAL_PARAMS, const irrl_eval
       g_err = std::string(who) + ": policy step refused its arguments"; return 1;
     }
     hipLaunchKernelGGL(irrl_eval_action_kernel, eval_grid(n * 12), dim3(256), 0, h->stream, a);
+    if (kk) {     // a step whose row fires: the kick, on the state the previous step (or the reset) left
+      const int r = irrl_eval_kick_row(a, a.t);
+      if (r >= 0)
+        hipLaunchKernelGGL(irrl_eval_perturb_kernel, eval_grid(n), dim3(256), 0, h->stream, n, a.kick_table + (size_t)r * (size_t)n * IRRL_EVAL_KICK_DIM, h->S.gc,
+                           h->S.gv);
+    }
     launch_step(h, h->P, (const float *)w.applied, obs, w.reward, done, w.extra);
     hipLaunchKernelGGL(sc ? irrl_eval_record_kernel<true> : irrl_eval_record_kernel<false>, eval_grid(n * 35), dim3(256), 0, h->stream, a);
   }
@@ -606,10 +627,37 @@ static int eval_rollout_steps(const char *who, IRRL_EVAL_PARAMS, const irrl_eval
   return 0;
 }
 int irrl_lstm_eval_rollout(IRRL_EVAL_PARAMS, void *hip_stream) {
-  return eval_rollout_steps("irrl_lstm_eval_rollout", IRRL_EVAL_FORWARD, nullptr, hip_stream);
+  return eval_rollout_steps("irrl_lstm_eval_rollout", IRRL_EVAL_FORWARD, nullptr, nullptr, hip_stream);
 }
 int irrl_lstm_eval_scenario(IRRL_EVAL_PARAMS, const irrl_eval_scenario *scenario, void *hip_stream) {
-  return eval_rollout_steps("irrl_lstm_eval_scenario", IRRL_EVAL_FORWARD, scenario, hip_stream);
+  return eval_rollout_steps("irrl_lstm_eval_scenario", IRRL_EVAL_FORWARD, scenario, nullptr, hip_stream);
+}
+int irrl_lstm_eval_perturbed(IRRL_EVAL_PARAMS, const irrl_eval_scenario *scenario, const irrl_eval_kicks *kicks, void *hip_stream) {
+  return eval_rollout_steps("irrl_lstm_eval_perturbed", IRRL_EVAL_FORWARD, scenario, kicks, hip_stream);
+}
+// one kick row per env on the pool now (the same kernel), stream-ordered on the pool's stream
+int irrl_env_perturb_base(irrl_env *h, const float *rows) {
+  if (!h) { g_err = "irrl_env_perturb_base: NULL handle"; return 1; }
+  if (!rows) { g_err = "irrl_env_perturb_base: NULL rows"; return 1; }
+  if (need_init(h)) return 1;
+  if (use_device(h)) return 1;
+  hipLaunchKernelGGL(irrl_eval_perturb_kernel, eval_grid(h->P.n_envs), dim3(256), 0, h->stream, h->P.n_envs, rows, h->S.gc, h->S.gv);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+int irrl_env_perturb_base_host(irrl_env *h, const float *rows) {
+  if (!h) { g_err = "irrl_env_perturb_base_host: NULL handle"; return 1; }
+  if (!rows) { g_err = "irrl_env_perturb_base_host: NULL rows"; return 1; }
+  if (need_init(h)) return 1;
+  HIP_TRY(hipSetDevice(h->device));
+  // through the pinned staging buffer into the handle's device scratch (the path of irrl_env_set_contact_coeff_host)
+  const size_t bytes = (size_t)h->P.n_envs * IRRL_EVAL_KICK_DIM * 4;
+  std::memcpy(h->h_pinned, rows, bytes);
+  HIP_TRY(hipMemcpyAsync(h->d_scratch, h->h_pinned, bytes, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(irrl_eval_perturb_kernel, eval_grid(h->P.n_envs), dim3(256), 0, h->stream, h->P.n_envs, (const float *)h->d_scratch, h->S.gc, h->S.gv);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return 0;
 }
 
 // THE SAME LOOP AS ONE PERSISTENT LAUNCH (csrc/env_eval_kernels.hpp: a wave keeps its four robots for all `steps`): exists where the actor-wave
@@ -620,10 +668,11 @@ int irrl_lstm_eval_rollout_supports(irrl_env *h, int hid) {
   if (!h) { g_err = "irrl_lstm_eval_rollout_supports: NULL handle"; return -1; }
   return rollout_one_tile(h, hid) ? 1 : 0;
 }
-static int eval_rollout_one_launch(const char *who, IRRL_EVAL_PARAMS, const irrl_eval_scenario *sc, void *hip_stream) {
+static int eval_rollout_one_launch(const char *who, IRRL_EVAL_PARAMS, const irrl_eval_scenario *sc, const irrl_eval_kicks *kk, void *hip_stream) {
   if (eval_rollout_check(who, h, steps, step0, hid, ob_dim, act_dim, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, depth, ring, cmd, vel_his, act_his, lstm_state, done,
                          obs, work, delay, cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std)) return 1;
   if (eval_scenario_check(who, sc)) return 1;
+  if (eval_kicks_check(who, kk)) return 1;
   if (need_init(h)) return 1;
   // which condition keeps the kernel from this pool / network (settings only: nothing is launched)
   if (hid != 48) { g_err = std::string(who) + ": the persistent kernel exists for hid 48 only (this policy has hid " + std::to_string(hid) + ")"; return 1; }
@@ -642,6 +691,7 @@ static int eval_rollout_one_launch(const char *who, IRRL_EVAL_PARAMS, const irrl
   EvalArgs a = eval_args(h, w, depth, ring, cmd, vel_his, act_his, done, obs, delay, cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std, clip, rec_obs_cond,
                          rec_act_clipped, rec_act_applied, rec_body, rec_torque, rec_obs_raw, rec_reward, rec_done, stats);
   eval_scenario_args(a, sc, step0);
+  eval_kicks_args(a, kk);
   a.slot = (int)(step0 % depth);
   a.steps = steps;
   // the actor alone, deterministic, no rollout rows: `value` and the critic's half of lstm_state are not written
@@ -652,10 +702,13 @@ static int eval_rollout_one_launch(const char *who, IRRL_EVAL_PARAMS, const irrl
   return 0;
 }
 int irrl_lstm_eval_rollout_persistent(IRRL_EVAL_PARAMS, void *hip_stream) {
-  return eval_rollout_one_launch("irrl_lstm_eval_rollout_persistent", IRRL_EVAL_FORWARD, nullptr, hip_stream);
+  return eval_rollout_one_launch("irrl_lstm_eval_rollout_persistent", IRRL_EVAL_FORWARD, nullptr, nullptr, hip_stream);
 }
 int irrl_lstm_eval_scenario_persistent(IRRL_EVAL_PARAMS, const irrl_eval_scenario *scenario, void *hip_stream) {
-  return eval_rollout_one_launch("irrl_lstm_eval_scenario_persistent", IRRL_EVAL_FORWARD, scenario, hip_stream);
+  return eval_rollout_one_launch("irrl_lstm_eval_scenario_persistent", IRRL_EVAL_FORWARD, scenario, nullptr, hip_stream);
+}
+int irrl_lstm_eval_perturbed_persistent(IRRL_EVAL_PARAMS, const irrl_eval_scenario *scenario, const irrl_eval_kicks *kicks, void *hip_stream) {
+  return eval_rollout_one_launch("irrl_lstm_eval_perturbed_persistent", IRRL_EVAL_FORWARD, scenario, kicks, hip_stream);
 }
 
 // irrl_mlp_rollout_supports: which `fuse` modes exist for this pool (the twin of irrl_lstm_rollout_supports; fuse 2 falls back inside the call)

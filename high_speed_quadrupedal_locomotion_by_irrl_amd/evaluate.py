@@ -9,6 +9,8 @@ rate / action low-passes, command ramp) without a host round trip per control st
                       evaluation loop (the test harnesses and tools translate their cases into one call of it)
   body_statistics     the statistics of a [frames, 13] body recording, of this build's loops and of the reference's simulator logs alike
   robustness_sweep    friction x delay x command grid in ONE Manual-mode pool -> one row of statistics per condition
+  perturbation_study  the reference's perturbation exploration (Exp_Raw_Data/Param-*.txt): friction x delay conditions x explorations in ONE pool,
+                      a warm-up, one random kick of every robot's base state, then the frames over which the ensemble converges or falls
 
 Semantics of control step t (global counter, carried across `run` calls), per env:
    cmd = (1 - a_cmd) cmd + a_cmd cmd_target;  ring[t % D] = obs;  o = ring[(t - delay) mod D];
@@ -22,6 +24,10 @@ tau = max(t - t0, 0): cmd_target of step t is row min(tau // cmd_every, S - 1) o
 the heading hold (heading_hold: the script's `--dir_fd`) replaces o[2] by the scaled output of a PI loop on the base yaw in front of the step,
 err = wrap(ref - yaw), I = clip(I + err dt, -W, W), out = kp err + ki I, I = 0 where done; the frame of step t goes to statistics bucket
 min(tau // stat_every, B - 1).
+
+A kick table (set_scenario's / reference_rollout's kicks, kick_first, kick_every; kick_rows, apply_kick, exploration_kicks, perturbation_study):
+row r of kicks [R, N, 11] displaces the robots' base state at the start of env step t = t0 + kick_first + r kick_every -- behind the actor and the
+action filter of step t, on the state step t - 1 left; see kick_rows for the row and apply_kick for the arithmetic.
 """
 import ctypes as C
 import math
@@ -146,6 +152,151 @@ def schedule_row(t, t0, every, rows):
     return min(max(int(t) - int(t0), 0) // int(every), int(rows) - 1)
 
 
+# ---- the kick table: base-state displacements at chosen control steps (include/irrl_env.h irrl_eval_kicks; csrc/eval_elements.hpp) ----
+KICK_DIM = 11            # IRRL_EVAL_KICK_DIM: dz | dq w x y z | dv x y z | dw x y z
+# the perturbation amplitudes of the reference's Exp_Raw_Data/Param-*.txt, in the files' order
+NOISE_KEYS = ("z_noise", "roll_noise", "pitch_noise", "x_dot_noise", "y_dot_noise", "z_dot_noise", "roll_dot_noise", "pitch_dot_noise", "yaw_dot_noise")
+
+
+def quaternion_product(a, b):
+    """a (x) b for quaternions [..., 4] = w x y z (Hamilton), float64"""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    aw, ax, ay, az = a[..., 0], a[..., 1], a[..., 2], a[..., 3]
+    bw, bx, by, bz = b[..., 0], b[..., 1], b[..., 2], b[..., 3]
+    return np.stack([aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+                     aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw], -1)
+
+
+def rotation_matrix(q):
+    """q [..., 4] = w x y z (unit) -> R [..., 3, 3], body -> world"""
+    q = np.asarray(q, np.float64)
+    w, x, y, z = q[..., 0], q[..., 1], q[..., 2], q[..., 3]
+    return np.stack([np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)], -1),
+                     np.stack([2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)], -1),
+                     np.stack([2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], -1)], -2)
+
+
+def kick_rows(dz=0.0, roll=0.0, pitch=0.0, yaw=0.0, dv=(0.0, 0.0, 0.0), dw=(0.0, 0.0, 0.0)):
+    """Kick rows [..., 11] float32 = dz | dq_w dq_x dq_y dq_z | dv_x dv_y dv_z | dw_x dw_y dw_z from increments that broadcast against each other
+    (dz, roll, pitch, yaw: [...]; dv, dw: [..., 3]).  Everything is BODY-FRAME: with q the base quaternion and R(q) its rotation matrix before
+    the kick, z += dz, v_world += R(q) dv, w_world += R(q) dw, q = normalised(q (x) dq).  Convention of dq, computed here in float64 (the device
+    does no trigonometry): dq = q_z(yaw) (x) q_y(pitch) (x) q_x(roll) with q_x(a) = (cos a/2, sin a/2, 0, 0) etc. -- intrinsic z-y'-x'', i.e. the
+    roll / pitch / yaw of body_frame() applied to an upright base give back these three angles.  All angles zero is the IDENTITY kick
+    dq = (1, 0, 0, 0), a real kick (it renormalises q).  "No kick for this env" is a row whose four dq words are zero: np.zeros(11)."""
+    dz, roll, pitch, yaw = (np.asarray(v, np.float64) for v in (dz, roll, pitch, yaw))
+    dv, dw = np.asarray(dv, np.float64), np.asarray(dw, np.float64)
+    if dv.shape[-1:] != (3,) or dw.shape[-1:] != (3,):
+        raise ValueError("dv and dw end in an axis of 3")
+    shape = np.broadcast_shapes(dz.shape, roll.shape, pitch.shape, yaw.shape, dv.shape[:-1], dw.shape[:-1])
+    half = lambda a: np.broadcast_to(a, shape) / 2.0
+    zero = np.zeros(shape)
+    qx = np.stack([np.cos(half(roll)), np.sin(half(roll)), zero, zero], -1)
+    qy = np.stack([np.cos(half(pitch)), zero, np.sin(half(pitch)), zero], -1)
+    qz = np.stack([np.cos(half(yaw)), zero, zero, np.sin(half(yaw))], -1)
+    out = np.zeros(shape + (KICK_DIM,))
+    out[..., 0] = np.broadcast_to(dz, shape)
+    out[..., 1:5] = quaternion_product(quaternion_product(qz, qy), qx)
+    out[..., 5:8] = np.broadcast_to(dv, shape + (3,))
+    out[..., 8:11] = np.broadcast_to(dw, shape + (3,))
+    return out.astype(np.float32)
+
+
+def kick_on(rows):
+    """which kick rows [..., 11] displace their env: the ones with a non-zero dq word"""
+    return np.any(np.asarray(rows)[..., 1:5] != 0, -1)
+
+
+def apply_kick(state_rows, rows):
+    """The float64 twin of the device's kick (csrc/eval_elements.hpp irrl_eval_kick_apply): state_rows [n, 288] (get_state), rows [n, 11] -> a new
+    [n, 288] with gc[2], gc[3:7], gv[0:3], gv[3:6] of the envs whose row is on (kick_on) displaced; everything else, and every env whose row is off,
+    is a copy."""
+    s = np.array(state_rows, np.float64)
+    k = np.asarray(rows, np.float64)
+    if s.ndim != 2 or k.shape != (s.shape[0], KICK_DIM):
+        raise ValueError("apply_kick: state rows [n, 288] and kick rows [n, %d]" % KICK_DIM)
+    on = kick_on(k)
+    q = s[:, _S_GC + 3:_S_GC + 7]
+    R = rotation_matrix(q)
+    z = s[:, _S_GC + 2] + k[:, 0]
+    v = s[:, _S_GV:_S_GV + 3] + np.einsum("nij,nj->ni", R, k[:, 5:8])
+    w = s[:, _S_GV + 3:_S_GV + 6] + np.einsum("nij,nj->ni", R, k[:, 8:11])
+    qn = quaternion_product(q, k[:, 1:5])
+    norm = np.sqrt((qn * qn).sum(-1, keepdims=True))
+    qn = qn / np.where(norm > 0, norm, 1.0)
+    s[on, _S_GC + 2] = z[on]
+    s[on, _S_GC + 3:_S_GC + 7] = qn[on]
+    s[on, _S_GV:_S_GV + 3] = v[on]
+    s[on, _S_GV + 3:_S_GV + 6] = w[on]
+    return s
+
+
+def kick_row_index(t, t0, kick_first, kick_every, rows):
+    """the row of a kick table that fires at control step t, or -1: t >= t0 + kick_first and t - t0 - kick_first = r kick_every, 0 <= r < rows.
+    In t, not in tau = max(t - t0, 0): nothing fires in front of t0 + kick_first."""
+    d = int(t) - int(t0) - int(kick_first)
+    if d < 0 or d % int(kick_every) != 0 or d // int(kick_every) >= int(rows):
+        return -1
+    return d // int(kick_every)
+
+
+def _kick_table(kicks, n):
+    """[n, 11] or [R, n, 11] -> [R, n, 11] float32"""
+    k = np.asarray(kicks, np.float32)
+    if k.ndim == 2:
+        k = k[None]
+    if k.ndim != 3 or k.shape[0] < 1 or k.shape[1:] != (n, KICK_DIM):
+        raise ValueError("kicks must have shape (%d, %d) or (R, %d, %d) with R >= 1" % (n, KICK_DIM, n, KICK_DIM))
+    return np.ascontiguousarray(k)
+
+
+def _kick_schedule(kick_first, kick_every):
+    kick_first, kick_every = int(kick_first), int(kick_every)
+    if kick_first < 0 or kick_every < 1:
+        raise ValueError("kick_first >= 0 and kick_every >= 1")
+    return kick_first, kick_every
+
+
+def exploration_kicks(n, noise, rng):
+    """`n` random kick rows [n, 11] float32 of the reference's perturbation exploration: every component uniform in [-a, a] with a = noise[key] for
+    the keys of the Exp_Raw_Data/Param-*.txt files (NOISE_KEYS; a missing key is 0): z_noise -> dz, roll_noise / pitch_noise -> the attitude
+    increment (yaw is not perturbed), x_dot_noise / y_dot_noise / z_dot_noise -> dv, roll_dot_noise / pitch_dot_noise / yaw_dot_noise -> dw, all
+    body-frame (kick_rows).  rng: a numpy Generator; the nine components are drawn in the order of NOISE_KEYS, n values each, zero amplitudes
+    included, so a draw does not depend on which amplitudes are set.
+    The reference's exploration harness is not in its tree -- only the amplitudes are on record -- so the uniform distribution and the body frame
+    are THIS build's choice."""
+    unknown = sorted(set(noise) - set(NOISE_KEYS))
+    if unknown:
+        raise KeyError("unknown noise key(s) %s: choose from %s" % (unknown, list(NOISE_KEYS)))
+    n = int(n)
+    d = {}
+    for k in NOISE_KEYS:
+        a = float(noise.get(k, 0.0))
+        if a < 0:
+            raise ValueError("%s >= 0" % k)
+        d[k] = rng.uniform(-1.0, 1.0, n) * a
+    return kick_rows(dz=d["z_noise"], roll=d["roll_noise"], pitch=d["pitch_noise"], dv=np.stack([d["x_dot_noise"], d["y_dot_noise"], d["z_dot_noise"]], 1),
+                     dw=np.stack([d["roll_dot_noise"], d["pitch_dot_noise"], d["yaw_dot_noise"]], 1))
+
+
+def perturb_base(env_impl, rows):
+    """displace the robots of an initialised FlexibleGymEnv NOW, one kick row per env (kick_rows): rows a torch tensor [N, 11] float32 on the
+    pool's device (stream-ordered on the pool's stream, no synchronisation) or anything numpy takes (copied over; waits for the stream)"""
+    from . import _lib
+    from ._lib import ptr
+    n = env_impl.getNumOfEnvs()
+    lib = _lib.load()
+    if hasattr(rows, "is_cuda"):
+        import torch
+        if not rows.is_cuda or rows.dtype != torch.float32 or tuple(rows.shape) != (n, KICK_DIM) or not rows.is_contiguous():
+            raise TypeError("rows: a contiguous float32 tensor [%d, %d] on the pool's device" % (n, KICK_DIM))
+        _lib.check(lib.irrl_env_perturb_base(env_impl._h, ptr(rows)))
+    else:
+        k = np.ascontiguousarray(rows, np.float32)
+        if k.shape != (n, KICK_DIM):
+            raise TypeError("rows must have shape (%d, %d)" % (n, KICK_DIM))
+        _lib.check(lib.irrl_env_perturb_base_host(env_impl._h, k.ctypes.data_as(C.POINTER(C.c_float))))
+
+
 # ---- numpy float64 twin ----
 def condition_state(ob0, depth):
     """state of `condition` after a reset: the reset observation fills the whole delay line, command, history and heading integrator are zero"""
@@ -184,7 +335,7 @@ def condition(state, t, obs, delay, cmd_target, a_cmd, a_vel, mean3, std3, *, cm
 
 
 def reference_rollout(env, actor, env_cfg, delay, cmd, steps, cmd_hz=1.0, vel_hz=None, act_hz=None, mu=None, warm=0, mu_warm=0.8, depth=None, *,
-                      cmd_schedule=None, cmd_every=1, heading=None, t0=0):
+                      cmd_schedule=None, cmd_every=1, heading=None, t0=0, kicks=None, kick_first=0, kick_every=1):
     """The evaluation loop in numpy float64 around `env` (reset() -> ob, step(a) -> ob, reward, done, extra, get_state() -> [n, 288],
     set_contact_coeff([n, 3])) and `actor` (act(o [n, 35], done [n]) -> [n, 12], already clipped if it clips).
     mu [n]: friction per env (contact_material); env i runs on mu_warm until step warm[i] (a scalar or [n]) and on mu[i] from then on, warm[i] = 0:
@@ -194,7 +345,9 @@ def reference_rollout(env, actor, env_cfg, delay, cmd, steps, cmd_hz=1.0, vel_hz
     warm[i] : warm[i] + frames is the caller's slice.
     cmd_schedule [S, n] or [S, n, 3] with cmd_every and t0: the command schedule of PolicyEvaluator.set_scenario in place of `cmd`; heading: a
     heading_hold dict -- the yaw comes from env.get_state() in front of the step, in float64; the record gains heading_out [steps, n] (the PI
-    output, 0 where the hold is off)."""
+    output, 0 where the hold is off).
+    kicks [n, 11] or [R, n, 11] with kick_first, kick_every (and t0): row kick_row_index(t, ...) displaces the base state through apply_kick and
+    env.get_state() / env.set_state() behind the action filter of step t, in front of env.step."""
     n = env.n
     delay, depth = _delay_rows(delay, n, depth)
     target = _cmd_rows(cmd, n)
@@ -204,6 +357,9 @@ def reference_rollout(env, actor, env_cfg, delay, cmd, steps, cmd_hz=1.0, vel_hz
     heading = heading_parameters(heading, n, float(env_cfg["Omega"]) if heading is not None else 0.0, dt)
     a_cmd, a_vel, a_act = lowpass_alpha(dt, cmd_hz), lowpass_alpha(dt, vel_hz), lowpass_alpha(dt, act_hz)
     warm = _step_rows(warm, n, "warm")
+    if kicks is not None:
+        kicks = _kick_table(kicks, n)
+        kick_first, kick_every = _kick_schedule(kick_first, kick_every)
     if mu is not None:
         mu = np.broadcast_to(np.asarray(mu, np.float64), (n,))
         coeff = contact_material(np.where(warm == 0, mu, mu_warm))
@@ -230,6 +386,9 @@ def reference_rollout(env, actor, env_cfg, delay, cmd, steps, cmd_hz=1.0, vel_hz
             a = (1 - a_act) * act_his + a_act * a
         act_his = np.asarray(a, np.float64)
         rec["act_applied"][t] = a
+        r = kick_row_index(t, t0, kick_first, kick_every, len(kicks)) if kicks is not None else -1
+        if r >= 0:
+            env.set_state(apply_kick(env.get_state(), kicks[r]))
         ob, rew, done, _ = env.step(np.asarray(a, np.float32))
         s = env.get_state()
         rec["body"][t, :, 0:7] = s[:, _S_GC:_S_GC + 7]
@@ -335,6 +494,10 @@ class PolicyEvaluator(object):
         self.heading_int = torch.zeros(n, **f32)               # the heading hold's integrator I (evaluator state, like cmd)
         self._omega, self._dt = float(cfg["Omega"]), float(dt)
         self.scenario = None
+        # which C entry points `run` calls: "auto" = the narrowest list that takes what is installed (irrl_lstm_eval_rollout / _scenario /
+        # _perturbed); "perturbed" = always the kick table's, with NULL for what is not installed -- the same code path by construction (the
+        # narrower entry points are calls of the wider ones with NULL), which is what the tests hold them to
+        self.entry_points = "auto"
         self.t = 0
         self.reset()
 
@@ -351,13 +514,15 @@ class PolicyEvaluator(object):
         if self.scenario is not None:
             self.scenario["t0"] = self.scenario["t0_rel"]
 
-    def set_scenario(self, cmd_schedule=None, cmd_every=1, heading=None, stat_buckets=1, stat_every=1, t0=None):
+    def set_scenario(self, cmd_schedule=None, cmd_every=1, heading=None, stat_buckets=1, stat_every=1, t0=None, kicks=None, kick_first=0, kick_every=1):
         """Install a scenario (include/irrl_env.h irrl_eval_scenario) for the following `run` calls; with tau = max(t - t0, 0):
         cmd_schedule [S, N] (v_x) or [S, N, 3]: the command target of step t is row min(tau // cmd_every, S - 1) (None: the constructor's cmd);
         heading: a dict of ref, kp, ki (a scalar or [N] each) and windup (None: the config's Omega) -- heading_hold(...) --, the PI loop on the base
         yaw whose output the actor sees as element 2, for the envs with a non-zero gain (None: off);
         stat_buckets B, stat_every: the frame of step t goes to bucket min(tau // stat_every, B - 1) of `stats`, which becomes [B, 18, N] and starts
-        from zero; t0: the origin on the global step counter (default: the current self.t).  The heading integrator keeps its value."""
+        from zero; t0: the origin on the global step counter (default: the current self.t).  The heading integrator keeps its value.
+        kicks [N, 11] or [R, N, 11] (kick_rows) with kick_first, kick_every: row r displaces the base state of the envs whose row is on at the
+        start of env step t0 + kick_first + r kick_every (include/irrl_env.h irrl_eval_kicks; None: no kicks)."""
         import torch
         f32 = dict(device=self.dev, dtype=torch.float32)
         table = self.cmd_target.unsqueeze(0) if cmd_schedule is None else torch.from_numpy(_schedule_rows(cmd_schedule, self.n).astype(np.float32)).to(self.dev)
@@ -366,10 +531,13 @@ class PolicyEvaluator(object):
             raise ValueError("cmd_every, stat_buckets and stat_every are at least 1")
         h = heading_parameters(heading, self.n, self._omega, self._dt)
         t0 = int(self.t if t0 is None else t0)
+        if kicks is not None:
+            kick_first, kick_every = _kick_schedule(kick_first, kick_every)
+            kicks = dict(table=torch.from_numpy(_kick_table(kicks, self.n)).to(self.dev), first=kick_first, every=kick_every)
         self.scenario = dict(t0=t0, t0_rel=t0 - self.t, cmd_table=table.contiguous(), cmd_every=cmd_every, stat_buckets=stat_buckets,
                              stat_every=stat_every, heading=None if h is None else dict(
                                  {k: torch.from_numpy(h[k].astype(np.float32)).to(self.dev) for k in ("ref", "kp", "ki")},
-                                 windup=float(np.float32(h["windup"])), dt=float(np.float32(h["dt"]))))
+                                 windup=float(np.float32(h["windup"])), dt=float(np.float32(h["dt"]))), kicks=kicks)
         self.stats = torch.zeros(stat_buckets, len(STAT_SLOTS), self.n, device=self.dev, dtype=torch.float64)
 
     def clear_scenario(self):
@@ -387,6 +555,15 @@ class PolicyEvaluator(object):
                             stat_buckets=s["stat_buckets"], stat_every=s["stat_every"], heading_ref=raw(h and h["ref"]), heading_kp=raw(h and h["kp"]),
                             heading_ki=raw(h and h["ki"]), heading_int=raw(self.heading_int), heading_windup=h["windup"] if h else 0.0,
                             heading_dt=h["dt"] if h else 0.0)
+
+    def _kicks_struct(self):
+        from ._lib import EvalKicks, ptr
+        k = self.scenario["kicks"]
+        return EvalKicks(kick_rows=int(k["table"].shape[0]), kick_first=k["first"], kick_every=k["every"], kick_table=ptr(k["table"]).value)
+
+    def perturb_base(self, rows):
+        """displace the pool's robots now, one kick row per env (the module's perturb_base)"""
+        perturb_base(self.env, rows)
 
     @property
     def persistent_supported(self):
@@ -422,12 +599,18 @@ class PolicyEvaluator(object):
             warr = _lstm_weight_table(self.policy, self.dev)
             lib = _lib.load()
             one_launch = resolve_persistent(persistent, lambda: self.persistent_supported)
-            if self.scenario is None:
+            if self.entry_points not in ("auto", "perturbed"):
+                raise ValueError("entry_points is 'auto' or 'perturbed'")
+            has_kicks = self.scenario is not None and self.scenario["kicks"] is not None
+            struct = None if self.scenario is None else self._scenario_struct()
+            kstruct = self._kicks_struct() if has_kicks else None
+            raw = lambda st: None if st is None else C.cast(C.pointer(st), C.c_void_p)
+            if has_kicks or self.entry_points == "perturbed":  # the kick table's struct behind the scenario's
+                fn, scenario = (lib.irrl_lstm_eval_perturbed_persistent if one_launch else lib.irrl_lstm_eval_perturbed), (raw(struct), raw(kstruct))
+            elif self.scenario is not None:                    # the scenario entry points: the same list with the host struct in front of the stream
+                fn, scenario = (lib.irrl_lstm_eval_scenario_persistent if one_launch else lib.irrl_lstm_eval_scenario), (raw(struct),)
+            else:
                 fn, scenario = (lib.irrl_lstm_eval_rollout_persistent if one_launch else lib.irrl_lstm_eval_rollout), ()
-            else:                                              # the scenario entry points: the same list with the host struct in front of the stream
-                fn = lib.irrl_lstm_eval_scenario_persistent if one_launch else lib.irrl_lstm_eval_scenario
-                struct = self._scenario_struct()
-                scenario = (C.cast(C.pointer(struct), C.c_void_p),)
             _lib.check(fn(
                 self.env._h, steps, self.t, self.hid, 35, 12, warr, *_head_ptrs(self.policy), self.depth, ptr(self.ring), ptr(self.cmd), ptr(self.vel_his),
                 ptr(self.act_his), ptr(self.lstm_state), ptr(self.done), ptr(self.obs), ptr(self.work), ptr(self.delay), ptr(self.cmd_target),
@@ -532,6 +715,78 @@ def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=100
     st = ev.bucket_statistics()
     return [dict(mu=m, delay=d, cmd=c, level=l + 1, cmd_level=(l + 1) / levels * c, **{k: number(k, v[2 * l + 1, i]) for k, v in st.items()})
             for i, (m, d, c) in enumerate(grid) for l in range(levels)]
+
+
+def perturbation_study(model_or_policy, env_cfg, mus, delays, cmd, explorations, noise, warm_steps=1000, frames=1000, seed=0, record_body=False,
+                       persistent=PERSISTENT_DEFAULT, bucket_steps=None, cmd_hz=1.0, vel_hz=None, act_hz=None, clip=True, mu_warm=0.8, device=None, kicks=None):
+    """The reference's perturbation exploration (Exp_Raw_Data/Param-*.txt: NoE explorations of FoE control steps from a base state displaced by
+    z_noise, roll_noise, pitch_noise and the *_dot_noise amplitudes, per friction and observation delay) in ONE Manual-mode pool of
+    len(mus) x len(delays) x explorations envs, env index = (i_mu * len(delays) + i_delay) * explorations + i_exploration, command `cmd` (v_x).
+    `warm_steps` control steps on friction mu_warm (None: the condition's own from the start), then the condition's friction and ONE kick of every
+    robot (exploration_kicks(N, noise, default_rng(seed)), or the given kicks [N, 11]) at the start of step warm_steps, then `frames` steps.
+    Statistics buckets of bucket_steps control steps (default: frames; warm_steps >= bucket_steps): bucket 0 is the window in front of the kick,
+    buckets 1 .. follow it.  persistent: PolicyEvaluator.run's keyword.
+    -> list of one dict per (mu, delay): mu, delay, cmd, explorations, surviving (the fraction of explorations without a fall in the post-kick
+    buckets), falls [E] (post-kick), stats (dict of [B, E] arrays, bucket_statistics), kicks [E, 11] and, with record_body, body [frames, E, 13]
+    (the post-kick frames; the reference's figure scripts reshape theirs as [env, frame, exploration, ...])."""
+    import torch
+    import yaml
+    from . import __BLACKPANTHER_V55_RESOURCE_DIRECTORY__ as rsc
+    from .flexible_robot import FlexibleGymEnv
+    conditions = [(float(m), int(d)) for m in mus for d in delays]
+    E, warm_steps, frames = int(explorations), int(warm_steps), int(frames)
+    bucket_steps = frames if bucket_steps is None else int(bucket_steps)
+    if not conditions or E < 1 or frames < 1:
+        raise ValueError("empty study")
+    if bucket_steps < 1 or warm_steps < bucket_steps:
+        raise ValueError("1 <= bucket_steps <= warm_steps: bucket 0 is the window in front of the kick")
+    n = len(conditions) * E
+    kicks = exploration_kicks(n, noise, np.random.default_rng(seed)) if kicks is None else _kick_table(kicks, n)[0]
+    cfg = dict(env_cfg.get("environment", env_cfg))
+    cfg["num_envs"] = n
+    cfg["Manual"] = True
+    dev_index = torch.cuda.current_device() if device is None else int(device)
+    env = FlexibleGymEnv(rsc, yaml.safe_dump(cfg, default_flow_style=False, width=float("inf")), device=dev_index)
+    env.init()
+    policy = load_policy(model_or_policy, torch.device("cuda", dev_index))
+    mu_rows = np.repeat([c[0] for c in conditions], E)
+    coeff = contact_material(mu_rows if mu_warm is None else np.full(n, mu_warm))
+    env.SetContactCoefficient(coeff)
+    ev = PolicyEvaluator(env, policy, np.repeat([c[1] for c in conditions], E), np.full(n, float(cmd)), cmd_hz=cmd_hz, vel_hz=vel_hz, act_hz=act_hz, clip=clip)
+    post = -(-frames // bucket_steps)
+    # the origin one bucket in front of the kick: bucket 0 = steps warm_steps - bucket_steps .. warm_steps - 1, the kick fires at tau = bucket_steps
+    ev.set_scenario(stat_buckets=1 + post, stat_every=bucket_steps, t0=warm_steps - bucket_steps, kicks=kicks, kick_first=bucket_steps)
+    if warm_steps > bucket_steps:
+        ev.run(warm_steps - bucket_steps, accumulate=False, persistent=persistent)
+    ev.run(bucket_steps, persistent=persistent)
+    if mu_warm is not None:                                    # (the setter's copy is ordered on the pool's stream, behind the warm-up)
+        env.SetContactCoefficient(contact_material(mu_rows))
+    rec = ev.run(frames, record=("body",) if record_body else (), persistent=persistent)
+    st = ev.bucket_statistics()
+    body = rec["body"].cpu().numpy() if record_body else None
+    out = []
+    for i, (m, d) in enumerate(conditions):
+        sl = slice(i * E, (i + 1) * E)
+        falls = st["falls"][1:, sl].sum(0)
+        row = dict(mu=m, delay=d, cmd=float(cmd), explorations=E, surviving=float(np.mean(falls == 0)), falls=falls, stats={k: v[:, sl] for k, v in st.items()},
+                   kicks=kicks[sl])
+        if record_body:
+            row["body"] = body[:, sl]
+        out.append(row)
+    return out
+
+
+def perturbation_table(rows):
+    """one line per (mu, delay) of a perturbation_study: the surviving fraction, and the ensemble mean of v_x / z / pitch of the survivors in the
+    bucket in front of the kick and in the last one"""
+    out = ["%-6s %-5s %-5s %-5s %-9s " % ("mu", "delay", "cmd", "E", "surviving") + " ".join("%-12s" % k for k in ("vx_before", "vx_last", "z_before", "z_last",
+                                                                                                              "pitch_before", "pitch_last"))]
+    for r in rows:
+        up = r["falls"] == 0
+        m = lambda k, b: float(r["stats"][k][b, up].mean()) if up.any() else float("nan")
+        out.append("%-6g %-5d %-5g %-5d %-9.4f " % (r["mu"], r["delay"], r["cmd"], r["explorations"], r["surviving"])
+                   + " ".join("%+12.4f" % m(k, b) for k in ("vx_body_mean", "z_mean", "pitch_mean") for b in (0, -1)))
+    return "\n".join(out)
 
 
 def sweep_table(rows):

@@ -504,6 +504,51 @@ int irrl_lstm_eval_scenario_persistent(irrl_env *env, int steps, long long step0
                                        float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats, const irrl_eval_scenario *scenario,
                                        void *hip_stream);
 
+/* THE EVALUATION LOOP WITH A KICK TABLE: caller-specified displacements of the robots' base state at chosen control steps, the ingredient of the
+ * reference's perturbation exploration (Exp_Raw_Data/Param-*.txt: NoE explorations of FoE steps from a base state displaced by z_noise, roll_noise,
+ * pitch_noise, *_dot_noise).  Semantics in ONE text, csrc/eval_elements.hpp.  A kick row is IRRL_EVAL_KICK_DIM = 11 floats per env,
+ *   dz | dq_w dq_x dq_y dq_z | dv_x dv_y dv_z | dw_x dw_y dw_z
+ * body-frame: with q the base quaternion and R(q) its rotation matrix BEFORE the kick, all in f32,
+ *   z += dz;   v_w += R(q) dv  (gv[0:3]);   w_w += R(q) dw  (gv[3:6]);   q = (q (x) dq) / |q (x) dq|.
+ * x, y, the joints and every other array of the pool are untouched: what a set_state of those ten words would do.  A row whose four dq words are
+ * all zero is "no kick for this env": the env is untouched bit for bit whatever the other seven words are.  The identity kick is dq = (1, 0, 0, 0)
+ * with everything else zero; it is a real kick (it renormalises).  dq from roll / pitch / yaw increments is host work; the device does no
+ * trigonometry.
+ * Schedule: with t0 the scenario's where one is given and 0 otherwise, row r of kick_table (device f32 [kick_rows, N, 11]) fires at the control
+ * step t with t >= t0 + kick_first and t - t0 - kick_first = r kick_every, 0 <= r < kick_rows.  The kick hits at the start of env step t: after
+ * the actor and the action filter of step t, on the state that step t - 1 (or the reset) left; the actor first sees it in the observation of
+ * step t + 1 (plus the env's delay); the heading hold of step t reads the pre-kick quaternion.
+ * kicks == NULL is exactly irrl_lstm_eval_scenario[_persistent], which are calls of these with NULL.  Both forms leave bit-identical buffers; the
+ * five-launch form issues one extra launch (the kernel of irrl_env_perturb_base) at a step whose row fires and none elsewhere; the persistent one
+ * exists exactly where irrl_lstm_eval_rollout_supports says so, with no fallback inside the call.
+ * Refused before any HIP call, with the entry point's name in the text: kick_rows < 1, kick_every < 1, kick_first < 0, a NULL kick_table. */
+#define IRRL_EVAL_KICK_DIM 11
+typedef struct irrl_eval_kicks {
+  int kick_rows;
+  long long kick_first;
+  int kick_every;
+  const float *kick_table;
+} irrl_eval_kicks;
+int irrl_lstm_eval_perturbed(irrl_env *env, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *lstm_w, const float *pi_w,
+                             const float *pi_b, const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring, float *cmd, float *vel_his,
+                             float *act_his, float *lstm_state, uint8_t *done, float *obs, float *work, const int *delay, const float *cmd_target, float a_cmd,
+                             float a_vel, float a_act, const float *cmd_mean, const float *cmd_std, int clip, float *rec_obs_cond, float *rec_act_clipped,
+                             float *rec_act_applied, float *rec_body, float *rec_torque, float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats,
+                             const irrl_eval_scenario *scenario, const irrl_eval_kicks *kicks, void *hip_stream);
+int irrl_lstm_eval_perturbed_persistent(irrl_env *env, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *lstm_w,
+                                        const float *pi_w, const float *pi_b, const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring,
+                                        float *cmd, float *vel_his, float *act_his, float *lstm_state, uint8_t *done, float *obs, float *work, const int *delay,
+                                        const float *cmd_target, float a_cmd, float a_vel, float a_act, const float *cmd_mean, const float *cmd_std, int clip,
+                                        float *rec_obs_cond, float *rec_act_clipped, float *rec_act_applied, float *rec_body, float *rec_torque,
+                                        float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats, const irrl_eval_scenario *scenario,
+                                        const irrl_eval_kicks *kicks, void *hip_stream);
+/* One kick row per env applied to the pool NOW, stream-ordered on the pool's stream (the same device function; the kernel the five-launch form
+ * launches at a kick step): rows is device f32 [N, 11] (irrl_env_perturb_base) or host f32 [N, 11] (irrl_env_perturb_base_host, which waits for
+ * the stream).  Any pool kind and lane layout: only the pool's gc[2:7] and gv[0:6] are written.  A NULL handle or NULL rows is refused before
+ * any HIP call. */
+int irrl_env_perturb_base(irrl_env *env, const float *rows);
+int irrl_env_perturb_base_host(irrl_env *env, const float *rows);
+
 #ifdef __cplusplus
 }
 #endif

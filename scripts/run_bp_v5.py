@@ -10,6 +10,9 @@ reference's own (run_bp_v5.py:8-13), resolved by the compat packages at the repo
     python scripts/run_bp_v5.py --test --model data/..._final.pkl --cmd 1.5 --steps 2000   # headless evaluation
     python scripts/run_bp_v5.py --test --sweep --model data/..._final.pkl --sweep_mu 0.05,0.4,0.8 --sweep_delay 0,1,2,3,4,5 --sweep_cmd 1,2,3,4,5 \
         --warm 1000 --steps 2000 --out table.json                                          # robustness grid, device-resident
+    python scripts/run_bp_v5.py --test --sweep --model data/..._final.pkl --sweep_mu 0.8,0.1 --sweep_delay 0,1,2,3,4,5 --cmd 5 \
+        --perturb z=0.02,roll=0.25,pitch=0.25,z_dot=1,roll_dot=1,pitch_dot=1 --explorations 10000 --perturb_at 1000 --steps 1000 \
+        --out explorations.npz                                                             # perturbation exploration, device-resident
 
 `--test` keeps the evaluation LOOP of the reference (run_bp_v5.py:353-470: Manual-mode env, externally supplied command in
 obs[0:3], observation delay line, velocity / action low-pass filters, numpy LSTM actor, per-step records of joint state,
@@ -77,6 +80,22 @@ def parse_args(argv):
     p.add_argument("--step_steps", type=int, default=5000, help="--step: control steps per level (even)")
     p.add_argument("--dir_fd", dest="flag_dir_fd", action="store_true", default=False,
                    help="--test: direction feedback, a PI loop (kp 1, ki 0.1, clamp Omega) on the base yaw replaces the yaw-rate command")
+    # --test --sweep --perturb: the perturbation exploration of the reference's Exp_Raw_Data/Param-*.txt
+    def noise(s):
+        out = {}
+        for item in str(s).split(","):
+            if item == "":
+                continue
+            k, _, v = item.partition("=")
+            out[k.strip() + "_noise"] = float(v)
+        return out
+    p.add_argument("--perturb", type=noise, default=None,
+                   help="--sweep: random base-state kicks, amplitudes as key=value out of z, roll, pitch, x_dot, y_dot, z_dot, roll_dot, pitch_dot, yaw_dot "
+                        "(the Param files' *_noise keys): --explorations robots per (--sweep_mu, --sweep_delay) at the command --cmd, one kick each at step "
+                        "--perturb_at, then --steps control steps; one row per (mu, delay), kicks and statistics to the .npz --out")
+    p.add_argument("--explorations", type=int, default=1000, help="--perturb: explorations per condition (the Param files' NoE)")
+    p.add_argument("--perturb_at", type=int, default=1000, help="--perturb: the control step of the kick (the warm-up in front of it runs on friction 0.8)")
+    p.add_argument("--perturb_seed", type=int, default=0, help="--perturb: seed of the kicks")
     return p.parse_args(argv)
 
 
@@ -173,6 +192,30 @@ def run_sweep(args, cfg):
     return rows
 
 
+def run_perturb(args, cfg):
+    """--test --sweep --perturb: the perturbation exploration (evaluate.perturbation_study) -- every (friction, delay) condition x --explorations is
+    one env of ONE Manual-mode pool.  Prints one row per (mu, delay); writes the kicks and the per-bucket statistics to --out (.npz)."""
+    import numpy as np
+    from high_speed_quadrupedal_locomotion_by_irrl_amd.evaluate import PERSISTENT_DEFAULT, perturbation_study, perturbation_table
+    if args.trained_model is None:
+        raise SystemExit("model path can't be ignored during test mode (--model)")
+    none_if_off = lambda f: None if f >= 1.0e6 else f
+    bucket = min(args.perturb_at, args.steps)
+    rows = perturbation_study(args.trained_model, cfg["environment"], args.sweep_mu, args.sweep_delay, args.flag_fix_cmd, args.explorations, args.perturb,
+                              warm_steps=args.perturb_at, frames=args.steps, seed=args.perturb_seed, bucket_steps=bucket, cmd_hz=args.cmd_filter_freq,
+                              vel_hz=none_if_off(args.vel_filter_freq), act_hz=none_if_off(args.act_filter_freq),
+                              persistent=PERSISTENT_DEFAULT if args.persistent is None else args.persistent)
+    print(perturbation_table(rows))
+    if args.out:
+        out = dict(mu=np.array([r["mu"] for r in rows]), delay=np.array([r["delay"] for r in rows]), cmd=np.array([r["cmd"] for r in rows]),
+                   surviving=np.array([r["surviving"] for r in rows]), falls=np.stack([r["falls"] for r in rows]), kicks=np.stack([r["kicks"] for r in rows]))
+        for k in rows[0]["stats"]:
+            out["stat_" + k] = np.stack([r["stats"][k] for r in rows])        # [condition, bucket, exploration]
+        np.savez_compressed(args.out, **out)
+        print("kicks and statistics written to", args.out)
+    return rows
+
+
 def main(argv=None):
     import torch
     args = parse_args(argv)
@@ -194,6 +237,8 @@ def main(argv=None):
         else:
             torch.distributed.init_process_group(backend)
     if not args.train and not args.flag_output:
+        if args.sweep and args.perturb is not None:
+            return run_perturb(args, cfg)
         return run_sweep(args, cfg) if args.sweep else run_test(args, cfg)
     if args.num_envs:
         cfg["environment"]["num_envs"] = args.num_envs

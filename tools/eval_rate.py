@@ -12,6 +12,10 @@ process, same pool, interleaved A, B, A, B (A = five launches per step), statist
 
 --scenario (with --ab): every leg runs with a scenario installed (PolicyEvaluator.set_scenario: a 5-row command staircase over the timed steps, the
 heading hold on every env, 4 statistics buckets) through irrl_lstm_eval_scenario[_persistent].
+
+--kicks K (with --ab): every leg runs with a kick table installed (PolicyEvaluator.set_scenario(kicks=): a tenth of the reference's exploration
+amplitudes on every env, one row every K timed steps) through irrl_lstm_eval_perturbed[_persistent].  Another trajectory than the run without
+kicks, so only roughly comparable with it.
 """
 import argparse
 import json
@@ -43,6 +47,14 @@ def ab(args, env, pol, delays, cmds, out):
             if args.scenario:
                 ev.set_scenario(cmd_schedule=EV.staircase_schedule(cmds, 5), cmd_every=max(args.steps // 5, 1), heading=EV.heading_hold(n), stat_buckets=4,
                                 stat_every=max(args.steps // 4, 1), t0=50)
+            if args.kicks:
+                rows = max(args.steps // args.kicks, 1)
+                noise = dict(z_noise=0.002, roll_noise=0.025, pitch_noise=0.025, z_dot_noise=0.1, roll_dot_noise=0.1, pitch_dot_noise=0.1)
+                table = EV.exploration_kicks(rows * n, noise, np.random.default_rng(0)).reshape(rows, n, EV.KICK_DIM)
+                scn = ev.scenario or {}
+                ev.set_scenario(cmd_schedule=None if not args.scenario else EV.staircase_schedule(cmds, 5), cmd_every=scn.get("cmd_every", 1),
+                                heading=EV.heading_hold(n) if args.scenario else None, stat_buckets=scn.get("stat_buckets", 1),
+                                stat_every=scn.get("stat_every", 1), t0=50, kicks=table, kick_first=args.kicks // 2, kick_every=args.kicks)
             ev.run(50, record=record, accumulate=acc, persistent=persistent)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -65,6 +77,7 @@ def main():
     ap.add_argument("--host-steps", type=int, default=200)
     ap.add_argument("--no-statistics", action="store_true", help="--ab: one more pair of legs with neither recorders nor statistics (accumulate=False)")
     ap.add_argument("--scenario", action="store_true", help="--ab: a 5-row command schedule, the heading hold and 4 statistics buckets on every leg")
+    ap.add_argument("--kicks", type=int, default=0, help="--ab: a kick table on every leg, one row of small kicks for every env every K timed steps")
     ap.add_argument("--ab", action="store_true", help="five launches per step (A) against the persistent launch (B), interleaved A, B, A, B")
     args = ap.parse_args()
     n = args.envs
@@ -75,7 +88,7 @@ def main():
     env = FlexibleGymEnv(pkg.__BLACKPANTHER_V55_RESOURCE_DIRECTORY__, yaml.safe_dump(cfg, default_flow_style=False, width=float("inf")))
     env.init()
     env.SetContactCoefficient(EV.contact_material(mus))
-    out = {"envs": n, "scenario": bool(args.scenario)}
+    out = {"envs": n, "scenario": bool(args.scenario), "kicks": int(args.kicks)}
     if args.ab:
         return ab(args, env, pol, delays, cmds, out)
     for name, record in (("statistics only", ()), ("all recorders", tuple(EV.RECORDERS))):
