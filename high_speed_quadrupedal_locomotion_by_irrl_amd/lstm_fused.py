@@ -367,8 +367,9 @@ def policy_rollout(policy, env_impl, steps, obs, states, dones, rng, rollout, ou
 
 
 def mlp_policy_step_supported(policy, obs):
+    # ob_dim <= 64: a wave's LDS scratch holds its four robots' observation rows in 4 x 64 words (csrc/policy_step.hpp MlpWaveLds)
     return (obs.is_cuda and obs.dtype == torch.float32 and len(policy.pi_fc) == 2 and policy.pi_fc[0].w.shape[1] == 64
-            and policy.pi_fc[1].w.shape == (64, 64) and policy.act_dim <= 15)
+            and policy.pi_fc[1].w.shape == (64, 64) and policy.act_dim <= 15 and 0 < obs.shape[-1] <= 64)
 
 
 def mlp_policy_step(policy, obs, dones, noise=None, rng=None, rollout=None, out=None):
