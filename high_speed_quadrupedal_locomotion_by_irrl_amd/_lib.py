@@ -114,6 +114,12 @@ SIGNATURES = {
                                  + [fp, fp, C.c_int] + [vp] * 9 + [vp, vp, vp]),
     "irrl_lstm_eval_perturbed_persistent": (C.c_int, [vp, C.c_int, C.c_longlong] + [C.c_int] * 3 + [vp] * 6 + [C.c_int] + [vp] * 8 + [vp] * 2 + [C.c_float] * 3
                                             + [fp, fp, C.c_int] + [vp] * 9 + [vp, vp, vp]),
+    # both forms with the gait measurements: the kick call's list with `const irrl_eval_gait *` (EvalGait below; None = NULL = the kick call)
+    # behind the kicks
+    "irrl_lstm_eval_measured": (C.c_int, [vp, C.c_int, C.c_longlong] + [C.c_int] * 3 + [vp] * 6 + [C.c_int] + [vp] * 8 + [vp] * 2 + [C.c_float] * 3
+                                + [fp, fp, C.c_int] + [vp] * 9 + [vp, vp, vp, vp]),
+    "irrl_lstm_eval_measured_persistent": (C.c_int, [vp, C.c_int, C.c_longlong] + [C.c_int] * 3 + [vp] * 6 + [C.c_int] + [vp] * 8 + [vp] * 2 + [C.c_float] * 3
+                                           + [fp, fp, C.c_int] + [vp] * 9 + [vp, vp, vp, vp]),
     # one kick row per env on the pool now: device rows [N, 11] / host rows
     "irrl_env_perturb_base": (C.c_int, [vp, vp]),
     "irrl_env_perturb_base_host": (C.c_int, [vp, fp]),
@@ -129,6 +135,12 @@ class EvalScenario(C.Structure):
 class EvalKicks(C.Structure):
     """struct irrl_eval_kicks of include/irrl_env.h (a HOST struct; kick_table a device pointer to [kick_rows, N, 11] f32); C.byref(...) or None"""
     _fields_ = [("kick_rows", C.c_int), ("kick_first", C.c_longlong), ("kick_every", C.c_int), ("kick_table", vp)]
+
+
+class EvalGait(C.Structure):
+    """struct irrl_eval_gait of include/irrl_env.h (a HOST struct of device pointers: gait f64 [stat_buckets, IRRL_EVAL_GAIT_COUNT, N], prev_contact u8
+    [N, 4], rec_gait f32 [steps, N, 32]); C.byref(...) or None"""
+    _fields_ = [("gait", vp), ("prev_contact", vp), ("rec_gait", vp)]
 
 
 def load():

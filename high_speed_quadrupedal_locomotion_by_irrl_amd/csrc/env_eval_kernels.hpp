@@ -31,6 +31,10 @@
 // before the scenario).
 // A kick table (irrl_lstm_eval_perturbed_persistent) adds, at the top of a step whose row fires, the kick on the lane context in every lane of
 // the robot (the env step's lane_carry then hands on the lead lane's kicked words); no LDS of its own.
+// The gait measurements (irrl_lstm_eval_measured_persistent) add, behind the env step, the robot's twelve torques and rates, its contact flags and
+// impulses -- three words per leg in sub-lane 0 of four quads -- into a wave scratch of their own (gsl, gcl); then lane r < 4
+// runs irrl_eval_gait_epilogue for robot r on its f64 column in LDS (gtl, handled at a bucket boundary and behind the last step as `st` is) and on the
+// robot's prev_contact bytes (pcl).  LDS: 163 264 B of 163 840 with them.
 // The critic is NOT run: the critic's half of lstm_state [N, 4 hid : 8 hid] and the `value` column of the work array are left untouched (the
 // actor never reads them, so calls of either form may follow each other).  HID 48, ob 35, act 12.
 __global__ void IRRL_ENV_BOUNDS
@@ -51,6 +55,13 @@ IRRL_RK(irrl_eval_persistent_kernel)(EnvParams P_, EnvState S_, float *ob, float
   __shared__ double stl[4][4 * NS];
   __shared__ float head_w[HID * 16];
   __shared__ float hdl[4][HD_FLOATS];
+  // the gait measurements: accumulators [4][IRRL_EVAL_GAIT_COUNT] | the lead lane's staging tq [4][12], qd [4][12], lam_w [4][12] per robot | contact flags |
+  // prev_contact (arrays of their own, see hdl)
+  constexpr int NGT = IRRL_EVAL_GAIT_COUNT, GS_FLOATS = 36;
+  __shared__ double gtl[4][4 * NGT];
+  __shared__ float gsl[4][4 * GS_FLOATS];
+  __shared__ int gcl[4][4 * 4];
+  __shared__ uint8_t pcl[4][4 * 4];
   __shared__ __attribute__((aligned(16))) float lds_w[LstmWaveImage<HID>::FLOATS];      // the ACTOR's operands, [gate column][K] (policy_step.hpp)
   lstm_wave_image_stage<HID, 256>(a, lds_w);
   for (int i = (int)threadIdx.x; i < HID * a.act_dim; i += 256) head_w[i] = a.pi_w[i];
@@ -140,7 +151,19 @@ IRRL_RK(irrl_eval_persistent_kernel)(EnvParams P_, EnvState S_, float *ob, float
   // and the bucket in `st` are NOT carried from step to step: a step of a call with a scenario recomputes the previous step's from the kernel
   // arguments, so that nothing but this word stays live across the env step for the scenario.  The scenario's
   // blocks are marked unlikely: block placement and the register allocator's spill weights then favour the step without one.
-  const int scn_ = __builtin_amdgcn_readfirstlane((ev.cmd_table ? 1 : 0) | (ev.stat_buckets > 1 ? 2 : 0) | (ev.heading_kp ? 4 : 0) | (ev.kick_table ? 8 : 0));
+  const int scn_ = __builtin_amdgcn_readfirstlane((ev.cmd_table ? 1 : 0) | (ev.stat_buckets > 1 ? 2 : 0) | (ev.heading_kp ? 4 : 0) | (ev.kick_table ? 8 : 0) |
+                                                     ((ev.gait || ev.rec_gait || ev.prev_contact) ? 16 : 0));
+  // the gait accumulators start from the caller's column of step 0's bucket, as `st` does; prev_contact comes in once
+  if (__builtin_expect((scn_ & 16) != 0, 0)) {
+    if (ev.gait) {
+      const int bucket0 = irrl_eval_stat_bucket(ev, irrl_eval_tau(ev, ev.t));
+      for (int i = lane0_; i < 4 * NGT; i += 64) {
+        const int r = i / NGT, s = i - r * NGT;
+        gtl[wave_][i] = (r < nrob_) ? ev.gait[((size_t)bucket0 * NGT + (size_t)s) * (size_t)a.N + (size_t)(e4_ + r)] : 0.0;
+      }
+    }
+    if (lane0_ < 16) pcl[wave_][lane0_] = (ev.prev_contact && lane0_ < nrob_ * 4) ? ev.prev_contact[(size_t)e4_ * 4 + lane0_] : (uint8_t)0;
+  }
   int slot_ = ev.slot;
   __syncthreads();   // the LDS image, the head weights and the wave's scratch have landed
   for (int k = 0; k < steps; k++) {
@@ -168,6 +191,19 @@ IRRL_RK(irrl_eval_persistent_kernel)(EnvParams P_, EnvState S_, float *ob, float
             const size_t col = (size_t)s * (size_t)ek.N + (size_t)(e4_ + r);
             ek.stats[(size_t)b_before * NS * (size_t)ek.N + col] = st[i];
             st[i] = ek.stats[(size_t)b * NS * (size_t)ek.N + col];
+          }
+          PS_WAVE_SYNC();
+        }
+      }
+      if (k > 0 && (scn_ & 18) == 18 && ek.gait) {     // the gait accumulators at the same boundary
+        const int b = irrl_eval_stat_bucket(ek, tau), b_before = irrl_eval_stat_bucket(ek, tau_before);
+        if (b != b_before) {
+          double *gt = gtl[wave_];
+          for (int i = lane; i < nrob_ * NGT; i += 64) {
+            const int r = i / NGT, s = i - r * NGT;
+            const size_t col = (size_t)s * (size_t)ek.N + (size_t)(e4_ + r);
+            ek.gait[(size_t)b_before * NGT * (size_t)ek.N + col] = gt[i];
+            gt[i] = ek.gait[(size_t)b * NGT * (size_t)ek.N + col];
           }
           PS_WAVE_SYNC();
         }
@@ -283,6 +319,31 @@ IRRL_RK(irrl_eval_persistent_kernel)(EnvParams P_, EnvState S_, float *ob, float
         if (i < nrob_ * 35) ek.rec_obs_raw[rowk * plane + (size_t)e4_ * 35 + (size_t)i] = ws[LAY::X + i];
       }
     }
+    // ---- 5b. the gait measurements, one block behind the env step (nothing of it inside step_compute or its Tail hook: the step without them
+    //          is then the parent's but for one scalar test here).  L is the FINAL lane context (the Tail hook's Lf, post-reset on a `done`):
+    //          every leg's sub-lane 0 of a robot that exists leaves its three torques, rates and impulses and its contact flag in the wave's
+    //          scratch, in the pool's order; then lane r < nrob_ owns robot r's column, prev_contact bytes and recorder row, and adds in the
+    //          five-launch kernel's index order (the done flag out of the scratch, as the actor reads it) ----
+    if (__builtin_expect((scn_ & 16) != 0, 0)) {
+      if (valid0_) {
+        float *gs = gsl[wave_] + rl_ * GS_FLOATS;
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+          gs[leg0_ * 3 + j] = L.tq[j]; gs[12 + leg0_ * 3 + j] = L.qd[j]; gs[24 + leg0_ * 3 + j] = L.lamw[j];
+        }
+        gcl[wave_][rl_ * 4 + leg0_] = L.in_contact;
+      }
+      PS_WAVE_SYNC();
+      if (lane < nrob_) {
+        const float *gs = gsl[wave_] + lane * GS_FLOATS;
+        const int *gc = gcl[wave_] + lane * 4;
+        if (ek.rec_gait)
+          irrl_eval_gait_record(ek.rec_gait + (rowk * (size_t)ek.N + (size_t)(e4_ + lane)) * IRRL_EVAL_GAIT_REC_DIM, gs, gs + 12, gc, gs + 24, ek.inv_control_dt);
+        irrl_eval_gait_epilogue(ws[LAY::DON + lane] != 0.0f, ek.gait ? gtl[wave_] + lane * NGT : nullptr, (size_t)1, ek.prev_contact ? pcl[wave_] + lane * 4 : nullptr,
+                                gs, gs + 12, gc, gs + 24, ek.inv_control_dt);
+      }
+      PS_WAVE_SYNC();
+    }
     slot_ = slot_ + 1 == ek.D ? 0 : slot_ + 1;
   }
   if (steps > 0) {
@@ -299,6 +360,16 @@ IRRL_RK(irrl_eval_persistent_kernel)(EnvParams P_, EnvState S_, float *ob, float
         const int r = i / NS, s = i - r * NS;
         ev.stats[((size_t)bucket1 * NS + (size_t)s) * (size_t)a.N + (size_t)(e4_ + r)] = st[i];
       }
+    }
+    if (__builtin_expect((scn_ & 16) != 0, 0)) {
+      if (ev.gait) {
+        const int bucket1 = irrl_eval_stat_bucket(ev, irrl_eval_tau(ev, ev.t + (long long)(steps - 1)));
+        for (int i = lane0_; i < nrob_ * NGT; i += 64) {
+          const int r = i / NGT, s = i - r * NGT;
+          ev.gait[((size_t)bucket1 * NGT + (size_t)s) * (size_t)a.N + (size_t)(e4_ + r)] = gtl[wave_][i];
+        }
+      }
+      if (ev.prev_contact && lane0_ < nrob_ * 4) ev.prev_contact[(size_t)e4_ * 4 + lane0_] = pcl[wave_][lane0_];
     }
     if (pok_) {      // the actor's LSTM state behind the last step (the critic's half is not touched)
 #pragma unroll

@@ -57,6 +57,13 @@ struct EvalArgs {
   int kick_rows, kick_every;        // read only where kick_table is set
   long long kick_first;
   const float *kick_table;          // [kick_rows, N, IRRL_EVAL_KICK_DIM] or NULL
+  // the gait measurements (irrl_eval_gait, include/irrl_env.h); all three NULL = none.  The buckets are the statistics' (stat_buckets, stat_every)
+  double *gait;                     // [stat_buckets, IRRL_EVAL_GAIT_COUNT, N] or NULL
+  uint8_t *prev_contact;            // [N, 4] the contact flags of the previous step (NULL with the recorder alone)
+  float *rec_gait;                  // [steps, N, IRRL_EVAL_GAIT_REC_DIM] or NULL
+  const int *in_contact;            // the pool (after the env step): [N, 4] contact flags, [N, 4, 3] world-frame impulses of the last substep
+  const float *lam_w;
+  float inv_control_dt;
 };
 
 // steps 1-6 of a control step for ONE element (env e, component j) of the observation: ring[slot] = raw, the delayed read, the rate low-pass,
@@ -207,4 +214,70 @@ static inline IRRL_EVAL_FN void irrl_eval_kick_apply(const float *k, float &pz, 
   x = qx * s;
   y = qy * s;
   z = qz * s;
+}
+
+// ---- the gait measurements: joint power, torque and ground-force sums, footfall pattern at control-step rate (irrl_eval_gait, include/irrl_env.h) ----
+// the four lam_w_z words of the recorder: the f32 product the GRFZ row widens
+static inline IRRL_EVAL_FN float irrl_eval_gait_fz(float lamw_z, float inv_control_dt) { return lamw_z * inv_control_dt; }
+// For ONE env, after the env step: tq / qd [12] (joint j = 3 leg + k; S.torque, gv[6:18]), in_contact [4], lamw [4][3] as the pool holds them, dn the
+// step's `done`.  g: the env's column of this step's bucket of `gait` (rows n words apart) or NULL; prev: the env's four prev_contact bytes or NULL.
+// A step that ends in `done` adds nothing and still sets prev := in_contact.  Every f32 word is widened to f64 first -- the products of two widened
+// words are exact -- and every sum is added in index order, so the rows N, P, PPOS, PNEG, STANCE, TOUCHDOWN, FLIGHT, GRFZ and the peaks of |tq|, |qd| are
+// the same on every machine; every square and every product that is rounded stands in a statement of its own (see the note on -ffp-contract at the top).
+static inline IRRL_EVAL_FN void irrl_eval_gait_epilogue(bool dn, double *g, size_t n, uint8_t *prev, const float *tq, const float *qd, const int *in_contact,
+                                                        const float *lamw, float inv_control_dt) {
+  if (g && !dn) {
+    double p = 0.0, ppos = 0.0, pneg = 0.0, tau2 = 0.0, tau2k = 0.0, ptau = 0.0, pqd = 0.0;
+    for (int j = 0; j < 12; j++) {
+      const double t = (double)tq[j], w = (double)qd[j];
+      const double tw = t * w;          // exact: 24 x 24 bits
+      p += tw;
+      if (tw > 0.0) ppos += tw;
+      if (tw < 0.0) pneg += tw;
+      const double tt = t * t;          // exact
+      if (j % 3 == 2) tau2k += tt; else tau2 += tt;
+      const double at = fabs(t), aw = fabs(w);
+      if (at > ptau) ptau = at;
+      if (aw > pqd) pqd = aw;
+    }
+    const double pp = p * p;
+    g[IRRL_EVAL_GAIT_N * n] += 1.0;
+    g[IRRL_EVAL_GAIT_P * n] += p;
+    g[IRRL_EVAL_GAIT_P2 * n] += pp;
+    g[IRRL_EVAL_GAIT_PPOS * n] += ppos;
+    g[IRRL_EVAL_GAIT_PNEG * n] += pneg;
+    g[IRRL_EVAL_GAIT_TAU2 * n] += tau2;
+    g[IRRL_EVAL_GAIT_TAU2_KNEE * n] += tau2k;
+    if (ptau > g[IRRL_EVAL_GAIT_PEAK_TAU * n]) g[IRRL_EVAL_GAIT_PEAK_TAU * n] = ptau;
+    if (pqd > g[IRRL_EVAL_GAIT_PEAK_QD * n]) g[IRRL_EVAL_GAIT_PEAK_QD * n] = pqd;
+    double grfz = 0.0, pgrf = 0.0;
+    bool any = false;
+    for (int l = 0; l < 4; l++) {
+      if (in_contact[l] == 0) continue;
+      any = true;
+      g[(IRRL_EVAL_GAIT_STANCE0 + l) * n] += 1.0;
+      if (prev && prev[l] == 0) g[(IRRL_EVAL_GAIT_TOUCHDOWN0 + l) * n] += 1.0;
+      const float fz = irrl_eval_gait_fz(lamw[l * 3 + 2], inv_control_dt);
+      grfz += (double)fz;
+      const double lx = (double)lamw[l * 3], ly = (double)lamw[l * 3 + 1], lz = (double)lamw[l * 3 + 2];
+      const double xx = lx * lx;
+      const double yy = ly * ly;
+      const double zz = lz * lz;
+      const double xy = xx + yy;
+      const double n2 = xy + zz;
+      const double nr = sqrt(n2);
+      const double f = nr * (double)inv_control_dt;
+      if (f > pgrf) pgrf = f;
+    }
+    if (!any) g[IRRL_EVAL_GAIT_FLIGHT * n] += 1.0;
+    g[IRRL_EVAL_GAIT_GRFZ * n] += grfz;
+    if (pgrf > g[IRRL_EVAL_GAIT_PEAK_GRF * n]) g[IRRL_EVAL_GAIT_PEAK_GRF * n] = pgrf;
+  }
+  if (prev)
+    for (int l = 0; l < 4; l++) prev[l] = in_contact[l] != 0 ? 1 : 0;
+}
+// the recorder's row of ONE env out of the same words: tq 12 | qd 12 | in_contact 4 | lam_w_z / control_dt 4
+static inline IRRL_EVAL_FN void irrl_eval_gait_record(float *r, const float *tq, const float *qd, const int *in_contact, const float *lamw, float inv_control_dt) {
+  for (int j = 0; j < 12; j++) { r[j] = tq[j]; r[12 + j] = qd[j]; }
+  for (int l = 0; l < 4; l++) { r[24 + l] = in_contact[l] != 0 ? 1.0f : 0.0f; r[28 + l] = irrl_eval_gait_fz(lamw[l * 3 + 2], inv_control_dt); }
 }

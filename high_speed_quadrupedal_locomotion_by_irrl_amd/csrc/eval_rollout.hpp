@@ -85,6 +85,15 @@ __global__ void __launch_bounds__(256) irrl_eval_record_kernel(const EvalArgs a)
   // the frame goes to this step's bucket of the statistics (no scenario: bucket 0, the whole buffer)
   const size_t bucket = SCN ? (size_t)irrl_eval_stat_bucket(a, irrl_eval_tau(a, a.t)) * (size_t)IRRL_EVAL_STAT_COUNT * (size_t)N : (size_t)0;
   irrl_eval_env_epilogue(dn != 0, a.cmd + e * 3, a.stats ? a.stats + bucket + e : nullptr, (size_t)N, gc[2], gc[3], gc[4], gc[5], gc[6], gv[0], gv[1], gv[2], gv[3], gv[4], gv[5]);
+  // the gait measurements (irrl_lstm_eval_measured): the same lane owns env e's column of `gait`, its prev_contact bytes and its recorder row
+  if (a.gait || a.rec_gait || a.prev_contact) {
+    const float *tq = a.torque + (size_t)e * 12, *lamw = a.lam_w + (size_t)e * 12;
+    const int *ic = a.in_contact + (size_t)e * 4;
+    if (a.rec_gait) irrl_eval_gait_record(a.rec_gait + (row * (size_t)N + (size_t)e) * IRRL_EVAL_GAIT_REC_DIM, tq, gv + 6, ic, lamw, a.inv_control_dt);
+    const size_t gbucket = SCN ? (size_t)irrl_eval_stat_bucket(a, irrl_eval_tau(a, a.t)) * (size_t)IRRL_EVAL_GAIT_COUNT * (size_t)N : (size_t)0;
+    irrl_eval_gait_epilogue(dn != 0, a.gait ? a.gait + gbucket + e : nullptr, (size_t)N, a.prev_contact ? a.prev_contact + (size_t)e * 4 : nullptr, tq, gv + 6, ic,
+                            lamw, a.inv_control_dt);
+  }
 }
 
 // a kick row per env on the pool's base state (irrl_env_perturb_base; the extra launch of irrl_lstm_eval_perturbed at a step whose row fires,

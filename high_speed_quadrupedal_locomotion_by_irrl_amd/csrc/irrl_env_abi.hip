@@ -579,7 +579,20 @@ static void eval_kicks_args(EvalArgs &a, const irrl_eval_kicks *kk) {
   if (!kk) return;
   a.kick_rows = kk->kick_rows; a.kick_every = kk->kick_every; a.kick_first = kk->kick_first; a.kick_table = kk->kick_table;
 }
-// the argument list the six evaluation entry points share, and its forwarding
+// the gait measurements of irrl_lstm_eval_measured[_persistent] (include/irrl_env.h): refused before any HIP call; NULL = none
+static int eval_gait_check(const char *who, const irrl_eval_gait *gg) {
+  if (!gg) return 0;
+  const std::string w = std::string(who) + ": gait: ";
+  if (!gg->gait && !gg->prev_contact && !gg->rec_gait) { g_err = w + "gait, prev_contact and rec_gait are all NULL (pass a NULL struct for no measurements)"; return 1; }
+  if (gg->gait && !gg->prev_contact) { g_err = w + "the accumulators need the contact flags of the previous step, prev_contact"; return 1; }
+  return 0;
+}
+static void eval_gait_args(EvalArgs &a, const irrl_env *h, const irrl_eval_gait *gg) {
+  if (!gg) return;
+  a.gait = gg->gait; a.prev_contact = gg->prev_contact; a.rec_gait = gg->rec_gait;
+  a.in_contact = h->S.in_contact; a.lam_w = h->S.lam_w; a.inv_control_dt = h->P.inv_control_dt;
+}
+// the argument list the eight evaluation entry points share, and its forwarding
 #define IRRL_EVAL_PARAMS                                                                                                                              \
   irrl_env *h, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *lstm_w, const float *pi_w, const float *pi_b,        \
       const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring, float *cmd, float *vel_his, float *act_his, float *lstm_state, \
@@ -590,11 +603,13 @@ static void eval_kicks_args(EvalArgs &a, const irrl_eval_kicks *kk) {
   h, steps, step0, hid, ob_dim, act_dim, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, depth, ring, cmd, vel_his, act_his, lstm_state, done, obs, work, delay, \
       cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std, clip, rec_obs_cond, rec_act_clipped, rec_act_applied, rec_body, rec_torque, rec_obs_raw,       \
       rec_reward, rec_done, stats
-static int eval_rollout_steps(const char *who, IRRL_EVAL_PARAMS, const irrl_eval_scenario *sc, const irrl_eval_kicks *kk, void *hip_stream) {
+static int eval_rollout_steps(const char *who, IRRL_EVAL_PARAMS, const irrl_eval_scenario *sc, const irrl_eval_kicks *kk, const irrl_eval_gait *gg,
+                              void *hip_stream) {
   if (eval_rollout_check(who, h, steps, step0, hid, ob_dim, act_dim, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, depth, ring, cmd, vel_his, act_his,
                          lstm_state, done, obs, work, delay, cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std)) return 1;
   if (eval_scenario_check(who, sc)) return 1;
   if (eval_kicks_check(who, kk)) return 1;
+  if (eval_gait_check(who, gg)) return 1;
   if (need_init(h)) return 1;
   HIP_TRY(hipSetDevice(h->device));
   h->stream = (hipStream_t)hip_stream;
@@ -604,6 +619,7 @@ static int eval_rollout_steps(const char *who, IRRL_EVAL_PARAMS, const irrl_eval
                          rec_act_clipped, rec_act_applied, rec_body, rec_torque, rec_obs_raw, rec_reward, rec_done, stats);
   eval_scenario_args(a, sc, step0);
   eval_kicks_args(a, kk);
+  eval_gait_args(a, h, gg);
   for (int k = 0; k < steps; k++) {
     a.slot = (int)((step0 + k) % depth);
     a.row = k;
@@ -627,13 +643,16 @@ static int eval_rollout_steps(const char *who, IRRL_EVAL_PARAMS, const irrl_eval
   return 0;
 }
 int irrl_lstm_eval_rollout(IRRL_EVAL_PARAMS, void *hip_stream) {
-  return eval_rollout_steps("irrl_lstm_eval_rollout", IRRL_EVAL_FORWARD, nullptr, nullptr, hip_stream);
+  return eval_rollout_steps("irrl_lstm_eval_rollout", IRRL_EVAL_FORWARD, nullptr, nullptr, nullptr, hip_stream);
 }
 int irrl_lstm_eval_scenario(IRRL_EVAL_PARAMS, const irrl_eval_scenario *scenario, void *hip_stream) {
-  return eval_rollout_steps("irrl_lstm_eval_scenario", IRRL_EVAL_FORWARD, scenario, nullptr, hip_stream);
+  return eval_rollout_steps("irrl_lstm_eval_scenario", IRRL_EVAL_FORWARD, scenario, nullptr, nullptr, hip_stream);
 }
 int irrl_lstm_eval_perturbed(IRRL_EVAL_PARAMS, const irrl_eval_scenario *scenario, const irrl_eval_kicks *kicks, void *hip_stream) {
-  return eval_rollout_steps("irrl_lstm_eval_perturbed", IRRL_EVAL_FORWARD, scenario, kicks, hip_stream);
+  return eval_rollout_steps("irrl_lstm_eval_perturbed", IRRL_EVAL_FORWARD, scenario, kicks, nullptr, hip_stream);
+}
+int irrl_lstm_eval_measured(IRRL_EVAL_PARAMS, const irrl_eval_scenario *scenario, const irrl_eval_kicks *kicks, const irrl_eval_gait *gait, void *hip_stream) {
+  return eval_rollout_steps("irrl_lstm_eval_measured", IRRL_EVAL_FORWARD, scenario, kicks, gait, hip_stream);
 }
 // one kick row per env on the pool now (the same kernel), stream-ordered on the pool's stream
 int irrl_env_perturb_base(irrl_env *h, const float *rows) {
@@ -668,11 +687,13 @@ int irrl_lstm_eval_rollout_supports(irrl_env *h, int hid) {
   if (!h) { g_err = "irrl_lstm_eval_rollout_supports: NULL handle"; return -1; }
   return rollout_one_tile(h, hid) ? 1 : 0;
 }
-static int eval_rollout_one_launch(const char *who, IRRL_EVAL_PARAMS, const irrl_eval_scenario *sc, const irrl_eval_kicks *kk, void *hip_stream) {
+static int eval_rollout_one_launch(const char *who, IRRL_EVAL_PARAMS, const irrl_eval_scenario *sc, const irrl_eval_kicks *kk, const irrl_eval_gait *gg,
+                              void *hip_stream) {
   if (eval_rollout_check(who, h, steps, step0, hid, ob_dim, act_dim, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, depth, ring, cmd, vel_his, act_his, lstm_state, done,
                          obs, work, delay, cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std)) return 1;
   if (eval_scenario_check(who, sc)) return 1;
   if (eval_kicks_check(who, kk)) return 1;
+  if (eval_gait_check(who, gg)) return 1;
   if (need_init(h)) return 1;
   // which condition keeps the kernel from this pool / network (settings only: nothing is launched)
   if (hid != 48) { g_err = std::string(who) + ": the persistent kernel exists for hid 48 only (this policy has hid " + std::to_string(hid) + ")"; return 1; }
@@ -692,6 +713,7 @@ static int eval_rollout_one_launch(const char *who, IRRL_EVAL_PARAMS, const irrl
                          rec_act_clipped, rec_act_applied, rec_body, rec_torque, rec_obs_raw, rec_reward, rec_done, stats);
   eval_scenario_args(a, sc, step0);
   eval_kicks_args(a, kk);
+  eval_gait_args(a, h, gg);
   a.slot = (int)(step0 % depth);
   a.steps = steps;
   // the actor alone, deterministic, no rollout rows: `value` and the critic's half of lstm_state are not written
@@ -702,13 +724,17 @@ static int eval_rollout_one_launch(const char *who, IRRL_EVAL_PARAMS, const irrl
   return 0;
 }
 int irrl_lstm_eval_rollout_persistent(IRRL_EVAL_PARAMS, void *hip_stream) {
-  return eval_rollout_one_launch("irrl_lstm_eval_rollout_persistent", IRRL_EVAL_FORWARD, nullptr, nullptr, hip_stream);
+  return eval_rollout_one_launch("irrl_lstm_eval_rollout_persistent", IRRL_EVAL_FORWARD, nullptr, nullptr, nullptr, hip_stream);
 }
 int irrl_lstm_eval_scenario_persistent(IRRL_EVAL_PARAMS, const irrl_eval_scenario *scenario, void *hip_stream) {
-  return eval_rollout_one_launch("irrl_lstm_eval_scenario_persistent", IRRL_EVAL_FORWARD, scenario, nullptr, hip_stream);
+  return eval_rollout_one_launch("irrl_lstm_eval_scenario_persistent", IRRL_EVAL_FORWARD, scenario, nullptr, nullptr, hip_stream);
 }
 int irrl_lstm_eval_perturbed_persistent(IRRL_EVAL_PARAMS, const irrl_eval_scenario *scenario, const irrl_eval_kicks *kicks, void *hip_stream) {
-  return eval_rollout_one_launch("irrl_lstm_eval_perturbed_persistent", IRRL_EVAL_FORWARD, scenario, kicks, hip_stream);
+  return eval_rollout_one_launch("irrl_lstm_eval_perturbed_persistent", IRRL_EVAL_FORWARD, scenario, kicks, nullptr, hip_stream);
+}
+int irrl_lstm_eval_measured_persistent(IRRL_EVAL_PARAMS, const irrl_eval_scenario *scenario, const irrl_eval_kicks *kicks, const irrl_eval_gait *gait,
+                                       void *hip_stream) {
+  return eval_rollout_one_launch("irrl_lstm_eval_measured_persistent", IRRL_EVAL_FORWARD, scenario, kicks, gait, hip_stream);
 }
 
 // irrl_mlp_rollout_supports: which `fuse` modes exist for this pool (the twin of irrl_lstm_rollout_supports; fuse 2 falls back inside the call)

@@ -28,6 +28,11 @@ min(tau // stat_every, B - 1).
 A kick table (set_scenario's / reference_rollout's kicks, kick_first, kick_every; kick_rows, apply_kick, exploration_kicks, perturbation_study):
 row r of kicks [R, N, 11] displaces the robots' base state at the start of env step t = t0 + kick_first + r kick_every -- behind the actor and the
 action filter of step t, on the state step t - 1 left; see kick_rows for the row and apply_kick for the arithmetic.
+
+Gait measurements (set_scenario's gait / measure_gait, run's "gait" recorder; gait_rows_numpy, gait_from_sums, reference_rollout's gait): behind
+every env step that does not end in `done`, the joint mechanical power sum_j tq_j qd_j, torque sums, contact flags and ground impulses of the pool
+are added to f64 sums [B, 20, N] in the statistics' buckets (Figure2.py:62-63, :198-222 of the reference: power and cost of transport per command
+level); see gait_from_sums for what comes out.
 """
 import ctypes as C
 import math
@@ -297,6 +302,129 @@ def perturb_base(env_impl, rows):
         _lib.check(lib.irrl_env_perturb_base_host(env_impl._h, k.ctypes.data_as(C.POINTER(C.c_float))))
 
 
+# ---- the gait measurements: joint power, cost of transport, footfall pattern (include/irrl_env.h irrl_eval_gait; csrc/eval_elements.hpp) ----
+# rows of the device sums (IRRL_EVAL_GAIT_*); the three peak_* rows are running maxima, every other row is a sum
+GAIT_SLOTS = ("n", "p", "p2", "ppos", "pneg", "tau2", "tau2_knee", "peak_tau", "peak_qd", "stance0", "stance1", "stance2", "stance3",
+              "touchdown0", "touchdown1", "touchdown2", "touchdown3", "flight", "grfz", "peak_grf")
+GAIT_PEAKS = tuple(GAIT_SLOTS.index(k) for k in ("peak_tau", "peak_qd", "peak_grf"))
+GAIT_REC_DIM = 32        # IRRL_EVAL_GAIT_REC_DIM: tq 12 | qd 12 | in_contact 4 | lam_w_z / control_dt 4
+_S_LAMW, _S_INCONTACT, _S_MASS = 135, 147, 154
+COT_VX_FLOOR = 0.05      # m/s: below this |mean v_x| a cost of transport is a division by noise, reported as NaN
+
+
+def gait_rows_numpy(rec_gait, rec_done, stat_buckets=1, stat_every=1, t=0, t0=0, prev_contact=None, sums=None, lamw=None, inv_control_dt=None):
+    """The float64 twin of the device's gait epilogue (csrc/eval_elements.hpp irrl_eval_gait_epilogue): rec_gait [T, N, 32] and rec_done [T, N] of
+    control steps t .. t + T - 1 -> (sums [stat_buckets, 20, N] float64 in the rows of GAIT_SLOTS, prev_contact [N, 4] uint8), with the bucket rule
+    of schedule_row(t, t0, stat_every, stat_buckets).  Sequential float64 adds in the device's order -- joints 0 .. 11, legs 0 .. 3, steps in
+    turn -- so the rows whose arithmetic is exact are the device's bit for bit.  prev_contact / sums: the state a previous call left (default: a
+    fresh evaluation, zeros).  The recorder holds only the z component of the impulse, so the peak_grf row needs lamw [T, N, 4, 3] (the pool's
+    lam_w) and inv_control_dt (float32); without them that row is NaN."""
+    rec = np.asarray(rec_gait)
+    done = np.asarray(rec_done).astype(bool)
+    T, N = done.shape
+    if rec.shape != (T, N, GAIT_REC_DIM):
+        raise ValueError("rec_gait [T, N, %d] and rec_done [T, N]" % GAIT_REC_DIM)
+    B = max(int(stat_buckets), 1)
+    G = {k: i for i, k in enumerate(GAIT_SLOTS)}
+    out = np.zeros((B, len(GAIT_SLOTS), N)) if sums is None else np.array(sums, np.float64).reshape(B, len(GAIT_SLOTS), N)
+    prev = np.zeros((N, 4), np.uint8) if prev_contact is None else np.array(prev_contact, np.uint8).reshape(N, 4)
+    tq, qd, fz = rec[:, :, 0:12].astype(np.float64), rec[:, :, 12:24].astype(np.float64), rec[:, :, 28:32].astype(np.float64)
+    contact = rec[:, :, 24:28] != 0
+    for k in range(T):
+        g = out[schedule_row(t + k, t0, stat_every, B)]
+        live = ~done[k]
+        p, ppos, pneg, tau2, tau2k, ptau, pqd = (np.zeros(N) for _ in range(7))
+        for j in range(12):
+            tw = tq[k, :, j] * qd[k, :, j]
+            p = p + tw
+            ppos = ppos + np.where(tw > 0, tw, 0.0)
+            pneg = pneg + np.where(tw < 0, tw, 0.0)
+            tt = tq[k, :, j] * tq[k, :, j]
+            if j % 3 == 2:
+                tau2k = tau2k + tt
+            else:
+                tau2 = tau2 + tt
+            ptau, pqd = np.maximum(ptau, np.abs(tq[k, :, j])), np.maximum(pqd, np.abs(qd[k, :, j]))
+        grfz, pgrf = np.zeros(N), np.zeros(N)
+        for l in range(4):
+            c = contact[k, :, l]
+            g[G["stance0"] + l] += np.where(live & c, 1.0, 0.0)
+            g[G["touchdown0"] + l] += np.where(live & c & (prev[:, l] == 0), 1.0, 0.0)
+            grfz = grfz + np.where(c, fz[k, :, l], 0.0)
+            if lamw is not None:
+                v = np.asarray(lamw)[k, :, l].astype(np.float64)
+                f = np.sqrt(v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1] + v[:, 2] * v[:, 2]) * np.float64(np.float32(inv_control_dt))
+                pgrf = np.maximum(pgrf, np.where(c, f, 0.0))
+        add = lambda key, v: g.__setitem__(G[key], g[G[key]] + np.where(live, v, 0.0))
+        peak = lambda key, v: g.__setitem__(G[key], np.maximum(g[G[key]], np.where(live, v, 0.0)))
+        add("n", 1.0); add("p", p); add("p2", p * p); add("ppos", ppos); add("pneg", pneg); add("tau2", tau2); add("tau2_knee", tau2k)
+        peak("peak_tau", ptau); peak("peak_qd", pqd)
+        add("flight", np.where(contact[k].any(1), 0.0, 1.0)); add("grfz", grfz); peak("peak_grf", pgrf)
+        prev = contact[k].astype(np.uint8)
+    if lamw is None:
+        out[:, G["peak_grf"]] = np.nan
+    return out, prev
+
+
+def gait_merge(sums):
+    """gait sums [B, 20, n] of several buckets -> [20, n] of the whole window: the sum rows added, the peak rows maximised"""
+    s = np.asarray(sums, np.float64)
+    if s.ndim == 2:
+        return s
+    out = s.sum(0)
+    for i in GAIT_PEAKS:
+        out[i] = s[:, i].max(0)
+    return out
+
+
+def gait_from_sums(sums, stats_sums, mass, control_dt, g=9.81, vx_floor=COT_VX_FLOOR):
+    """gait sums [20, n] (GAIT_SLOTS) and the body statistics' sums [18, n] (STAT_SLOTS) of the same window -> dict of [n] arrays:
+    power_mean, power_std (W, p = sum_j tq_j qd_j per control step: Figure2.py:62-63), power_pos, power_neg (mean positive / negative joint work
+    rate), cot = power_mean / (mass g mean v_x) (Figure2.py:198-222; NaN where |mean v_x| < vx_floor m/s or no frame was added), duty0 .. duty3
+    (stance frames / frames), stride_hz0 .. stride_hz3 (touchdowns / window seconds, the window being frames * control_dt), flight (fraction of
+    frames with no leg in contact), grfz_bw (mean of sum_legs lam_w_z / control_dt over mass g; see include/irrl_env.h for the unit), tau2_mean,
+    tau2_knee_mean (joint side; the knee motor sits behind a 1.55 reduction, Figure2.py:32-34), peak_tau, peak_qd, peak_grf, gait_frames.
+    mass: [n] or a scalar (the reference's figure uses m = 10, g = 9.8)."""
+    s = {k: np.asarray(sums[i], np.float64) for i, k in enumerate(GAIT_SLOTS)}
+    b = {k: np.asarray(stats_sums[i], np.float64) for i, k in enumerate(STAT_SLOTS)}
+    some = s["n"] > 0
+    cnt = np.maximum(s["n"], 1.0)
+    mass = np.broadcast_to(np.asarray(mass, np.float64), s["n"].shape)
+    weight = mass * float(g)
+    pm = s["p"] / cnt
+    vx = b["vx"] / np.maximum(b["n"], 1.0)
+    ok = some & (np.abs(vx) >= float(vx_floor))
+    out = {"power_mean": pm, "power_std": np.sqrt(np.maximum(s["p2"] / cnt - pm * pm, 0.0)), "power_pos": s["ppos"] / cnt, "power_neg": s["pneg"] / cnt,
+           "cot": np.where(ok, pm / (weight * np.where(ok, vx, 1.0)), np.nan)}
+    seconds = cnt * float(control_dt)
+    for l in range(4):
+        out["duty%d" % l] = s["stance%d" % l] / cnt
+        out["stride_hz%d" % l] = s["touchdown%d" % l] / seconds
+    out.update({"flight": s["flight"] / cnt, "grfz_bw": s["grfz"] / cnt / weight, "tau2_mean": s["tau2"] / cnt, "tau2_knee_mean": s["tau2_knee"] / cnt,
+                "peak_tau": s["peak_tau"], "peak_qd": s["peak_qd"], "peak_grf": s["peak_grf"], "gait_frames": s["n"].astype(np.int64)})
+    return out
+
+
+def gait_from_record(rec, lo, hi, mass, control_dt, g=9.81, vx_floor=COT_VX_FLOOR):
+    """gait_from_sums over the control steps lo .. hi - 1 of a reference_rollout(..., gait=True) record: the twin's sums of rec["gait"] / rec["done"]
+    (the contact flags of step lo - 1 as prev_contact) and the mean body-frame v_x of rec["body"] over the same steps"""
+    lo, hi = int(lo), int(hi)
+    prev = (np.asarray(rec["gait"])[lo - 1, :, 24:28] != 0).astype(np.uint8) if lo > 0 else None
+    sums, _ = gait_rows_numpy(rec["gait"][lo:hi], rec["done"][lo:hi], prev_contact=prev)
+    n = sums.shape[2]
+    body = np.zeros((len(STAT_SLOTS), n))
+    body[STAT_SLOTS.index("n")] = hi - lo
+    body[STAT_SLOTS.index("vx")] = [body_frame(np.asarray(rec["body"])[lo:hi, e])[0][:, 0].sum() for e in range(n)]
+    return gait_from_sums(sums[0], body, mass, control_dt, g, vx_floor)
+
+
+def gait_record_from_state(state_rows, control_dt):
+    """the recorder's 32 words [n, 32] float64 out of get_state() rows [n, 288]: torque | gv[6:18] | in_contact | lam_w_z / control_dt"""
+    s = np.asarray(state_rows, np.float64)
+    return np.concatenate([s[:, _S_TORQUE:_S_TORQUE + 12], s[:, _S_GV + 6:_S_GV + 18], (s[:, _S_INCONTACT:_S_INCONTACT + 4] != 0).astype(np.float64),
+                           s[:, _S_LAMW + 2:_S_LAMW + 12:3] / float(control_dt)], 1)
+
+
 # ---- numpy float64 twin ----
 def condition_state(ob0, depth):
     """state of `condition` after a reset: the reset observation fills the whole delay line, command, history and heading integrator are zero"""
@@ -335,7 +463,7 @@ def condition(state, t, obs, delay, cmd_target, a_cmd, a_vel, mean3, std3, *, cm
 
 
 def reference_rollout(env, actor, env_cfg, delay, cmd, steps, cmd_hz=1.0, vel_hz=None, act_hz=None, mu=None, warm=0, mu_warm=0.8, depth=None, *,
-                      cmd_schedule=None, cmd_every=1, heading=None, t0=0, kicks=None, kick_first=0, kick_every=1):
+                      cmd_schedule=None, cmd_every=1, heading=None, t0=0, kicks=None, kick_first=0, kick_every=1, gait=False):
     """The evaluation loop in numpy float64 around `env` (reset() -> ob, step(a) -> ob, reward, done, extra, get_state() -> [n, 288],
     set_contact_coeff([n, 3])) and `actor` (act(o [n, 35], done [n]) -> [n, 12], already clipped if it clips).
     mu [n]: friction per env (contact_material); env i runs on mu_warm until step warm[i] (a scalar or [n]) and on mu[i] from then on, warm[i] = 0:
@@ -347,7 +475,9 @@ def reference_rollout(env, actor, env_cfg, delay, cmd, steps, cmd_hz=1.0, vel_hz
     heading_hold dict -- the yaw comes from env.get_state() in front of the step, in float64; the record gains heading_out [steps, n] (the PI
     output, 0 where the hold is off).
     kicks [n, 11] or [R, n, 11] with kick_first, kick_every (and t0): row kick_row_index(t, ...) displaces the base state through apply_kick and
-    env.get_state() / env.set_state() behind the action filter of step t, in front of env.step."""
+    env.get_state() / env.set_state() behind the action filter of step t, in front of env.step.
+    gait: the record gains gait [steps, n, 32], the words of the device's rec_gait out of env.get_state() behind every step (gait_record_from_state;
+    feed it to gait_rows_numpy with the record's done)."""
     n = env.n
     delay, depth = _delay_rows(delay, n, depth)
     target = _cmd_rows(cmd, n)
@@ -371,6 +501,8 @@ def reference_rollout(env, actor, env_cfg, delay, cmd, steps, cmd_hz=1.0, vel_hz
     rec = dict(body=np.zeros((steps, n, 13)), torque=np.zeros((steps, n, 12)), obs_raw=np.zeros((steps, n, 35)), obs_cond=np.zeros((steps, n, 35)),
                act_clipped=np.zeros((steps, n, 12)), act_applied=np.zeros((steps, n, 12)), reward=np.zeros((steps, n)), done=np.zeros((steps, n), bool),
                heading_out=np.zeros((steps, n)))
+    if gait:
+        rec["gait"] = np.zeros((steps, n, GAIT_REC_DIM))
     for t in range(steps):
         switch = (warm == t) & (warm > 0)
         if mu is not None and switch.any():
@@ -394,6 +526,8 @@ def reference_rollout(env, actor, env_cfg, delay, cmd, steps, cmd_hz=1.0, vel_hz
         rec["body"][t, :, 0:7] = s[:, _S_GC:_S_GC + 7]
         rec["body"][t, :, 7:13] = s[:, _S_GV:_S_GV + 6]
         rec["torque"][t] = s[:, _S_TORQUE:_S_TORQUE + 12]
+        if gait:
+            rec["gait"][t] = gait_record_from_state(s, dt)
         rec["obs_raw"][t] = ob
         rec["reward"][t] = rew
         rec["done"][t] = done
@@ -493,10 +627,14 @@ class PolicyEvaluator(object):
         self.stats = torch.zeros(len(STAT_SLOTS), n, device=dev, dtype=torch.float64)
         self.heading_int = torch.zeros(n, **f32)               # the heading hold's integrator I (evaluator state, like cmd)
         self._omega, self._dt = float(cfg["Omega"]), float(dt)
+        # the gait measurements (set_scenario(gait=True)): f64 sums [B, 20, N] or None; the contact flags of the previous step (evaluator state)
+        self.gait = None
+        self.prev_contact = torch.zeros(n, 4, device=dev, dtype=torch.uint8)
         self.scenario = None
         # which C entry points `run` calls: "auto" = the narrowest list that takes what is installed (irrl_lstm_eval_rollout / _scenario /
-        # _perturbed); "perturbed" = always the kick table's, with NULL for what is not installed -- the same code path by construction (the
-        # narrower entry points are calls of the wider ones with NULL), which is what the tests hold them to
+        # _perturbed / _measured); "perturbed" = always the kick table's, "measured" = always the gait measurements', with NULL for what is not
+        # installed -- the same code path by construction (the narrower entry points are calls of the wider ones with NULL), which is what the
+        # tests hold them to
         self.entry_points = "auto"
         self.t = 0
         self.reset()
@@ -510,11 +648,13 @@ class PolicyEvaluator(object):
         for b in (self.cmd, self.vel_his, self.act_his, self.lstm_state, self.heading_int):
             b.zero_()
         self.done.zero_()
+        self.prev_contact.zero_()
         self.t = 0
         if self.scenario is not None:
             self.scenario["t0"] = self.scenario["t0_rel"]
 
-    def set_scenario(self, cmd_schedule=None, cmd_every=1, heading=None, stat_buckets=1, stat_every=1, t0=None, kicks=None, kick_first=0, kick_every=1):
+    def set_scenario(self, cmd_schedule=None, cmd_every=1, heading=None, stat_buckets=1, stat_every=1, t0=None, kicks=None, kick_first=0, kick_every=1,
+                     gait=False):
         """Install a scenario (include/irrl_env.h irrl_eval_scenario) for the following `run` calls; with tau = max(t - t0, 0):
         cmd_schedule [S, N] (v_x) or [S, N, 3]: the command target of step t is row min(tau // cmd_every, S - 1) (None: the constructor's cmd);
         heading: a dict of ref, kp, ki (a scalar or [N] each) and windup (None: the config's Omega) -- heading_hold(...) --, the PI loop on the base
@@ -522,7 +662,9 @@ class PolicyEvaluator(object):
         stat_buckets B, stat_every: the frame of step t goes to bucket min(tau // stat_every, B - 1) of `stats`, which becomes [B, 18, N] and starts
         from zero; t0: the origin on the global step counter (default: the current self.t).  The heading integrator keeps its value.
         kicks [N, 11] or [R, N, 11] (kick_rows) with kick_first, kick_every: row r displaces the base state of the envs whose row is on at the
-        start of env step t0 + kick_first + r kick_every (include/irrl_env.h irrl_eval_kicks; None: no kicks)."""
+        start of env step t0 + kick_first + r kick_every (include/irrl_env.h irrl_eval_kicks; None: no kicks).
+        gait: measure joint power, torque and ground-force sums and the footfall pattern (include/irrl_env.h irrl_eval_gait) into `gait`
+        [B, 20, N] (GAIT_SLOTS), bucketed like `stats` and zeroed here; read with gait_statistics / bucket_gait_statistics."""
         import torch
         f32 = dict(device=self.dev, dtype=torch.float32)
         table = self.cmd_target.unsqueeze(0) if cmd_schedule is None else torch.from_numpy(_schedule_rows(cmd_schedule, self.n).astype(np.float32)).to(self.dev)
@@ -539,12 +681,14 @@ class PolicyEvaluator(object):
                                  {k: torch.from_numpy(h[k].astype(np.float32)).to(self.dev) for k in ("ref", "kp", "ki")},
                                  windup=float(np.float32(h["windup"])), dt=float(np.float32(h["dt"]))), kicks=kicks)
         self.stats = torch.zeros(stat_buckets, len(STAT_SLOTS), self.n, device=self.dev, dtype=torch.float64)
+        self.gait = torch.zeros(stat_buckets, len(GAIT_SLOTS), self.n, device=self.dev, dtype=torch.float64) if gait else None
 
     def clear_scenario(self):
         """back to the constructor's constant command, no heading hold, one statistics window [18, N] (zeroed)"""
         import torch
         self.scenario = None
         self.stats = torch.zeros(len(STAT_SLOTS), self.n, device=self.dev, dtype=torch.float64)
+        self.gait = None
 
     def _scenario_struct(self):
         from ._lib import EvalScenario, ptr
@@ -577,7 +721,7 @@ class PolicyEvaluator(object):
 
     def run(self, steps, record=(), accumulate=True, persistent=False):
         """`steps` control steps from ONE C call (stream-ordered on torch's current stream, no synchronisation).  record: names out of
-        RECORDERS -> dict of device tensors [steps, N, .]; accumulate: add these steps' frames to the per-env statistics.
+        RECORDERS, and "gait" (rec_gait [steps, N, 32]: tq | qd | in_contact | lam_w_z / control_dt) -> dict of device tensors [steps, N, .]; accumulate: add these steps' frames to the per-env statistics.
         persistent: False = five launches per control step (every pool and policy; also steps the critic's half of lstm_state); True = the
         whole call as one persistent launch (raises with the library's text where the kernel does not exist); "auto" = the persistent launch
         where `persistent_supported`, else five launches per step.  The two forms leave bit-identical buffers -- except the critic's half of
@@ -587,25 +731,35 @@ class PolicyEvaluator(object):
         from ._lib import ptr
         from .lstm_fused import _head_ptrs, _lstm_weight_table
         steps = int(steps)
-        unknown = [k for k in record if k not in RECORDERS]
+        unknown = [k for k in record if k not in RECORDERS and k != "gait"]
         if unknown:
-            raise KeyError("unknown recorder(s) %s: choose from %s" % (unknown, sorted(RECORDERS)))
+            raise KeyError("unknown recorder(s) %s: choose from %s" % (unknown, sorted(RECORDERS) + ["gait"]))
         out = {}
         for k in record:
-            shape = (steps, self.n) + ((RECORDERS[k],) if RECORDERS[k] else ())
+            shape = (steps, self.n) + ((GAIT_REC_DIM,) if k == "gait" else (RECORDERS[k],) if RECORDERS[k] else ())
             out[k] = torch.empty(shape, device=self.dev, dtype=torch.bool if k == "done" else torch.float32)
         with torch.cuda.device(self.dev):
             self.policy.prepare()                              # the kernels' permuted weight copies follow the parameters (a learner may have stepped)
             warr = _lstm_weight_table(self.policy, self.dev)
             lib = _lib.load()
             one_launch = resolve_persistent(persistent, lambda: self.persistent_supported)
-            if self.entry_points not in ("auto", "perturbed"):
-                raise ValueError("entry_points is 'auto' or 'perturbed'")
+            if self.entry_points not in ("auto", "perturbed", "measured"):
+                raise ValueError("entry_points is 'auto', 'perturbed' or 'measured'")
             has_kicks = self.scenario is not None and self.scenario["kicks"] is not None
             struct = None if self.scenario is None else self._scenario_struct()
             kstruct = self._kicks_struct() if has_kicks else None
             raw = lambda st: None if st is None else C.cast(C.pointer(st), C.c_void_p)
-            if has_kicks or self.entry_points == "perturbed":  # the kick table's struct behind the scenario's
+            # the gait measurements: the sums where installed and accumulating, the recorder where asked for; with the sums installed prev_contact
+            # goes along through unmeasured steps too (a warm-up), so that the first measured step knows its predecessor's flags
+            gstruct = None
+            if self.gait is not None or "gait" in out:
+                gstruct = _lib.EvalGait(gait=ptr(self.gait).value if (self.gait is not None and accumulate) else None,
+                                        prev_contact=ptr(self.prev_contact).value if self.gait is not None else None,
+                                        rec_gait=ptr(out["gait"]).value if "gait" in out else None)
+            if gstruct is not None or self.entry_points == "measured":
+                fn = lib.irrl_lstm_eval_measured_persistent if one_launch else lib.irrl_lstm_eval_measured
+                scenario = (raw(struct), raw(kstruct), raw(gstruct))
+            elif has_kicks or self.entry_points == "perturbed":  # the kick table's struct behind the scenario's
                 fn, scenario = (lib.irrl_lstm_eval_perturbed_persistent if one_launch else lib.irrl_lstm_eval_perturbed), (raw(struct), raw(kstruct))
             elif self.scenario is not None:                    # the scenario entry points: the same list with the host struct in front of the stream
                 fn, scenario = (lib.irrl_lstm_eval_scenario_persistent if one_launch else lib.irrl_lstm_eval_scenario), (raw(struct),)
@@ -621,6 +775,38 @@ class PolicyEvaluator(object):
 
     def zero_statistics(self):
         self.stats.zero_()
+        if self.gait is not None:
+            self.gait.zero_()
+
+    def measure_gait(self, on=True):
+        """switch the gait measurements on (zeroed sums, one bucket per statistics bucket) or off without touching the scenario; set_scenario(...,
+        gait=True) is this behind the scenario's installation"""
+        import torch
+        buckets = self.stats.shape[0] if self.stats.dim() == 3 else 1
+        self.gait = torch.zeros(buckets, len(GAIT_SLOTS), self.n, device=self.dev, dtype=torch.float64) if on else None
+
+    def total_mass(self):
+        """per-env total mass [N] (trunk + 12 links, IRRL_S_MASS of get_state: randomised per env under StochasticDynamics)"""
+        return np.asarray(self.env.get_state(), np.float64)[:, _S_MASS:_S_MASS + 13].sum(1)
+
+    def _gait_sums(self):
+        if self.gait is None:
+            raise RuntimeError("no gait measurements installed: set_scenario(..., gait=True)")
+        sums, body = self.gait.cpu().numpy(), self.stats.cpu().numpy()
+        return sums, body if body.ndim == 3 else body[None]
+
+    def gait_statistics(self, mass=None, g=9.81):
+        """power, cost of transport and footfall statistics per env over the frames accumulated since zero_statistics() (synchronises): dict of [N]
+        numpy arrays, see gait_from_sums; mass: None = total_mass()"""
+        sums, body = self._gait_sums()
+        return gait_from_sums(gait_merge(sums), body.sum(0), self.total_mass() if mass is None else mass, self._dt, g)
+
+    def bucket_gait_statistics(self, mass=None, g=9.81):
+        """the same per bucket of the installed scenario: dict of [B, N] numpy arrays"""
+        sums, body = self._gait_sums()
+        mass = self.total_mass() if mass is None else mass
+        per = [gait_from_sums(s, b, mass, self._dt, g) for s, b in zip(sums, body)]
+        return {k: np.stack([p[k] for p in per], 0) for k in per[0]}
 
     def statistics(self):
         """per-env statistics over the frames accumulated since zero_statistics() (synchronises): dict of [N] numpy arrays, see statistics_from_sums"""
@@ -664,7 +850,8 @@ def load_policy(model_or_policy, device):
 
 
 def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=1000, steps=2000, cmd_hz=1.0, vel_hz=None, act_hz=None, clip=True,
-                     mu_warm=0.8, device=None, persistent=PERSISTENT_DEFAULT, levels=None, level_steps=None, heading=None):
+                     mu_warm=0.8, device=None, persistent=PERSISTENT_DEFAULT, levels=None, level_steps=None, heading=None, gait=False,
+                     mass=None, g=9.81):
     """The reference's robustness grid in one pool: len(mus) x len(delays) x len(cmds) Manual-mode envs (condition index = (i_mu * len(delays) +
     i_delay) * len(cmds) + i_cmd), `warm_steps` control steps on friction mu_warm, then `steps` on the condition's own friction over which the
     statistics are taken.  env_cfg: the `environment:` mapping of a config.  persistent: PolicyEvaluator.run's keyword (same statistics bit for bit
@@ -673,7 +860,9 @@ def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=100
     levels (with an even level_steps): the script's `--step` staircase in place of `steps` at the full command -- level l = 1 .. levels commands
     l / levels * cmd for level_steps control steps (the warm-up runs at level 1), the run is levels * level_steps steps, still ONE call, with two
     statistics buckets per level; -> one row per (condition, level), taken over the SECOND half of the level, with the keys `level` and
-    `cmd_level` (the commanded v_x of that level)."""
+    `cmd_level` (the commanded v_x of that level).
+    gait: every row gains the keys of gait_from_sums over the same frames -- cot, power_mean, duty0 .. 3, stride_hz0 .. 3, ... -- with `mass`
+    (None: each env's own total) and g; off, the rows are what they were."""
     import torch
     import yaml
     from . import __BLACKPANTHER_V55_RESOURCE_DIRECTORY__ as rsc
@@ -699,26 +888,31 @@ def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=100
         steps = levels * level_steps
         # the origin behind the warm-up: tau = 0 until then, so the warm-up runs at level 1 (and with the heading hold on)
         ev.set_scenario(cmd_schedule=staircase_schedule([g[2] for g in grid], levels), cmd_every=level_steps, heading=heading, stat_buckets=2 * levels,
-                        stat_every=level_steps // 2, t0=max(int(warm_steps), 0))
-    elif heading is not None:
-        ev.set_scenario(heading=heading)
+                        stat_every=level_steps // 2, t0=max(int(warm_steps), 0), gait=gait)
+    elif heading is not None or gait:
+        ev.set_scenario(heading=heading, gait=gait)
     if warm_steps > 0:
         ev.run(warm_steps, accumulate=False, persistent=persistent)
         coeff[:, 0] = [g[0] for g in grid]                     # (the setter's copy is ordered on the pool's stream, behind the warm-up)
         env.SetContactCoefficient(coeff)
     ev.zero_statistics()
     ev.run(steps, persistent=persistent)
-    number = lambda k, x: int(x) if k in ("falls", "frames") else float(x)
+    number = lambda k, x: int(x) if k in ("falls", "frames", "gait_frames") else float(x)
     if levels is None:
         st = ev.statistics()
+        if gait:
+            st.update(ev.gait_statistics(mass, g))
         return [dict(mu=m, delay=d, cmd=c, **{k: number(k, v[i]) for k, v in st.items()}) for i, (m, d, c) in enumerate(grid)]
     st = ev.bucket_statistics()
+    if gait:
+        st.update(ev.bucket_gait_statistics(mass, g))
     return [dict(mu=m, delay=d, cmd=c, level=l + 1, cmd_level=(l + 1) / levels * c, **{k: number(k, v[2 * l + 1, i]) for k, v in st.items()})
             for i, (m, d, c) in enumerate(grid) for l in range(levels)]
 
 
 def perturbation_study(model_or_policy, env_cfg, mus, delays, cmd, explorations, noise, warm_steps=1000, frames=1000, seed=0, record_body=False,
-                       persistent=PERSISTENT_DEFAULT, bucket_steps=None, cmd_hz=1.0, vel_hz=None, act_hz=None, clip=True, mu_warm=0.8, device=None, kicks=None):
+                       persistent=PERSISTENT_DEFAULT, bucket_steps=None, cmd_hz=1.0, vel_hz=None, act_hz=None, clip=True, mu_warm=0.8, device=None, kicks=None,
+                       gait=False, mass=None, g=9.81):
     """The reference's perturbation exploration (Exp_Raw_Data/Param-*.txt: NoE explorations of FoE control steps from a base state displaced by
     z_noise, roll_noise, pitch_noise and the *_dot_noise amplitudes, per friction and observation delay) in ONE Manual-mode pool of
     len(mus) x len(delays) x explorations envs, env index = (i_mu * len(delays) + i_delay) * explorations + i_exploration, command `cmd` (v_x).
@@ -728,7 +922,8 @@ def perturbation_study(model_or_policy, env_cfg, mus, delays, cmd, explorations,
     buckets 1 .. follow it.  persistent: PolicyEvaluator.run's keyword.
     -> list of one dict per (mu, delay): mu, delay, cmd, explorations, surviving (the fraction of explorations without a fall in the post-kick
     buckets), falls [E] (post-kick), stats (dict of [B, E] arrays, bucket_statistics), kicks [E, 11] and, with record_body, body [frames, E, 13]
-    (the post-kick frames; the reference's figure scripts reshape theirs as [env, frame, exploration, ...])."""
+    (the post-kick frames; the reference's figure scripts reshape theirs as [env, frame, exploration, ...]).
+    gait: every row gains `gait`, a dict of [B, E] arrays with the keys of gait_from_sums per bucket (mass None: each env's own total)."""
     import torch
     import yaml
     from . import __BLACKPANTHER_V55_RESOURCE_DIRECTORY__ as rsc
@@ -755,7 +950,7 @@ def perturbation_study(model_or_policy, env_cfg, mus, delays, cmd, explorations,
     ev = PolicyEvaluator(env, policy, np.repeat([c[1] for c in conditions], E), np.full(n, float(cmd)), cmd_hz=cmd_hz, vel_hz=vel_hz, act_hz=act_hz, clip=clip)
     post = -(-frames // bucket_steps)
     # the origin one bucket in front of the kick: bucket 0 = steps warm_steps - bucket_steps .. warm_steps - 1, the kick fires at tau = bucket_steps
-    ev.set_scenario(stat_buckets=1 + post, stat_every=bucket_steps, t0=warm_steps - bucket_steps, kicks=kicks, kick_first=bucket_steps)
+    ev.set_scenario(stat_buckets=1 + post, stat_every=bucket_steps, t0=warm_steps - bucket_steps, kicks=kicks, kick_first=bucket_steps, gait=gait)
     if warm_steps > bucket_steps:
         ev.run(warm_steps - bucket_steps, accumulate=False, persistent=persistent)
     ev.run(bucket_steps, persistent=persistent)
@@ -763,6 +958,7 @@ def perturbation_study(model_or_policy, env_cfg, mus, delays, cmd, explorations,
         env.SetContactCoefficient(contact_material(mu_rows))
     rec = ev.run(frames, record=("body",) if record_body else (), persistent=persistent)
     st = ev.bucket_statistics()
+    gt = ev.bucket_gait_statistics(mass, g) if gait else None
     body = rec["body"].cpu().numpy() if record_body else None
     out = []
     for i, (m, d) in enumerate(conditions):
@@ -772,29 +968,44 @@ def perturbation_study(model_or_policy, env_cfg, mus, delays, cmd, explorations,
                    kicks=kicks[sl])
         if record_body:
             row["body"] = body[:, sl]
+        if gait:
+            row["gait"] = {k: v[:, sl] for k, v in gt.items()}
         out.append(row)
     return out
 
 
-def perturbation_table(rows):
+def perturbation_table(rows, gait=False):
     """one line per (mu, delay) of a perturbation_study: the surviving fraction, and the ensemble mean of v_x / z / pitch of the survivors in the
-    bucket in front of the kick and in the last one"""
+    bucket in front of the kick and in the last one; gait (rows of a study with gait=True): the cost of transport and the mean duty factor too"""
     out = ["%-6s %-5s %-5s %-5s %-9s " % ("mu", "delay", "cmd", "E", "surviving") + " ".join("%-12s" % k for k in ("vx_before", "vx_last", "z_before", "z_last",
                                                                                                               "pitch_before", "pitch_last"))]
+    if gait:
+        out[0] += " " + " ".join("%-12s" % k for k in ("cot_before", "cot_last", "duty_before", "duty_last"))
     for r in rows:
         up = r["falls"] == 0
         m = lambda k, b: float(r["stats"][k][b, up].mean()) if up.any() else float("nan")
         out.append("%-6g %-5d %-5g %-5d %-9.4f " % (r["mu"], r["delay"], r["cmd"], r["explorations"], r["surviving"])
                    + " ".join("%+12.4f" % m(k, b) for k in ("vx_body_mean", "z_mean", "pitch_mean") for b in (0, -1)))
+        if gait:
+            gm = lambda keys, b: float(np.nanmean(np.stack([r["gait"][k][b, up] for k in keys]))) if up.any() else float("nan")
+            out[-1] += " " + " ".join("%+12.4f" % gm(keys, b) for keys in (("cot",), ("duty0", "duty1", "duty2", "duty3")) for b in (0, -1))
     return "\n".join(out)
 
 
-def sweep_table(rows):
+def sweep_table(rows, gait=False):
+    """one line per row of a robustness_sweep; gait (rows of a sweep with gait=True): the cost of transport, the mean mechanical power, the four
+    duty factors, the stride frequency (mean over the legs) and the flight fraction too"""
     keys = ("vx_body_mean", "vx_body_std", "z_mean", "z_std", "roll_std", "pitch_mean", "pitch_std", "yaw_rate_mean")
     staircase = bool(rows) and "level" in rows[0]              # one row per (condition, level): the level and its commanded v_x as well
     lead = ("mu", "delay", "cmd") + (("level", "cmd_level") if staircase else ()) + ("falls",)
     out = [" ".join("%-*s" % (9 if k == "cmd_level" else 6 if k == "mu" else 5, k) for k in lead) + " " + " ".join("%-12s" % k for k in keys)]
+    gkeys = ("cot", "power_mean", "duty0", "duty1", "duty2", "duty3", "stride_hz", "flight")
+    if gait:
+        out[0] += " " + " ".join("%-12s" % k for k in gkeys)
     for r in rows:
         lvl = "%-5d %-9g " % (r["level"], r["cmd_level"]) if staircase else ""
         out.append("%-6g %-5d %-5g %s%-5d " % (r["mu"], r["delay"], r["cmd"], lvl, r["falls"]) + " ".join("%+12.4f" % r[k] for k in keys))
+        if gait:
+            g = dict(r, stride_hz=float(np.mean([r["stride_hz%d" % l] for l in range(4)])))
+            out[-1] += " " + " ".join("%+12.4f" % g[k] for k in gkeys)
     return "\n".join(out)

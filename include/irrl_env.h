@@ -549,6 +549,63 @@ int irrl_lstm_eval_perturbed_persistent(irrl_env *env, int steps, long long step
 int irrl_env_perturb_base(irrl_env *env, const float *rows);
 int irrl_env_perturb_base_host(irrl_env *env, const float *rows);
 
+/* THE EVALUATION LOOP WITH GAIT MEASUREMENTS: joint mechanical power, torque and ground-force sums and the footfall pattern at control-step rate,
+ * the quantities of the reference's own analysis of its evaluation runs (Data_Visualization_Code/Figure2.py:62-63 power = sum_j qd_j tau_j per
+ * control step, :198-222 TCoT = P / (m g v) per command level, :36 and :97-116 the gait diagrams out of the contact flags; run_bp_v5.py:446-457
+ * logs the same words every step).  Semantics in ONE text, csrc/eval_elements.hpp irrl_eval_gait_epilogue.  After the env step of control step t,
+ * with the words the pool holds then -- tq = torque [N, 12], qd = gv[:, 6:18], in_contact [N, 4] and lam_w [N, 4, 3] -- an env whose step did NOT
+ * end in `done` adds one frame to its column of
+ *   gait (device f64 [stat_buckets, IRRL_EVAL_GAIT_COUNT, N]; bucket = the bucket of `stats`, one without a scenario),
+ * every f32 word widened to f64 first, sums added in index order (j = 0 .. 11, leg = 0 .. 3); rows IRRL_EVAL_GAIT_* below.  A step that ends in
+ * `done` adds nothing (its words are the reset state, not a sample of the gait).  Every step, `done` or not, then sets prev_contact[e, leg] =
+ * (in_contact != 0); prev_contact is caller-owned evaluator state, device u8 [N, 4], zero for a fresh evaluation.  The PEAK rows are running
+ * maxima, not sums: buckets and envs combine with max.
+ * WHAT lam_w IS: the world-frame contact IMPULSE (N s) of the LAST physics substep of the control step, zero for a leg that substep did not
+ * have in the contact list -- the contact solve overwrites it every substep; it is not the control step's sum.  The env's contact reward scales
+ * its norm by 1 / control_dt and so do the rows here: GRFZ and PEAK_GRF are in the reward's unit, lam_w / control_dt, which is the mean force
+ * of the last substep times simulation_dt / control_dt.  Divide by that ratio on the host for newtons.
+ * rec_gait (device f32 [steps, N, IRRL_EVAL_GAIT_REC_DIM], may be NULL = off), row k = step k of this call, `done` steps included:
+ *   tq 12 | qd 12 | in_contact 4 (0.0 / 1.0) | lam_w_z * (1 / control_dt) 4 (the f32 product)
+ * gait == NULL (the struct pointer) is exactly irrl_lstm_eval_perturbed[_persistent], which are calls of these with NULL; IRRL_EVAL_STAT_COUNT and
+ * the layout of `stats` are unchanged.  Both forms leave bit-identical buffers (gait, prev_contact, rec_gait included); the persistent one exists
+ * exactly where irrl_lstm_eval_rollout_supports says so, with no fallback inside the call.  Every pool kind and lane layout for the other.
+ * Refused before any HIP call, with the entry point's name in the text: a struct with `gait` set and prev_contact NULL; a struct whose three
+ * pointers are all NULL.  rec_gait alone (prev_contact NULL or not) is the recorder only; prev_contact alone keeps the flags up to date through
+ * steps that are not measured (a warm-up), so that the first measured step sees its predecessor's. */
+enum {
+  IRRL_EVAL_GAIT_N = 0,            /* frames added (steps that did not end in `done`) */
+  IRRL_EVAL_GAIT_P, IRRL_EVAL_GAIT_P2,        /* p = sum_j tq_j qd_j (W): sum, sum of squares */
+  IRRL_EVAL_GAIT_PPOS, IRRL_EVAL_GAIT_PNEG,   /* sum_j max(tq_j qd_j, 0), sum_j min(tq_j qd_j, 0) */
+  IRRL_EVAL_GAIT_TAU2,             /* sum of tq_j^2 over the 8 abad / hip joints */
+  IRRL_EVAL_GAIT_TAU2_KNEE,        /* sum of tq_j^2 over the 4 knee joints (j % 3 == 2) */
+  IRRL_EVAL_GAIT_PEAK_TAU, IRRL_EVAL_GAIT_PEAK_QD,   /* running max of |tq_j|, |qd_j| */
+  IRRL_EVAL_GAIT_STANCE0, IRRL_EVAL_GAIT_STANCE1, IRRL_EVAL_GAIT_STANCE2, IRRL_EVAL_GAIT_STANCE3,           /* frames with the leg in contact */
+  IRRL_EVAL_GAIT_TOUCHDOWN0, IRRL_EVAL_GAIT_TOUCHDOWN1, IRRL_EVAL_GAIT_TOUCHDOWN2, IRRL_EVAL_GAIT_TOUCHDOWN3,   /* prev_contact == 0 && in_contact != 0 */
+  IRRL_EVAL_GAIT_FLIGHT,           /* frames with no leg in contact */
+  IRRL_EVAL_GAIT_GRFZ,             /* sum over legs in contact of (double)(lam_w_z * (1 / control_dt)) */
+  IRRL_EVAL_GAIT_PEAK_GRF,         /* running max over legs in contact of |lam_w| * (1 / control_dt), the norm in f64 */
+  IRRL_EVAL_GAIT_COUNT
+};
+#define IRRL_EVAL_GAIT_REC_DIM 32
+typedef struct irrl_eval_gait {
+  double *gait;
+  uint8_t *prev_contact;
+  float *rec_gait;
+} irrl_eval_gait;
+int irrl_lstm_eval_measured(irrl_env *env, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *lstm_w, const float *pi_w,
+                            const float *pi_b, const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring, float *cmd, float *vel_his,
+                            float *act_his, float *lstm_state, uint8_t *done, float *obs, float *work, const int *delay, const float *cmd_target, float a_cmd,
+                            float a_vel, float a_act, const float *cmd_mean, const float *cmd_std, int clip, float *rec_obs_cond, float *rec_act_clipped,
+                            float *rec_act_applied, float *rec_body, float *rec_torque, float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats,
+                            const irrl_eval_scenario *scenario, const irrl_eval_kicks *kicks, const irrl_eval_gait *gait, void *hip_stream);
+int irrl_lstm_eval_measured_persistent(irrl_env *env, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *lstm_w,
+                                       const float *pi_w, const float *pi_b, const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring,
+                                       float *cmd, float *vel_his, float *act_his, float *lstm_state, uint8_t *done, float *obs, float *work, const int *delay,
+                                       const float *cmd_target, float a_cmd, float a_vel, float a_act, const float *cmd_mean, const float *cmd_std, int clip,
+                                       float *rec_obs_cond, float *rec_act_clipped, float *rec_act_applied, float *rec_body, float *rec_torque,
+                                       float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats, const irrl_eval_scenario *scenario,
+                                       const irrl_eval_kicks *kicks, const irrl_eval_gait *gait, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,8 @@ reference's own (run_bp_v5.py:8-13), resolved by the compat packages at the repo
     python scripts/run_bp_v5.py --test --sweep --model data/..._final.pkl --sweep_mu 0.8,0.1 --sweep_delay 0,1,2,3,4,5 --cmd 5 \
         --perturb z=0.02,roll=0.25,pitch=0.25,z_dot=1,roll_dot=1,pitch_dot=1 --explorations 10000 --perturb_at 1000 --steps 1000 \
         --out explorations.npz                                                             # perturbation exploration, device-resident
+    python scripts/run_bp_v5.py --test --sweep --step --gait --model data/..._final.pkl --persistent on   # cost of transport, duty factors and
+                                                                                           # touchdown rate per (friction, command level)
 
 `--test` keeps the evaluation LOOP of the reference (run_bp_v5.py:353-470: Manual-mode env, externally supplied command in
 obs[0:3], observation delay line, velocity / action low-pass filters, numpy LSTM actor, per-step records of joint state,
@@ -78,6 +80,11 @@ def parse_args(argv):
                    help="--test: the command staircase, (t // step_steps + 1) / 4 of the command, four levels (--sweep: --steps is replaced by 4 x "
                         "--step_steps and the table has one row per condition and level, over the second half of the level)")
     p.add_argument("--step_steps", type=int, default=5000, help="--step: control steps per level (even)")
+    p.add_argument("--gait", dest="flag_gait", action="store_true", default=False,
+                   help="--sweep: measure joint power, cost of transport, duty factors and stride frequency on the device as well (with --step: per "
+                        "command level, the table behind the reference's Figure 2 bar chart); --gait_mass / --gait_g as in that figure")
+    p.add_argument("--gait_mass", type=float, default=None, help="--gait: the mass of the cost of transport [kg] (default: each robot's own total)")
+    p.add_argument("--gait_g", type=float, default=9.81, help="--gait: the gravity of the cost of transport [m/s^2]")
     p.add_argument("--dir_fd", dest="flag_dir_fd", action="store_true", default=False,
                    help="--test: direction feedback, a PI loop (kp 1, ki 0.1, clamp Omega) on the base yaw replaces the yaw-rate command")
     # --test --sweep --perturb: the perturbation exploration of the reference's Exp_Raw_Data/Param-*.txt
@@ -179,12 +186,13 @@ def run_sweep(args, cfg):
     n = len(args.sweep_mu) * len(args.sweep_delay) * len(args.sweep_cmd)
     # --step: four levels of --step_steps steps in place of --steps, one row per condition and level; --dir_fd: the heading hold on every env.
     # Still one pool and one call per run: with --persistent on, one launch (two with a warm-up).
+    gait = dict(gait=True, mass=args.gait_mass, g=args.gait_g) if args.flag_gait else {}
     rows = robustness_sweep(args.trained_model, cfg["environment"], args.sweep_mu, args.sweep_delay, args.sweep_cmd, warm_steps=args.warm, steps=args.steps,
                             cmd_hz=args.cmd_filter_freq, vel_hz=none_if_off(args.vel_filter_freq), act_hz=none_if_off(args.act_filter_freq),
                             persistent=PERSISTENT_DEFAULT if args.persistent is None else args.persistent,
                             levels=4 if args.flag_step else None, level_steps=args.step_steps if args.flag_step else None,
-                            heading=heading_hold(n) if args.flag_dir_fd else None)
-    print(sweep_table(rows))
+                            heading=heading_hold(n) if args.flag_dir_fd else None, **gait)
+    print(sweep_table(rows, gait=True) if args.flag_gait else sweep_table(rows))
     if args.out:
         with open(args.out, "w") as f:
             json.dump(rows, f, indent=1)
@@ -204,13 +212,16 @@ def run_perturb(args, cfg):
     rows = perturbation_study(args.trained_model, cfg["environment"], args.sweep_mu, args.sweep_delay, args.flag_fix_cmd, args.explorations, args.perturb,
                               warm_steps=args.perturb_at, frames=args.steps, seed=args.perturb_seed, bucket_steps=bucket, cmd_hz=args.cmd_filter_freq,
                               vel_hz=none_if_off(args.vel_filter_freq), act_hz=none_if_off(args.act_filter_freq),
-                              persistent=PERSISTENT_DEFAULT if args.persistent is None else args.persistent)
-    print(perturbation_table(rows))
+                              persistent=PERSISTENT_DEFAULT if args.persistent is None else args.persistent,
+                              **(dict(gait=True, mass=args.gait_mass, g=args.gait_g) if args.flag_gait else {}))
+    print(perturbation_table(rows, gait=True) if args.flag_gait else perturbation_table(rows))
     if args.out:
         out = dict(mu=np.array([r["mu"] for r in rows]), delay=np.array([r["delay"] for r in rows]), cmd=np.array([r["cmd"] for r in rows]),
                    surviving=np.array([r["surviving"] for r in rows]), falls=np.stack([r["falls"] for r in rows]), kicks=np.stack([r["kicks"] for r in rows]))
         for k in rows[0]["stats"]:
             out["stat_" + k] = np.stack([r["stats"][k] for r in rows])        # [condition, bucket, exploration]
+        for k in (rows[0]["gait"] if args.flag_gait else ()):
+            out["gait_" + k] = np.stack([r["gait"][k] for r in rows])
         np.savez_compressed(args.out, **out)
         print("kicks and statistics written to", args.out)
     return rows

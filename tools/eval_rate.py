@@ -16,6 +16,9 @@ heading hold on every env, 4 statistics buckets) through irrl_lstm_eval_scenario
 --kicks K (with --ab): every leg runs with a kick table installed (PolicyEvaluator.set_scenario(kicks=): a tenth of the reference's exploration
 amplitudes on every env, one row every K timed steps) through irrl_lstm_eval_perturbed[_persistent].  Another trajectory than the run without
 kicks, so only roughly comparable with it.
+
+--gait (with --ab): every leg measures joint power, torque and ground-force sums and the footfall pattern too (PolicyEvaluator.measure_gait) through
+irrl_lstm_eval_measured[_persistent]; the same trajectory as the run without, so the difference is the measurements' cost.
 """
 import argparse
 import json
@@ -55,6 +58,8 @@ def ab(args, env, pol, delays, cmds, out):
                 ev.set_scenario(cmd_schedule=None if not args.scenario else EV.staircase_schedule(cmds, 5), cmd_every=scn.get("cmd_every", 1),
                                 heading=EV.heading_hold(n) if args.scenario else None, stat_buckets=scn.get("stat_buckets", 1),
                                 stat_every=scn.get("stat_every", 1), t0=50, kicks=table, kick_first=args.kicks // 2, kick_every=args.kicks)
+            if args.gait:
+                ev.measure_gait()
             ev.run(50, record=record, accumulate=acc, persistent=persistent)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -78,6 +83,7 @@ def main():
     ap.add_argument("--no-statistics", action="store_true", help="--ab: one more pair of legs with neither recorders nor statistics (accumulate=False)")
     ap.add_argument("--scenario", action="store_true", help="--ab: a 5-row command schedule, the heading hold and 4 statistics buckets on every leg")
     ap.add_argument("--kicks", type=int, default=0, help="--ab: a kick table on every leg, one row of small kicks for every env every K timed steps")
+    ap.add_argument("--gait", action="store_true", help="--ab: the gait measurements (power, contact statistics) on every leg")
     ap.add_argument("--ab", action="store_true", help="five launches per step (A) against the persistent launch (B), interleaved A, B, A, B")
     args = ap.parse_args()
     n = args.envs
@@ -88,7 +94,7 @@ def main():
     env = FlexibleGymEnv(pkg.__BLACKPANTHER_V55_RESOURCE_DIRECTORY__, yaml.safe_dump(cfg, default_flow_style=False, width=float("inf")))
     env.init()
     env.SetContactCoefficient(EV.contact_material(mus))
-    out = {"envs": n, "scenario": bool(args.scenario), "kicks": int(args.kicks)}
+    out = {"envs": n, "scenario": bool(args.scenario), "kicks": int(args.kicks), "gait": bool(args.gait)}
     if args.ab:
         return ab(args, env, pol, delays, cmds, out)
     for name, record in (("statistics only", ()), ("all recorders", tuple(EV.RECORDERS))):
