@@ -123,6 +123,9 @@ SIGNATURES = {
     # one kick row per env on the pool now: device rows [N, 11] / host rows
     "irrl_env_perturb_base": (C.c_int, [vp, vp]),
     "irrl_env_perturb_base_host": (C.c_int, [vp, fp]),
+    # the ensemble analysis of a body recorder: rec_body, rows, num_envs, conditions, explorations, frame_first, frame_every, frames | mask |
+    # `const irrl_eval_ensemble_spec *` (EvalEnsembleSpec below) | entropy, counts, hist, moments | stream
+    "irrl_eval_ensemble": (C.c_int, [vp] + [C.c_int] * 7 + [vp, vp] + [vp] * 4 + [vp]),
 }
 
 
@@ -141,6 +144,13 @@ class EvalGait(C.Structure):
     """struct irrl_eval_gait of include/irrl_env.h (a HOST struct of device pointers: gait f64 [stat_buckets, IRRL_EVAL_GAIT_COUNT, N], prev_contact u8
     [N, 4], rec_gait f32 [steps, N, 32]); C.byref(...) or None"""
     _fields_ = [("gait", vp), ("prev_contact", vp), ("rec_gait", vp)]
+
+
+class EvalEnsembleSpec(C.Structure):
+    """struct irrl_eval_ensemble_spec of include/irrl_env.h (a HOST struct of scalars: the entropy cells lb / ub / prec and the histogram ranges
+    per feature, hist_bins = 0 for no histograms); C.byref(...)"""
+    _fields_ = [("lb", C.c_double * 6), ("ub", C.c_double * 6), ("prec", C.c_double * 6), ("hist_lo", C.c_double * 6), ("hist_hi", C.c_double * 6),
+                ("hist_bins", C.c_int)]
 
 
 def load():

@@ -281,3 +281,75 @@ static inline IRRL_EVAL_FN void irrl_eval_gait_record(float *r, const float *tq,
   for (int j = 0; j < 12; j++) { r[j] = tq[j]; r[12 + j] = qd[j]; }
   for (int l = 0; l < 4; l++) { r[24 + l] = in_contact[l] != 0 ? 1.0f : 0.0f; r[28 + l] = irrl_eval_gait_fz(lamw[l * 3 + 2], inv_control_dt); }
 }
+
+// ---- the ensemble analysis of a body recorder: features, cell key, histogram bin (irrl_eval_ensemble, include/irrl_env.h) ----
+// One recorder row (base x y z | quaternion w x y z | world linear velocity | world angular velocity) -> the reference's state vector
+// x = (z, roll, pitch, body-frame v_z, body-frame w_x, body-frame w_y) (Data_Visualization_Code/Figure4.py:98-101), every word widened to f64 first,
+// the rotation matrix and the angles as irrl_eval_env_epilogue builds them.  Element 3 is (R^T v)_z, NOT the statistics' world v_z.
+static inline IRRL_EVAL_FN void irrl_eval_ensemble_features(const float *row13, double *x6) {
+  const double pz = row13[2];
+  const double w = row13[3], x = row13[4], y = row13[5], z = row13[6];
+  const double v0 = row13[7], v1 = row13[8], v2 = row13[9];
+  const double o0 = row13[10], o1 = row13[11], o2 = row13[12];
+  const double r00 = 1 - 2 * (y * y + z * z), r01 = 2 * (x * y - w * z), r02 = 2 * (x * z + w * y);
+  const double r10 = 2 * (x * y + w * z), r11 = 1 - 2 * (x * x + z * z), r12 = 2 * (y * z - w * x);
+  const double r20 = 2 * (x * z - w * y), r21 = 2 * (w * x + y * z), r22 = 1 - 2 * (x * x + y * y);
+  const double roll = atan2(2 * (w * x + y * z), 1 - 2 * (x * x + y * y));
+  double sp = 2 * (w * y - x * z);
+  sp = sp > 1.0 ? 1.0 : sp < -1.0 ? -1.0 : sp;
+  x6[0] = pz;
+  x6[1] = roll;
+  x6[2] = asin(sp);
+  x6[3] = r02 * v0 + r12 * v1 + r22 * v2;
+  x6[4] = r00 * o0 + r10 * o1 + r20 * o2;
+  x6[5] = r01 * o0 + r11 * o1 + r21 * o2;
+}
+static inline IRRL_EVAL_FN bool irrl_eval_ensemble_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN and +-inf
+// The cell key of one sample: per feature c_i = (long long)(min(max(x_i, lb_i), ub_i) / prec_i) -- a C cast, truncation toward zero like the
+// reference's astype(int), so the cell around 0 is double width -- and with lo_i = (long long)(lb_i / prec_i), hi_i = (long long)(ub_i / prec_i),
+// radix_i = hi_i - lo_i + 1 the key is the mixed-radix number of (c_i - lo_i), feature 0 the most significant digit.  -> false (sample dropped)
+// where a feature is not finite.  The spec has passed irrl_eval_ensemble_spec_error: every quotient fits a long long, the key stays below 2^63.
+static inline IRRL_EVAL_FN bool irrl_eval_ensemble_key(const double *x6, const irrl_eval_ensemble_spec &s, uint64_t *key) {
+  uint64_t k = 0;
+  for (int i = 0; i < IRRL_EVAL_ENSEMBLE_DIM; i++) {
+    const double x = x6[i];
+    if (!irrl_eval_ensemble_finite(x)) return false;
+    const double clipped = fmin(fmax(x, s.lb[i]), s.ub[i]);
+    const long long c = (long long)(clipped / s.prec[i]);
+    const long long lo = (long long)(s.lb[i] / s.prec[i]), hi = (long long)(s.ub[i] / s.prec[i]);
+    k = k * (uint64_t)(hi - lo + 1) + (uint64_t)(c - lo);
+  }
+  *key = k;
+  return true;
+}
+// The histogram bin of one (unclipped) feature value, or -1: floor((x - lo) * (bins / (hi - lo))), x == hi in the last bin, outside [lo, hi]
+// dropped.  (The product can round up to `bins` for an x one ulp under hi: that lands in the last bin too.)
+static inline IRRL_EVAL_FN int irrl_eval_ensemble_bin(double x, double lo, double hi, int bins) {
+  if (!(x >= lo && x <= hi)) return -1;
+  if (x == hi) return bins - 1;
+  const double scale = (double)bins / (hi - lo);
+  const double d = x - lo;
+  const int b = (int)floor(d * scale);
+  return b < bins ? b : bins - 1;
+}
+// what is wrong with a spec, or NULL: the refusals of irrl_eval_ensemble that concern the spec alone (host code: the product of the cell ranges
+// is taken exactly, in 128-bit integers)
+static inline const char *irrl_eval_ensemble_spec_error(const irrl_eval_ensemble_spec &s) {
+  const double cells_max = 4611686018427387904.0;   // 2^62
+  unsigned __int128 product = 1;
+  for (int i = 0; i < IRRL_EVAL_ENSEMBLE_DIM; i++) {
+    if (!(s.prec[i] > 0.0) || !irrl_eval_ensemble_finite(s.prec[i])) return "prec_i > 0";
+    if (!irrl_eval_ensemble_finite(s.lb[i]) || !irrl_eval_ensemble_finite(s.ub[i]) || s.lb[i] > s.ub[i]) return "lb_i <= ub_i, both finite";
+    const double ql = s.lb[i] / s.prec[i], qh = s.ub[i] / s.prec[i];
+    if (!(fabs(ql) < cells_max && fabs(qh) < cells_max)) return "a bound lies beyond 2^62 cells";
+    const long long lo = (long long)ql, hi = (long long)qh;
+    product *= (unsigned __int128)(hi - lo + 1);
+    if (product >= ((unsigned __int128)1 << 63)) return "the product of the six cell ranges reaches 2^63: the key does not fit 64 bits";
+  }
+  if (s.hist_bins < 0 || s.hist_bins > IRRL_EVAL_ENSEMBLE_MAX_BINS) return "hist_bins lies in 0 .. 256";
+  if (s.hist_bins > 0)
+    for (int i = 0; i < IRRL_EVAL_ENSEMBLE_DIM; i++)
+      if (!(s.hist_hi[i] > s.hist_lo[i]) || !irrl_eval_ensemble_finite(s.hist_hi[i]) || !irrl_eval_ensemble_finite(s.hist_lo[i]))
+        return "hist_lo_i < hist_hi_i, both finite";
+  return NULL;
+}

@@ -21,6 +21,7 @@
 #include "irrl_csv.hpp"
 #include "../../include/irrl_env.h"
 #include "eval_rollout.hpp"   // the evaluation loop's kernels (irrl_lstm_eval_rollout below)
+#include "eval_ensemble.hpp"  // the ensemble analysis: argument block and launcher of csrc/eval_ensemble.hip (irrl_eval_ensemble below)
 
 #include <cmath>
 #include <string>
@@ -1326,6 +1327,31 @@ int irrl_random_permutation(long long n, unsigned seed, unsigned counter, long l
   hipLaunchKernelGGL(irrl_random_permutation_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, (uint32_t)n, half_bits, seed,
                      counter, out);
   HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// ---- ensemble analysis of a body recorder (kernel and launcher: csrc/eval_ensemble.hip; per-sample arithmetic: csrc/eval_elements.hpp) ----
+int irrl_eval_ensemble(const float *rec_body, int rows, int num_envs, int conditions, int explorations, int frame_first, int frame_every, int frames,
+                       const uint8_t *mask, const irrl_eval_ensemble_spec *spec, double *entropy, uint32_t *counts, uint32_t *hist, double *moments,
+                       void *hip_stream) {
+  const std::string w = "irrl_eval_ensemble: ";
+  if (!rec_body || !spec || !entropy) { g_err = w + "NULL rec_body, spec or entropy"; return 1; }
+  if (rows < 1 || num_envs < 1 || conditions < 1 || conditions > 65535) { g_err = w + "rows >= 1, num_envs >= 1, 1 <= conditions <= 65535"; return 1; }
+  if (explorations < 1 || explorations > IRRL_EVAL_ENSEMBLE_MAX) {
+    g_err = w + "explorations lies in 1 .. 16384 (one workgroup sorts a condition's keys in LDS)"; return 1;
+  }
+  if ((long long)conditions * (long long)explorations != (long long)num_envs) { g_err = w + "conditions * explorations != num_envs"; return 1; }
+  if (frames < 0 || frame_first < 0 || frame_every < 1) { g_err = w + "frames >= 0, frame_first >= 0, frame_every >= 1"; return 1; }
+  if (frames > 0 && (long long)frame_first + (long long)(frames - 1) * (long long)frame_every >= (long long)rows) {
+    g_err = w + "frame_first + (frames - 1) * frame_every reaches past the recorder's rows"; return 1;
+  }
+  if (const char *bad = irrl_eval_ensemble_spec_error(*spec)) { g_err = w + "spec: " + bad; return 1; }
+  if (frames == 0) return 0;
+  EnsembleArgs a;
+  a.rec_body = rec_body; a.N = num_envs; a.E = explorations; a.P = irrl_eval_ensemble_padded(explorations);
+  a.frame_first = frame_first; a.frame_every = frame_every; a.C = conditions; a.F = frames; a.mask = mask; a.spec = *spec;
+  a.entropy = entropy; a.counts = counts; a.hist = spec->hist_bins > 0 ? hist : nullptr; a.moments = moments;
+  HIP_TRY(irrl_eval_ensemble_launch(a, (hipStream_t)hip_stream));
   return 0;
 }
 

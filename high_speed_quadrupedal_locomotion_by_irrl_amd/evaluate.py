@@ -578,6 +578,280 @@ def statistics_from_sums(sums):
             "pitch_rate_body_std": std("wy"), "vz_std": std("vz"), "frames": s["n"].astype(np.int64), "falls": s["falls"].astype(np.int64)}
 
 
+# ---- the ensemble analysis of a body recorder: entropy, cell counts, histograms, moments per (condition, frame) ----
+ENSEMBLE_FEATURES = ("z", "roll", "pitch", "vz_body", "wx_body", "wy_body")
+# the cells of Data_Visualization_Code/Figure3.py:361-366 and the density ranges of Figure3.py:198-199, 218 (101 bins)
+ENSEMBLE_SPEC_REFERENCE = dict(lb=(0.0, -3.14, -1.57, -10.0, -10.0, -10.0), ub=(0.5, 3.14, 1.57, 10.0, 10.0, 10.0),
+                               prec=(0.005, 0.02, 0.02, 0.005, 0.025, 0.025),
+                               hist_lo=(0.2, -1.0, -1.0, -5.0, -5.0, -5.0), hist_hi=(0.4, 1.0, 1.0, 5.0, 5.0, 5.0), hist_bins=101)
+ENSEMBLE_MAX = 16384          # IRRL_EVAL_ENSEMBLE_MAX
+ENSEMBLE_MAX_BINS = 256       # IRRL_EVAL_ENSEMBLE_MAX_BINS
+ENSEMBLE_EDGE = 1e-9          # ensemble_edges: how close to a cell boundary (in cells) a sample counts as "on an edge"
+
+
+def ensemble_spec(spec):
+    """a spec mapping (keys of ENSEMBLE_SPEC_REFERENCE; the histogram keys may be left out: no histograms) -> dict of float64 [6] arrays and
+    the int hist_bins, refused like irrl_eval_ensemble refuses its struct"""
+    s = {k: np.array(spec[k], np.float64).reshape(6) for k in ("lb", "ub", "prec")}
+    bins = int(spec.get("hist_bins", 0) or 0)
+    for k in ("hist_lo", "hist_hi"):
+        s[k] = np.array(spec[k], np.float64).reshape(6) if bins > 0 else np.zeros(6)
+    s["hist_bins"] = bins
+    if not (np.all(np.isfinite(s["prec"])) and np.all(s["prec"] > 0)):
+        raise ValueError("ensemble spec: prec_i > 0")
+    if not (np.all(np.isfinite(s["lb"])) and np.all(np.isfinite(s["ub"])) and np.all(s["lb"] <= s["ub"])):
+        raise ValueError("ensemble spec: lb_i <= ub_i, both finite")
+    if not (np.all(np.abs(s["lb"] / s["prec"]) < 2.0 ** 62) and np.all(np.abs(s["ub"] / s["prec"]) < 2.0 ** 62)):
+        raise ValueError("ensemble spec: a bound lies beyond 2^62 cells")
+    product = 1
+    for r in ensemble_radix(s)[1]:
+        product *= int(r)
+    if product >= 2 ** 63:
+        raise ValueError("ensemble spec: the product of the six cell ranges reaches 2^63: the key does not fit 64 bits")
+    if bins < 0 or bins > ENSEMBLE_MAX_BINS:
+        raise ValueError("ensemble spec: hist_bins lies in 0 .. %d" % ENSEMBLE_MAX_BINS)
+    if bins > 0 and not (np.all(np.isfinite(s["hist_lo"])) and np.all(np.isfinite(s["hist_hi"])) and np.all(s["hist_hi"] > s["hist_lo"])):
+        raise ValueError("ensemble spec: hist_lo_i < hist_hi_i, both finite")
+    return s
+
+
+def ensemble_radix(s):
+    """-> (lo [6], radix [6]) int64 of a spec: lo_i = trunc(lb_i / prec_i), radix_i = trunc(ub_i / prec_i) - lo_i + 1"""
+    lo = (s["lb"] / s["prec"]).astype(np.int64)
+    hi = (s["ub"] / s["prec"]).astype(np.int64)
+    return lo, hi - lo + 1
+
+
+def ensemble_features(body):
+    """body [..., 13] (a body recorder: base x y z, quaternion w x y z, world linear velocity, world angular velocity) -> x [..., 6] float64 =
+    (z, roll, pitch, body-frame v_z, body-frame w_x, body-frame w_y), csrc/eval_elements.hpp irrl_eval_ensemble_features statement for statement
+    (the reference's state vector, Figure4.py:98-101, with the rotation matrix of the quaternion itself: the figure script's
+    qua2matrix(w, x, x, z) slip is not reproduced)"""
+    d = np.asarray(body, np.float32).astype(np.float64)
+    pz = d[..., 2]
+    w, x, y, z = d[..., 3], d[..., 4], d[..., 5], d[..., 6]
+    v0, v1, v2 = d[..., 7], d[..., 8], d[..., 9]
+    o0, o1, o2 = d[..., 10], d[..., 11], d[..., 12]
+    r00 = 1 - 2 * (y * y + z * z); r01 = 2 * (x * y - w * z); r02 = 2 * (x * z + w * y)
+    r10 = 2 * (x * y + w * z); r11 = 1 - 2 * (x * x + z * z); r12 = 2 * (y * z - w * x)
+    r20 = 2 * (x * z - w * y); r21 = 2 * (w * x + y * z); r22 = 1 - 2 * (x * x + y * y)
+    with np.errstate(invalid="ignore"):
+        roll = np.arctan2(2 * (w * x + y * z), 1 - 2 * (x * x + y * y))
+        sp = 2 * (w * y - x * z)
+        sp = np.where(sp > 1.0, 1.0, np.where(sp < -1.0, -1.0, sp))
+        pitch = np.arcsin(sp)
+        return np.stack([pz, roll, pitch, r02 * v0 + r12 * v1 + r22 * v2, r00 * o0 + r10 * o1 + r20 * o2, r01 * o0 + r11 * o1 + r21 * o2], -1)
+
+
+def ensemble_keys(x, spec):
+    """x [..., 6] -> (key uint64 [...], kept bool [...]): irrl_eval_ensemble_key -- clip, divide by prec, truncate toward zero (astype: the cell
+    around 0 is double width), mixed radix with feature 0 the most significant digit; kept is False where a feature is not finite (key 0 there)"""
+    s = ensemble_spec(spec)
+    x = np.asarray(x, np.float64)
+    kept = np.all(np.isfinite(x), -1)
+    lo, radix = ensemble_radix(s)
+    safe = np.where(kept[..., None], x, 0.0)
+    cells = (np.minimum(np.maximum(safe, s["lb"]), s["ub"]) / s["prec"]).astype(np.int64)
+    key = np.zeros(x.shape[:-1], np.uint64)
+    for i in range(6):
+        key = key * np.uint64(radix[i]) + (cells[..., i] - lo[i]).astype(np.uint64)
+    return np.where(kept, key, np.uint64(0)), kept
+
+
+def ensemble_bins(x, lo, hi, bins):
+    """irrl_eval_ensemble_bin on an array: floor((x - lo) * (bins / (hi - lo))), x == hi in the last bin, -1 outside [lo, hi] (and for NaN)"""
+    x = np.asarray(x, np.float64)
+    with np.errstate(invalid="ignore"):
+        inside = (x >= lo) & (x <= hi)
+        scale = float(bins) / (hi - lo)
+        b = np.floor((np.where(inside, x, lo) - lo) * scale).astype(np.int64)
+    b = np.minimum(b, bins - 1)
+    return np.where(inside, np.where(x == hi, bins - 1, b), -1)
+
+
+def ensemble_edges(x, spec, tol=ENSEMBLE_EDGE):
+    """x [..., 6] -> bool [...]: is the sample "on an edge" of the entropy cells -- an unclipped feature within tol cells of a cell boundary other
+    than 0 (truncation has no boundary at 0), or a feature within tol * prec of lb or ub -- so that two correct f64 evaluations of the features
+    (different atan2 / asin / fused multiply-adds) may put it into different cells.  Non-finite samples are not on an edge (both sides drop them)."""
+    s = ensemble_spec(spec)
+    x = np.asarray(x, np.float64)
+    fin = np.all(np.isfinite(x), -1, keepdims=True)
+    x = np.where(fin, x, 0.5 * (s["lb"] + s["ub"]))
+    q = x / s["prec"]
+    r = np.round(q)
+    inside = (x > s["lb"]) & (x < s["ub"])
+    edge = inside & (np.abs(q - r) < tol) & (r != 0)
+    edge |= (np.abs(x - s["lb"]) < tol * s["prec"]) | (np.abs(x - s["ub"]) < tol * s["prec"])
+    return np.any(edge, -1) & fin[..., 0]
+
+
+def _ensemble_frames(rows, frame_first, frame_every, frames):
+    frame_first, frame_every = int(frame_first), int(frame_every)
+    if frame_first < 0 or frame_every < 1:
+        raise ValueError("frame_first >= 0, frame_every >= 1")
+    most = max(0, -(-(rows - frame_first) // frame_every))
+    frames = most if frames is None else int(frames)
+    if frames < 0 or frames > most:
+        raise ValueError("frame_first + (frames - 1) * frame_every reaches past the recorder's %d rows" % rows)
+    return frame_first, frame_every, frames
+
+
+def _ensemble_shape(n, conditions):
+    conditions = int(conditions)
+    if conditions < 1 or n % conditions:
+        raise ValueError("conditions * explorations != num_envs")
+    e = n // conditions
+    if e < 1 or e > ENSEMBLE_MAX:
+        raise ValueError("explorations lies in 1 .. %d" % ENSEMBLE_MAX)
+    return conditions, e
+
+
+def ensemble_numpy(body, conditions, spec, mask=None, frame_first=0, frame_every=1, frames=None):
+    """The float64 twin of irrl_eval_ensemble (include/irrl_env.h): body [rows, N, 13] with env index = condition * E + exploration, analysed
+    frame f = row frame_first + f * frame_every (frames None: as many as the rows hold), mask [N] (None: all) -> dict of
+    entropy [C, F] f64 (nats), kept / occupied / largest [C, F] uint32, hist [C, F, 6, hist_bins] uint32 (None without bins),
+    moments [C, F, 6, 2] f64 (sum x | sum x^2 of the unclipped features over the kept samples)."""
+    s = ensemble_spec(spec)
+    body = np.asarray(body)
+    rows, n = body.shape[0], body.shape[1]
+    C_, E = _ensemble_shape(n, conditions)
+    frame_first, frame_every, F = _ensemble_frames(rows, frame_first, frame_every, frames)
+    bins = s["hist_bins"]
+    out = dict(entropy=np.zeros((C_, F)), kept=np.zeros((C_, F), np.uint32), occupied=np.zeros((C_, F), np.uint32), largest=np.zeros((C_, F), np.uint32),
+               hist=np.zeros((C_, F, 6, bins), np.uint32) if bins > 0 else None, moments=np.zeros((C_, F, 6, 2)))
+    on = np.ones(n, bool) if mask is None else np.asarray(mask).reshape(n) != 0
+    for f in range(F):
+        x = ensemble_features(body[frame_first + f * frame_every])
+        key, kept = ensemble_keys(x, s)
+        kept &= on
+        for c in range(C_):
+            sl = slice(c * E, (c + 1) * E)
+            k, xs = key[sl][kept[sl]], x[sl][kept[sl]]
+            m = len(k)
+            out["kept"][c, f] = m
+            out["moments"][c, f, :, 0] = xs.sum(0)
+            out["moments"][c, f, :, 1] = (xs * xs).sum(0)
+            if bins > 0:
+                for i in range(6):
+                    b = ensemble_bins(xs[:, i], s["hist_lo"][i], s["hist_hi"][i], bins)
+                    out["hist"][c, f, i] = np.bincount(b[b >= 0], minlength=bins)
+            if m:
+                _, cnt = np.unique(k, return_counts=True)     # sorted keys: the runs in the kernel's order
+                p = cnt / float(m)
+                out["entropy"][c, f] = -np.sum(p * np.log(p))
+                out["occupied"][c, f] = len(cnt)
+                out["largest"][c, f] = cnt.max()
+    return out
+
+
+def ensemble_device(rec_body, conditions, spec, mask=None, frame_first=0, frame_every=1, frames=None, hist=True, moments=True):
+    """ensemble_numpy on the device: rec_body a float32 device tensor [rows, N, 13] (PolicyEvaluator.run(record=("body",))), mask a uint8 / bool
+    device tensor [N] or None -- ONE call of irrl_eval_ensemble on torch's current stream, no synchronisation -> dict of device tensors with the
+    twin's keys (hist None with hist=False or without bins, moments None with moments=False)."""
+    import torch
+    from . import _lib
+    from ._lib import ptr
+    s = ensemble_spec(spec)
+    if rec_body.dim() != 3 or rec_body.shape[2] != 13 or rec_body.dtype != torch.float32 or not rec_body.is_cuda:
+        raise ValueError("rec_body is a float32 device tensor [rows, N, 13]")
+    rec_body = _lib.contig(rec_body)
+    rows, n = int(rec_body.shape[0]), int(rec_body.shape[1])
+    C_, E = _ensemble_shape(n, conditions)
+    frame_first, frame_every, F = _ensemble_frames(rows, frame_first, frame_every, frames)
+    dev = rec_body.device
+    if mask is not None:
+        mask = _lib.contig(mask.to(device=dev, dtype=torch.uint8).reshape(n))
+    bins = s["hist_bins"]
+    st = _lib.EvalEnsembleSpec(hist_bins=bins)
+    for k in ("lb", "ub", "prec", "hist_lo", "hist_hi"):
+        setattr(st, k, (C.c_double * 6)(*s[k]))
+    out = dict(entropy=torch.zeros(C_, F, device=dev, dtype=torch.float64), counts=torch.zeros(C_, F, 3, device=dev, dtype=torch.int32),
+               hist=torch.zeros(C_, F, 6, bins, device=dev, dtype=torch.int32) if (hist and bins > 0) else None,
+               moments=torch.zeros(C_, F, 6, 2, device=dev, dtype=torch.float64) if moments else None)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().irrl_eval_ensemble(ptr(rec_body), rows, n, C_, E, frame_first, frame_every, F, ptr(mask), C.cast(C.pointer(st), C.c_void_p),
+                                                  ptr(out["entropy"]), ptr(out["counts"]), ptr(out["hist"]), ptr(out["moments"]), _lib.stream_ptr(dev)))
+    counts = out.pop("counts")
+    out.update(kept=counts[..., 0], occupied=counts[..., 1], largest=counts[..., 2])
+    return out
+
+
+def ensemble_to_numpy(res):
+    """a result of ensemble_device -> the twin's dict of numpy arrays (synchronises; the counters as uint32)"""
+    out = {}
+    for k, v in res.items():
+        a = None if v is None else (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v))
+        out[k] = a.astype(np.uint32) if a is not None and k in ("kept", "occupied", "largest", "hist") else a
+    return out
+
+
+def ensemble_row(res, c, control_dt, frame0=0):
+    """condition c of an ensemble result (numpy) as perturbation_study hands it out: dict of t [F] (= (frame0 + frame) * control_dt), entropy,
+    kept, occupied, largest [F], hist [F, 6, bins] or None, mean and std [F, 6] of the unclipped features over the kept samples (NaN where none)"""
+    kept = np.asarray(res["kept"][c], np.float64)
+    row = dict(t=(frame0 + np.arange(len(kept))) * float(control_dt), entropy=np.array(res["entropy"][c]), kept=np.array(res["kept"][c]),
+               occupied=np.array(res["occupied"][c]), largest=np.array(res["largest"][c]), hist=None if res["hist"] is None else np.array(res["hist"][c]))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = res["moments"][c][:, :, 0] / kept[:, None]
+        row["mean"] = mean
+        row["std"] = np.sqrt(np.maximum(res["moments"][c][:, :, 1] / kept[:, None] - mean * mean, 0.0))
+    return row
+
+
+def entropy_curve(t, a, b, c, d):
+    """the reference's piecewise_func3 (Figure4.py:169-173): the plateau b up to a, slope d up to c, constant d (c - a) + b after"""
+    t = np.asarray(t, np.float64)
+    return b + d * np.clip(t - a, 0.0, c - a)
+
+
+def entropy_rate(t, H, stride=1):
+    """Least-squares fit of entropy_curve to an entropy series without scipy: every pair a < c out of the frame times t[::stride] is tried, and
+    for a pair the curve is b + d g(t) with g = clip(t - a, 0, c - a), linear in (b, d): closed-form least squares, the sums over the frames from
+    prefix sums (so the whole grid costs O(n^2) words).  t ascending.  -> dict(a, b, c, d, residual (the root of the mean squared error), kappa
+    (= d, nats/s: the entropy's decay rate), t_floor (= c))."""
+    t, H = np.asarray(t, np.float64).reshape(-1), np.asarray(H, np.float64).reshape(-1)
+    n = len(t)
+    if n < 3 or len(H) != n or np.any(np.diff(t) <= 0):
+        raise ValueError("entropy_rate needs at least 3 frames and ascending times")
+    tm, hm = t.mean(), H.mean()
+    tc, hc = t - tm, H - hm                                    # centred: the normal equations lose fewer digits
+    pre = lambda v: np.concatenate([[0.0], np.cumsum(v)])
+    St, Stt, Sh, Sth = pre(tc), pre(tc * tc), pre(hc), pre(tc * hc)
+    idx = np.arange(0, n, max(int(stride), 1))
+    i, j = np.meshgrid(idx, idx, indexing="ij")
+    ok = i < j
+    a, c = tc[i], tc[j]
+    mid, tail = (j - i).astype(np.float64), (n - 1 - j).astype(np.float64)
+    dt_, dtt, dh, dth = St[j + 1] - St[i + 1], Stt[j + 1] - Stt[i + 1], Sh[j + 1] - Sh[i + 1], Sth[j + 1] - Sth[i + 1]
+    sg = dt_ - a * mid + tail * (c - a)
+    sgg = dtt - 2 * a * dt_ + a * a * mid + tail * (c - a) ** 2
+    sgh = dth - a * dh + (c - a) * (Sh[n] - Sh[j + 1])
+    sy, syy = Sh[n], float(np.sum(hc * hc))
+    den = n * sgg - sg * sg
+    with np.errstate(invalid="ignore", divide="ignore"):
+        d = (n * sgh - sg * sy) / den
+        b = (sy - d * sg) / n
+        sse = syy - b * sy - d * sgh
+    sse = np.where(ok & (den > 0), sse, np.inf)
+    bi, bj = np.unravel_index(np.argmin(sse), sse.shape)
+    a_, c_ = t[idx[bi]], t[idx[bj]]
+    g = np.clip(t - a_, 0.0, c_ - a_)                          # the winning pair once more, directly
+    gm = g.mean()
+    d_ = float(np.sum((g - gm) * (H - hm)) / np.sum((g - gm) ** 2))
+    b_ = float(hm - d_ * gm)
+    res = float(np.sqrt(np.mean((entropy_curve(t, a_, b_, c_, d_) - H) ** 2)))
+    return dict(a=float(a_), b=b_, c=float(c_), d=d_, residual=res, kappa=d_, t_floor=float(c_))
+
+
+def poincare_section(body_rows, every, offset=0):
+    """the strided return map of ONE robot (Figure4.py:191-199: frames offset, offset + every, ... of a run): body_rows [frames, 13] -> the
+    features [K, 6] (ENSEMBLE_FEATURES) of those frames; the map's points are (section[:-1], section[1:])"""
+    every, offset = int(every), int(offset)
+    if every < 1 or offset < 0:
+        raise ValueError("every >= 1, offset >= 0")
+    return ensemble_features(np.asarray(body_rows)[offset::every])
+
+
 # ---- the device loop ----
 def resolve_persistent(persistent, supported):
     """the `persistent` keyword of PolicyEvaluator.run / robustness_sweep (False, True, "auto"; the command line's "off" / "on" too) -> bool;
@@ -912,7 +1186,7 @@ def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=100
 
 def perturbation_study(model_or_policy, env_cfg, mus, delays, cmd, explorations, noise, warm_steps=1000, frames=1000, seed=0, record_body=False,
                        persistent=PERSISTENT_DEFAULT, bucket_steps=None, cmd_hz=1.0, vel_hz=None, act_hz=None, clip=True, mu_warm=0.8, device=None, kicks=None,
-                       gait=False, mass=None, g=9.81):
+                       gait=False, mass=None, g=9.81, ensemble=None, frame_chunk=None, ensemble_survivors=False):
     """The reference's perturbation exploration (Exp_Raw_Data/Param-*.txt: NoE explorations of FoE control steps from a base state displaced by
     z_noise, roll_noise, pitch_noise and the *_dot_noise amplitudes, per friction and observation delay) in ONE Manual-mode pool of
     len(mus) x len(delays) x explorations envs, env index = (i_mu * len(delays) + i_delay) * explorations + i_exploration, command `cmd` (v_x).
@@ -923,11 +1197,28 @@ def perturbation_study(model_or_policy, env_cfg, mus, delays, cmd, explorations,
     -> list of one dict per (mu, delay): mu, delay, cmd, explorations, surviving (the fraction of explorations without a fall in the post-kick
     buckets), falls [E] (post-kick), stats (dict of [B, E] arrays, bucket_statistics), kicks [E, 11] and, with record_body, body [frames, E, 13]
     (the post-kick frames; the reference's figure scripts reshape theirs as [env, frame, exploration, ...]).
-    gait: every row gains `gait`, a dict of [B, E] arrays with the keys of gait_from_sums per bucket (mass None: each env's own total)."""
+    gait: every row gains `gait`, a dict of [B, E] arrays with the keys of gait_from_sums per bucket (mass None: each env's own total).
+    ensemble: a spec (ENSEMBLE_SPEC_REFERENCE) -- every row gains `ensemble`, the dict of ensemble_row per post-kick frame (t, entropy, kept,
+    occupied, largest, hist, mean, std), analysed on the device from the body recorder (irrl_eval_ensemble), which is recorded for that whether or
+    not record_body hands it out.  frame_chunk K: the post-kick frames run as successive calls of at most K steps (the evaluator resumes bit
+    for bit), each call's recorder is analysed (and copied out with record_body) and released before the next call takes its place, so the
+    device memory of the recorder is K, not `frames`, rows.  ensemble_survivors: analyse only the explorations without a post-kick fall (the
+    mask is known after the last frame, so the whole recorder is kept: refused together with frame_chunk).
+    ensemble None (the default): the return value is what it was, key for key."""
     import torch
     import yaml
     from . import __BLACKPANTHER_V55_RESOURCE_DIRECTORY__ as rsc
     from .flexible_robot import FlexibleGymEnv
+    if ensemble is not None:
+        ensemble = ensemble_spec(ensemble)
+    elif ensemble_survivors:
+        raise ValueError("ensemble_survivors needs an ensemble spec")
+    if frame_chunk is not None:
+        frame_chunk = int(frame_chunk)
+        if frame_chunk < 1:
+            raise ValueError("frame_chunk >= 1")
+        if ensemble_survivors:
+            raise ValueError("ensemble_survivors needs the whole run's recorder: it does not go with frame_chunk")
     conditions = [(float(m), int(d)) for m in mus for d in delays]
     E, warm_steps, frames = int(explorations), int(warm_steps), int(frames)
     bucket_steps = frames if bucket_steps is None else int(bucket_steps)
@@ -936,6 +1227,8 @@ def perturbation_study(model_or_policy, env_cfg, mus, delays, cmd, explorations,
     if bucket_steps < 1 or warm_steps < bucket_steps:
         raise ValueError("1 <= bucket_steps <= warm_steps: bucket 0 is the window in front of the kick")
     n = len(conditions) * E
+    if ensemble is not None:
+        _ensemble_shape(n, len(conditions))                    # (refused here, in front of the pool's allocation)
     kicks = exploration_kicks(n, noise, np.random.default_rng(seed)) if kicks is None else _kick_table(kicks, n)[0]
     cfg = dict(env_cfg.get("environment", env_cfg))
     cfg["num_envs"] = n
@@ -956,10 +1249,26 @@ def perturbation_study(model_or_policy, env_cfg, mus, delays, cmd, explorations,
     ev.run(bucket_steps, persistent=persistent)
     if mu_warm is not None:                                    # (the setter's copy is ordered on the pool's stream, behind the warm-up)
         env.SetContactCoefficient(contact_material(mu_rows))
-    rec = ev.run(frames, record=("body",) if record_body else (), persistent=persistent)
+    want_body = record_body or ensemble is not None
+    chunk = frames if frame_chunk is None else min(frame_chunk, frames)
+    body_parts, ens_parts, rec = [], [], None
+    for first in range(0, frames, chunk):
+        rec = None                                             # the previous call's recorder goes back to the allocator before this call's is taken
+        rec = ev.run(min(chunk, frames - first), record=("body",) if want_body else (), persistent=persistent)
+        if ensemble is not None and not ensemble_survivors:
+            ens_parts.append(ensemble_to_numpy(ensemble_device(rec["body"], len(conditions), ensemble)))
+        if record_body:
+            body_parts.append(rec["body"].cpu().numpy())
     st = ev.bucket_statistics()
     gt = ev.bucket_gait_statistics(mass, g) if gait else None
-    body = rec["body"].cpu().numpy() if record_body else None
+    body = (body_parts[0] if len(body_parts) == 1 else np.concatenate(body_parts, 0)) if record_body else None
+    ens = None
+    if ensemble is not None:
+        if ensemble_survivors:                                 # (one chunk: rec is the whole run's recorder)
+            up = torch.from_numpy((st["falls"][1:].sum(0) == 0).astype(np.uint8)).to(ev.dev)
+            ens_parts.append(ensemble_to_numpy(ensemble_device(rec["body"], len(conditions), ensemble, mask=up)))
+        ens = {k: (None if ens_parts[0][k] is None else np.concatenate([p[k] for p in ens_parts], 1)) for k in ens_parts[0]}
+    rec = None
     out = []
     for i, (m, d) in enumerate(conditions):
         sl = slice(i * E, (i + 1) * E)
@@ -970,17 +1279,23 @@ def perturbation_study(model_or_policy, env_cfg, mus, delays, cmd, explorations,
             row["body"] = body[:, sl]
         if gait:
             row["gait"] = {k: v[:, sl] for k, v in gt.items()}
+        if ens is not None:
+            row["ensemble"] = ensemble_row(ens, i, ev._dt)
         out.append(row)
     return out
 
 
-def perturbation_table(rows, gait=False):
+def perturbation_table(rows, gait=False, ensemble=False):
     """one line per (mu, delay) of a perturbation_study: the surviving fraction, and the ensemble mean of v_x / z / pitch of the survivors in the
-    bucket in front of the kick and in the last one; gait (rows of a study with gait=True): the cost of transport and the mean duty factor too"""
+    bucket in front of the kick and in the last one; gait (rows of a study with gait=True): the cost of transport and the mean duty factor too;
+    ensemble (rows of a study with an ensemble spec): the entropy of the first and of the last frame, its decay rate kappa (nats/s) and the
+    time at which it reaches its floor (entropy_rate; NaN for fewer than 3 frames)"""
     out = ["%-6s %-5s %-5s %-5s %-9s " % ("mu", "delay", "cmd", "E", "surviving") + " ".join("%-12s" % k for k in ("vx_before", "vx_last", "z_before", "z_last",
                                                                                                               "pitch_before", "pitch_last"))]
     if gait:
         out[0] += " " + " ".join("%-12s" % k for k in ("cot_before", "cot_last", "duty_before", "duty_last"))
+    if ensemble:
+        out[0] += " " + " ".join("%-12s" % k for k in ("H0", "H_last", "kappa", "t_floor"))
     for r in rows:
         up = r["falls"] == 0
         m = lambda k, b: float(r["stats"][k][b, up].mean()) if up.any() else float("nan")
@@ -989,6 +1304,10 @@ def perturbation_table(rows, gait=False):
         if gait:
             gm = lambda keys, b: float(np.nanmean(np.stack([r["gait"][k][b, up] for k in keys]))) if up.any() else float("nan")
             out[-1] += " " + " ".join("%+12.4f" % gm(keys, b) for keys in (("cot",), ("duty0", "duty1", "duty2", "duty3")) for b in (0, -1))
+        if ensemble:
+            e = r["ensemble"]
+            fit = entropy_rate(e["t"], e["entropy"], stride=max(1, len(e["t"]) // 500)) if len(e["t"]) >= 3 else dict(kappa=float("nan"), t_floor=float("nan"))
+            out[-1] += " " + " ".join("%+12.4f" % v for v in (e["entropy"][0], e["entropy"][-1], fit["kappa"], fit["t_floor"]))
     return "\n".join(out)
 
 

@@ -606,6 +606,38 @@ int irrl_lstm_eval_measured_persistent(irrl_env *env, int steps, long long step0
                                        float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats, const irrl_eval_scenario *scenario,
                                        const irrl_eval_kicks *kicks, const irrl_eval_gait *gait, void *hip_stream);
 
+/* ENSEMBLE ANALYSIS OF A BODY RECORDER: state-space entropy, cell counts, per-feature histograms and moments per (condition, frame) -- what the
+ * reference's figure scripts do with a perturbation exploration (Data_Visualization_Code/Figure3.py:145-151 and Figure4.py:160-166 `entropy`,
+ * Figure3.py:213-230 the time x value densities).  rec_body is the recorder of the evaluation loop, device f32 [rows, num_envs, 13] (base x y z,
+ * quaternion w x y z, world linear velocity, world angular velocity), env index = condition * explorations + exploration.  Semantics in ONE text,
+ * csrc/eval_elements.hpp: irrl_eval_ensemble_features turns a row into x = (z, roll, pitch, body-frame v_z, body-frame w_x, body-frame w_y) in
+ * f64, irrl_eval_ensemble_key clips, divides by prec and TRUNCATES toward zero (the reference's astype(int): the cell around 0 is double width)
+ * and packs the six cell indices into one mixed-radix key, irrl_eval_ensemble_bin is the histogram rule
+ *   b = (int)floor((x - hist_lo) * (hist_bins / (hist_hi - hist_lo))),  x == hist_hi -> the last bin,  x outside [hist_lo, hist_hi] dropped.
+ * For condition c and analysed frame f (row frame_first + f * frame_every of the recorder) over the explorations e whose mask byte is non-zero
+ * (mask NULL: all) and whose six features are finite -- M of them --:
+ *   entropy[c, f] = -sum over occupied cells of (n / M) log(n / M)  (nats; n = samples in the cell);  0 where M = 0
+ *   counts[c, f]  = M | number of occupied cells | the largest n
+ *   hist[c, f, i, b]   (NULL or hist_bins = 0: off) = kept samples whose UNCLIPPED feature i falls into bin b
+ *   moments[c, f, i]   (NULL: off) = sum x_i | sum x_i^2 over the kept samples, unclipped, f64
+ * One workgroup per (c, f) sorts the keys: entropy, counts and hist are the same bits from run to run and under any permutation of a
+ * condition's explorations.  Stateless and stream-ordered, no env handle.
+ * Refused before any HIP call, with "irrl_eval_ensemble" in the text: a NULL rec_body, spec or entropy; conditions * explorations != num_envs;
+ * explorations outside 1 .. IRRL_EVAL_ENSEMBLE_MAX; frames < 0, frame_first < 0, frame_every < 1, frame_first + (frames - 1) * frame_every >= rows;
+ * prec_i <= 0, lb_i > ub_i, a bound that is not finite or lies beyond 2^62 cells; a product of the six cell ranges of 2^63 or more; hist_bins
+ * outside 0 .. IRRL_EVAL_ENSEMBLE_MAX_BINS, or hist_hi_i <= hist_lo_i with bins on.  frames == 0 is accepted and does nothing. */
+#define IRRL_EVAL_ENSEMBLE_DIM 6
+#define IRRL_EVAL_ENSEMBLE_MAX 16384
+#define IRRL_EVAL_ENSEMBLE_MAX_BINS 256
+typedef struct irrl_eval_ensemble_spec {
+  double lb[6], ub[6], prec[6];
+  double hist_lo[6], hist_hi[6];
+  int hist_bins;
+} irrl_eval_ensemble_spec;
+int irrl_eval_ensemble(const float *rec_body, int rows, int num_envs, int conditions, int explorations, int frame_first, int frame_every, int frames,
+                       const uint8_t *mask, const irrl_eval_ensemble_spec *spec, double *entropy, uint32_t *counts, uint32_t *hist, double *moments,
+                       void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

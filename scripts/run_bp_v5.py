@@ -13,6 +13,7 @@ reference's own (run_bp_v5.py:8-13), resolved by the compat packages at the repo
     python scripts/run_bp_v5.py --test --sweep --model data/..._final.pkl --sweep_mu 0.8,0.1 --sweep_delay 0,1,2,3,4,5 --cmd 5 \
         --perturb z=0.02,roll=0.25,pitch=0.25,z_dot=1,roll_dot=1,pitch_dot=1 --explorations 10000 --perturb_at 1000 --steps 1000 \
         --out explorations.npz                                                             # perturbation exploration, device-resident
+    ... --perturb ... --entropy [--entropy_chunk 100]                                      # + entropy, cells, histograms per frame (Figure3/4.py)
     python scripts/run_bp_v5.py --test --sweep --step --gait --model data/..._final.pkl --persistent on   # cost of transport, duty factors and
                                                                                            # touchdown rate per (friction, command level)
 
@@ -103,6 +104,11 @@ def parse_args(argv):
     p.add_argument("--explorations", type=int, default=1000, help="--perturb: explorations per condition (the Param files' NoE)")
     p.add_argument("--perturb_at", type=int, default=1000, help="--perturb: the control step of the kick (the warm-up in front of it runs on friction 0.8)")
     p.add_argument("--perturb_seed", type=int, default=0, help="--perturb: seed of the kicks")
+    p.add_argument("--entropy", dest="flag_entropy", action="store_true", default=False,
+                   help="--perturb: the reference's ensemble analysis per post-kick frame on the device (evaluate.ENSEMBLE_SPEC_REFERENCE: state-space entropy, "
+                        "occupied cells, per-feature histograms, mean and standard deviation); the table gains H0, H_last, kappa and t_floor, --out the arrays")
+    p.add_argument("--entropy_chunk", type=int, default=None,
+                   help="--entropy: run the post-kick frames in calls of at most this many steps, so that the body recorder on the device holds that many rows")
     return p.parse_args(argv)
 
 
@@ -204,17 +210,18 @@ def run_perturb(args, cfg):
     """--test --sweep --perturb: the perturbation exploration (evaluate.perturbation_study) -- every (friction, delay) condition x --explorations is
     one env of ONE Manual-mode pool.  Prints one row per (mu, delay); writes the kicks and the per-bucket statistics to --out (.npz)."""
     import numpy as np
-    from high_speed_quadrupedal_locomotion_by_irrl_amd.evaluate import PERSISTENT_DEFAULT, perturbation_study, perturbation_table
+    from high_speed_quadrupedal_locomotion_by_irrl_amd.evaluate import ENSEMBLE_SPEC_REFERENCE, PERSISTENT_DEFAULT, perturbation_study, perturbation_table
     if args.trained_model is None:
         raise SystemExit("model path can't be ignored during test mode (--model)")
     none_if_off = lambda f: None if f >= 1.0e6 else f
     bucket = min(args.perturb_at, args.steps)
+    entropy = dict(ensemble=ENSEMBLE_SPEC_REFERENCE, frame_chunk=args.entropy_chunk) if args.flag_entropy else {}
     rows = perturbation_study(args.trained_model, cfg["environment"], args.sweep_mu, args.sweep_delay, args.flag_fix_cmd, args.explorations, args.perturb,
                               warm_steps=args.perturb_at, frames=args.steps, seed=args.perturb_seed, bucket_steps=bucket, cmd_hz=args.cmd_filter_freq,
                               vel_hz=none_if_off(args.vel_filter_freq), act_hz=none_if_off(args.act_filter_freq),
                               persistent=PERSISTENT_DEFAULT if args.persistent is None else args.persistent,
-                              **(dict(gait=True, mass=args.gait_mass, g=args.gait_g) if args.flag_gait else {}))
-    print(perturbation_table(rows, gait=True) if args.flag_gait else perturbation_table(rows))
+                              **(dict(gait=True, mass=args.gait_mass, g=args.gait_g) if args.flag_gait else {}), **entropy)
+    print(perturbation_table(rows, gait=args.flag_gait, ensemble=args.flag_entropy))
     if args.out:
         out = dict(mu=np.array([r["mu"] for r in rows]), delay=np.array([r["delay"] for r in rows]), cmd=np.array([r["cmd"] for r in rows]),
                    surviving=np.array([r["surviving"] for r in rows]), falls=np.stack([r["falls"] for r in rows]), kicks=np.stack([r["kicks"] for r in rows]))
@@ -222,6 +229,9 @@ def run_perturb(args, cfg):
             out["stat_" + k] = np.stack([r["stats"][k] for r in rows])        # [condition, bucket, exploration]
         for k in (rows[0]["gait"] if args.flag_gait else ()):
             out["gait_" + k] = np.stack([r["gait"][k] for r in rows])
+        for k in (rows[0]["ensemble"] if args.flag_entropy else ()):
+            if rows[0]["ensemble"][k] is not None:
+                out["ensemble_" + k] = np.stack([r["ensemble"][k] for r in rows])  # [condition, frame, ...]
         np.savez_compressed(args.out, **out)
         print("kicks and statistics written to", args.out)
     return rows
