@@ -130,6 +130,56 @@ IRRL_DEV v3 rot_tmul(rot3 R, v3 v) {                                            
              R.r0.z * v.x + R.r1.z * v.y + R.r2.z * v.z);
 }
 
+// A PAIR of 3-vectors under ONE operator (the angular and linear halves of a spatial velocity, acceleration or force: the same rotation, the
+// same cross-product operand, the same inertia): component k is the vf2 (first.k, second.k), so every +, -, * and a * b + c below is one
+// v_pk_*_f32 for both vectors, the shared operand broadcast to both halves.  Every helper is the text of the scalar helper it replaces with
+// vf2 in the place of vf -- the same products fused into the same adds in the same order, half by half -- so results are bit for bit those
+// of the two scalar calls (tests/test_v3p_host.py).  Used only where two vectors really go through one operator with no lane exchange in
+// between; built from vf2, pk2, pk_lo, pk_hi and vf2's operators alone (both lane layouts and the host emulation have them).
+// -DIRRL_NO_V3P (A/B builds): the pair is two v3 and every helper the two scalar calls.
+#ifdef IRRL_NO_V3P
+struct v3p { v3 a, b; };
+IRRL_DEV v3p pk3(v3 a, v3 b) { v3p r; r.a = a; r.b = b; return r; }
+IRRL_DEV v3 lo3(v3p p) { return p.a; }
+IRRL_DEV v3 hi3(v3p p) { return p.b; }
+IRRL_DEV v3p operator+(v3p a, v3p b) { return pk3(a.a + b.a, a.b + b.b); }
+IRRL_DEV v3p operator-(v3p a, v3p b) { return pk3(a.a - b.a, a.b - b.b); }
+IRRL_DEV v3p operator*(vf s, v3p a) { return pk3(s * a.a, s * a.b); }
+IRRL_DEV v3p cross(v3 a, v3p b) { return pk3(cross(a, b.a), cross(a, b.b)); }
+IRRL_DEV v3p cross(v3p a, v3 b) { return pk3(cross(a.a, b), cross(a.b, b)); }
+IRRL_DEV v3p cross(v3p a, v3p b) { return pk3(cross(a.a, b.a), cross(a.b, b.b)); }
+IRRL_DEV v3p mul(sym3 A, v3p v) { return pk3(mul(A, v.a), mul(A, v.b)); }
+IRRL_DEV v3p rot_mul(rot3 R, v3p v) { return pk3(rot_mul(R, v.a), rot_mul(R, v.b)); }
+IRRL_DEV v3p rot_tmul(rot3 R, v3p v) { return pk3(rot_tmul(R, v.a), rot_tmul(R, v.b)); }
+#else
+struct v3p { vf2 x, y, z; };
+IRRL_DEV v3p mk3p(vf2 x, vf2 y, vf2 z) { v3p r; r.x = x; r.y = y; r.z = z; return r; }
+IRRL_DEV v3p pk3(v3 a, v3 b) { return mk3p(pk2(a.x, b.x), pk2(a.y, b.y), pk2(a.z, b.z)); }
+IRRL_DEV v3 lo3(v3p p) { return mk3(pk_lo(p.x), pk_lo(p.y), pk_lo(p.z)); }
+IRRL_DEV v3 hi3(v3p p) { return mk3(pk_hi(p.x), pk_hi(p.y), pk_hi(p.z)); }
+IRRL_DEV v3p operator+(v3p a, v3p b) { return mk3p(a.x + b.x, a.y + b.y, a.z + b.z); }
+IRRL_DEV v3p operator-(v3p a, v3p b) { return mk3p(a.x - b.x, a.y - b.y, a.z - b.z); }
+IRRL_DEV v3p operator*(vf s, v3p a) { return mk3p(s * a.x, s * a.y, s * a.z); }
+IRRL_DEV v3p cross(v3 a, v3p b) { return mk3p(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+IRRL_DEV v3p cross(v3p a, v3 b) { return mk3p(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+IRRL_DEV v3p cross(v3p a, v3p b) { return mk3p(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+IRRL_DEV v3p mul(sym3 A, v3p v) {
+  return mk3p(A.xx * v.x + A.xy * v.y + A.xz * v.z, A.xy * v.x + A.yy * v.y + A.yz * v.z, A.xz * v.x + A.yz * v.y + A.zz * v.z);
+}
+IRRL_DEV v3p rot_mul(rot3 R, v3p v) {                                                                  // (R a, R b)
+  return mk3p(R.r0.x * v.x + R.r0.y * v.y + R.r0.z * v.z, R.r1.x * v.x + R.r1.y * v.y + R.r1.z * v.z, R.r2.x * v.x + R.r2.y * v.y + R.r2.z * v.z);
+}
+IRRL_DEV v3p rot_tmul(rot3 R, v3p v) {                                                                 // (R^T a, R^T b)
+  return mk3p(R.r0.x * v.x + R.r1.x * v.y + R.r2.x * v.z, R.r0.y * v.x + R.r1.y * v.y + R.r2.y * v.z, R.r0.z * v.x + R.r1.z * v.y + R.r2.z * v.z);
+}
+#endif
+// a 6-vector u = [linear | angular] as the pair (u[0..2], u[3..5]) and back
+IRRL_DEV v3p pk6(const vf u[6]) { return pk3(mk3(u[0], u[1], u[2]), mk3(u[3], u[4], u[5])); }
+IRRL_DEV void unpk6(v3p p, vf u[6]) {
+  const v3 a = lo3(p), b = hi3(p);
+  u[0] = a.x; u[1] = a.y; u[2] = a.z; u[3] = b.x; u[4] = b.y; u[5] = b.z;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Philox4x32-10 counter RNG: counter = (env, episode, step, purpose), key = (seed, "IRR1")
 // ---------------------------------------------------------------------------------------------
@@ -1165,12 +1215,14 @@ IRRL_DEV void physics_substep(const EnvParams &P, EnvLane &L, const vf pT[3]) {
   Ioc.yy = sub_suffix_sum(Io.yy); Ioc.yz = sub_suffix_sum(Io.yz); Ioc.zz = sub_suffix_sum(Io.zz);
   IRRL_MARK("crba_ci");
   // CRBA column of joint `sub` (D) and its entries of C_l
-  v3 Pc = cross(ax, hc - mc * p_s);
-  v3 Lc = mul(Ioc, ax) - cross(hc, cross(ax, p_s));
+  const v3p axp = cross(ax, pk3(hc - mc * p_s, p_s));           // the joint axis against both arms
+  v3 Pc = lo3(axp);
+  v3 Lc = mul(Ioc, ax) - cross(hc, hi3(axp));
   vf Bs[6] = {Pc.x, Pc.y, Pc.z, Lc.x, Lc.y, Lc.z};
   vf ck0 = (Lc.x - (k.pA.y * Pc.z - k.pA.z * Pc.y)) + vsel(is0, rotor, 0.0f);        // e_x . (L - pA x P)
-  vf ck1 = dot(k.h, Lc - cross(k.pT, Pc)) + vsel(is1, rotor, 0.0f);
-  vf ck2 = dot(k.h, Lc - cross(k.pS, Pc)) + vsel(sub == 2, rotor, 0.0f);
+  const v3p m12 = pk3(Lc, Lc) - cross(pk3(k.pT, k.pS), Pc);      // moments about the hip and knee origins
+  vf ck1 = dot(k.h, lo3(m12)) + vsel(is1, rotor, 0.0f);
+  vf ck2 = dot(k.h, hi3(m12)) + vsel(sub == 2, rotor, 0.0f);
   LegDyn D;
   {
     vf C00 = sub_bcast<0>(ck0), C01 = sub_bcast<1>(ck0), C02 = sub_bcast<2>(ck0), C11 = sub_bcast<1>(ck1), C12 = sub_bcast<2>(ck1), C22 = sub_bcast<2>(ck2);
@@ -1257,17 +1309,22 @@ IRRL_DEV void physics_substep(const EnvParams &P, EnvLane &L, const vf pT[3]) {
   v3 alp = al - dal;                                           // parent's angular acceleration
   v3 dj = mk3(vsel(is3, 0.0f, PICK3(k.pA.x, k.pT.x - k.pA.x, k.pS.x - k.pT.x)), vsel(is3, 0.0f, PICK3(k.pA.y, k.pT.y - k.pA.y, k.pS.y - k.pT.y)),
               vsel(is3, 0.0f, PICK3(k.pA.z, k.pT.z - k.pA.z, k.pS.z - k.pT.z)));
-  v3 da = cross(alp, dj) + cross(wp, cross(wp, dj));
+  const v3p dap = cross(pk3(alp, wp), pk3(dj, cross(wp, dj)));   // (alp x d, wp x (wp x d))
+  v3 da = lo3(dap) + hi3(dap);
   v3 a = a0 + mk3(sub_prefix_sum(da.x), sub_prefix_sum(da.y), sub_prefix_sum(da.z));
 #endif
-  v3 f = m_s * (a + cross(al, rc) + cross(w, cross(w, rc)));
-  v3 n0 = mul(IB, al) + cross(w, mul(IB, w)) + cross(c, f);   // moment about the BASE origin: n + (p_s + rc) x f
+  const v3p alw = pk3(al, w);
+  const v3p fp = cross(alw, pk3(rc, cross(w, rc)));              // (al x rc, w x (w x rc))
+  v3 f = m_s * (a + lo3(fp) + hi3(fp));
+  const v3p Iaw = mul(IB, alw);                                  // (I al, I w)
+  v3 n0 = lo3(Iaw) + cross(w, hi3(Iaw)) + cross(c, f);        // moment about the BASE origin: n + (p_s + rc) x f
   v3 F = mk3(sub_suffix_sum(f.x), sub_suffix_sum(f.y), sub_suffix_sum(f.z));
   v3 N0 = mk3(sub_suffix_sum(n0.x), sub_suffix_sum(n0.y), sub_suffix_sum(n0.z));
   vf b_s = dot(ax, N0 - cross(p_s, F));                         // joint bias = axis . moment about the joint origin
   {
-    v3 fb = L.m.m0 * (a0 + cross(wB, cross(wB, L.m.com0)));
-    v3 nb = cross(wB, mul(I0, wB)) + cross(L.m.com0, fb);
+    const v3p bp = cross(wB, pk3(cross(wB, L.m.com0), mul(I0, wB)));   // (wB x (wB x com0), wB x (I0 wB))
+    v3 fb = L.m.m0 * (a0 + lo3(bp));
+    v3 nb = hi3(bp) + cross(L.m.com0, fb);
     D.bias_b[0] = fb.x + sub_bcast<0>(legs_sum(F.x)); D.bias_b[1] = fb.y + sub_bcast<0>(legs_sum(F.y)); D.bias_b[2] = fb.z + sub_bcast<0>(legs_sum(F.z));
     D.bias_b[3] = nb.x + sub_bcast<0>(legs_sum(N0.x)); D.bias_b[4] = nb.y + sub_bcast<0>(legs_sum(N0.y)); D.bias_b[5] = nb.z + sub_bcast<0>(legs_sum(N0.z));
   }
@@ -1327,8 +1384,20 @@ IRRL_DEV void physics_substep(const EnvParams &P, EnvLane &L, const vf pT[3]) {
     for (int i = 0; i < 6; i++) { Ya[0][i] = sub_bcast<0>(Yr[i]); Ya[1][i] = sub_bcast<1>(Yr[i]); Ya[2][i] = sub_bcast<2>(Yr[i]); }
     // own Delassus block, row r: Y_r . Y_c + JC_r . Jl_c
     vf gr[3];
+#ifndef IRRL_NO_V3P
+    {
+      // columns 0 and 1 as a pair: the same multipliers JC_r and Y_r against two columns (the loop below, two accumulators in one)
+      vf2 acc = jc0 * pk2(Jl[0][0], Jl[1][0]) + jc1 * pk2(Jl[0][1], Jl[1][1]) + jc2 * pk2(Jl[0][2], Jl[1][2]);
+#pragma unroll
+      for (int i = 0; i < 6; i++) acc = acc + Yr[i] * pk2(Ya[0][i], Ya[1][i]);
+      gr[0] = pk_lo(acc); gr[1] = pk_hi(acc);
+    }
+#pragma unroll
+    for (int cc = 2; cc < 3; cc++) {
+#else
 #pragma unroll
     for (int cc = 0; cc < 3; cc++) {
+#endif
       vf acc = jc0 * Jl[cc][0] + jc1 * Jl[cc][1] + jc2 * Jl[cc][2];
 #pragma unroll
       for (int i = 0; i < 6; i++) acc += Yr[i] * Ya[cc][i];
@@ -1460,8 +1529,7 @@ _Pragma("unroll 2")
 #pragma unroll
     for (int i = 0; i < 6; i++) xbc[i] = legs_sum(sub_sum(Yr[i] * lam_r));
     l6_bwd(D.L6, xbc);
-#pragma unroll
-    for (int i = 0; i < 6; i++) ub[i] += xbc[i];
+    unpk6(pk6(ub) + pk6(xbc), ub);
     {
       vf v0 = sub_sum(jc0 * lam_r), v1 = sub_sum(jc1 * lam_r), v2 = sub_sum(jc2 * lam_r);   // columns of JC^T lam
       vf v = PICK3(v0, v1, v2);
@@ -1496,8 +1564,10 @@ _Pragma("unroll 2")
   L.in_contact = vsel_i(active, 1, 0);
   L.ccount = L.ccount + to_u(L.in_contact);
   // back to world-frame gv, then positions (semi-implicit Euler); joint `sub` integrates in its own lane
-  L.vw = rot_mul(R, mk3(ub[0], ub[1], ub[2]));
-  L.ww = rot_mul(R, mk3(ub[3], ub[4], ub[5]));
+  {
+    const v3p VWn = rot_mul(R, pk6(ub));
+    L.vw = lo3(VWn); L.ww = hi3(VWn);
+  }
   {
     vf qn = q_s + dt * ul_s;
     L.q[0] = sub_bcast<0>(qn); L.q[1] = sub_bcast<1>(qn); L.q[2] = sub_bcast<2>(qn);

@@ -1,5 +1,8 @@
 """Build A/B variants of libirrl_env.so (same ABI, different -D switches) into csrc/_variants/ for one-call GPU comparisons.
-usage: python tools/build_variants.py name=-DFLAG[,-DFLAG2] ...   (name 'base' = no extra flags)"""
+usage: python tools/build_variants.py name=-DFLAG[,-DFLAG2] ...   (name 'base' = no extra flags)
+Switches of the env kernels that exist for this: -DIRRL_NO_FMA_DPP (lanes_hip16.hpp: exchange + multiply-add as two instructions),
+-DIRRL_NO_BOX (env_core.hpp: no trunk-box collider), -DIRRL_NO_V3P (env_core.hpp: pairs of 3-vectors as two scalar v3 -- the 16-lane units
+then assemble to the instructions of the build before the pairs), -DIRRL_RNEA_SERIAL, -DIRRL_PROFILE_WAVES."""
 import os, subprocess, sys
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 from high_speed_quadrupedal_locomotion_by_irrl_amd import build as B
@@ -25,9 +28,10 @@ for spec in sys.argv[1:]:
     B_ENV = env_flags
     common = list(B.COMMON_FLAGS) + flags
     for src, fl, obj in (("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=16"] + B_ENV, "l16"),
-                         ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=16", "-DIRRL_ROLLOUT_RT_UNIT"] + B_ENV, "l16rt"), ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=4"] + B_ENV, "l4"),
+                         ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=16", "-DIRRL_ROLLOUT_RT_UNIT"] + B_ENV, "l16rt"),
+                         ("env_kernels.hip", list(B.EVAL_UNIT_FLAGS) + B_ENV, "l16ev"), ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=4"] + B_ENV, "l4"),
                          ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=4", "-DIRRL_L4_WAVES2"] + (B_ENV if swapped else list(B.ENV_FLAGS_W2)), "l4w2"),
-                         ("irrl_env_abi.hip", [], "abi")):
+                         ("irrl_env_abi.hip", [], "abi"), ("eval_ensemble.hip", [], "ens")):      # (the units of build.build())
         o = os.path.join(out, f"{name}_{obj}.o")
         objs.append(o)
         if src == "env_kernels.hip":   # same route as the product build: device assembly -> ISA pass -> assemble -> embed
