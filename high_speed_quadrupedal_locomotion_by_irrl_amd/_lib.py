@@ -126,6 +126,9 @@ SIGNATURES = {
     # the ensemble analysis of a body recorder: rec_body, rows, num_envs, conditions, explorations, frame_first, frame_every, frames | mask |
     # `const irrl_eval_ensemble_spec *` (EvalEnsembleSpec below) | entropy, counts, hist, moments | stream
     "irrl_eval_ensemble": (C.c_int, [vp] + [C.c_int] * 7 + [vp, vp] + [vp] * 4 + [vp]),
+    # the recurrence analysis of a body recorder: rec_body, rows, num_envs, frame_first, frame_every, frames |
+    # `const irrl_eval_recurrence_spec *` (EvalRecurrenceSpec below) | counts, lag, matrix | stream
+    "irrl_eval_recurrence": (C.c_int, [vp] + [C.c_int] * 5 + [vp] + [vp] * 3 + [vp]),
 }
 
 
@@ -151,6 +154,14 @@ class EvalEnsembleSpec(C.Structure):
     per feature, hist_bins = 0 for no histograms); C.byref(...)"""
     _fields_ = [("lb", C.c_double * 6), ("ub", C.c_double * 6), ("prec", C.c_double * 6), ("hist_lo", C.c_double * 6), ("hist_hi", C.c_double * 6),
                 ("hist_bins", C.c_int)]
+
+
+class EvalRecurrenceSpec(C.Structure):
+    """struct irrl_eval_recurrence_spec of include/irrl_env.h (a HOST struct of scalars: the box lb / ub, the level width eps, the number of
+    levels, the recurrence radius in levels, the Theiler window, the shortest diagonal / vertical line, the number of lag words, the robots whose
+    matrices are wanted); C.byref(...)"""
+    _fields_ = [("lb", C.c_double * 6), ("ub", C.c_double * 6), ("eps", C.c_double), ("steps", C.c_int), ("radius", C.c_int), ("theiler", C.c_int),
+                ("lmin", C.c_int), ("vmin", C.c_int), ("lags", C.c_int), ("matrix_count", C.c_int), ("matrix_env", C.c_int * 8)]
 
 
 def load():

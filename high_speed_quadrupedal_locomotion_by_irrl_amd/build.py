@@ -185,14 +185,15 @@ def build(force=False, verbose=False, extra_flags=()):
     # the env kernels in both lane layouts (same source, different lane-primitive header; the 4-lane layout once more for two waves per
     # SIMD; the 16-lane layout once more for the run-time-solver twins of the rollout kernels alone, and once more for the persistent evaluation
     # kernel alone) through the ISA pass, then the C-ABI +
-    # LSTM kernels and the ensemble analysis (a translation unit of its own) through the plain driver
+    # LSTM kernels, the ensemble analysis and the recurrence analysis (a translation unit each) through the plain driver
     units = [("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=16"] + ENV_FLAGS, "env_kernels_l16.o"),
              ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=16", "-DIRRL_ROLLOUT_RT_UNIT"] + ENV_FLAGS, "env_kernels_l16rt.o"),
              ("env_kernels.hip", EVAL_UNIT_FLAGS + ENV_FLAGS, "env_kernels_l16ev.o"),
              ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=4"] + ENV_FLAGS, "env_kernels_l4.o"),
              ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=4", "-DIRRL_L4_WAVES2"] + ENV_FLAGS_W2, "env_kernels_l4w2.o"),
              ("irrl_env_abi.hip", ['-DIRRL_SRC_HASH="%s"' % want], "irrl_env_abi.o"),
-             ("eval_ensemble.hip", [], "eval_ensemble.o")]
+             ("eval_ensemble.hip", [], "eval_ensemble.o"),
+             ("eval_recurrence.hip", [], "eval_recurrence.o")]
     from concurrent.futures import ThreadPoolExecutor
     def one(u):
         src, flags, obj = u

@@ -7,6 +7,7 @@
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 #include "../../include/irrl_env.h"
 
 #ifdef __HIPCC__
@@ -351,5 +352,73 @@ static inline const char *irrl_eval_ensemble_spec_error(const irrl_eval_ensemble
     for (int i = 0; i < IRRL_EVAL_ENSEMBLE_DIM; i++)
       if (!(s.hist_hi[i] > s.hist_lo[i]) || !irrl_eval_ensemble_finite(s.hist_hi[i]) || !irrl_eval_ensemble_finite(s.hist_lo[i]))
         return "hist_lo_i < hist_hi_i, both finite";
+  return NULL;
+}
+
+// ---- the recurrence analysis of a body recorder: frame row, normalised state, squared distance, quantised level (irrl_eval_recurrence) ----
+// What the reference's recurrence plot does with ONE robot's recording (Data_Visualization_Code/Figure4.py:495-509): the state vector of
+// irrl_eval_ensemble_features per frame, centred and divided by a box, all pairwise Euclidean distances, quantised as min(floor(d / eps), steps).
+// the recorder row of analysed frame i
+static inline IRRL_EVAL_FN long long irrl_eval_recurrence_row(int frame_first, int frame_every, int i) {
+  return (long long)frame_first + (long long)i * (long long)frame_every;
+}
+// u_k = (x_k - (lb_k + ub_k) / 2.0) / (ub_k - lb_k) (Figure4.py:502), written with stride `su` between the six words (the kernel keeps the
+// states of a robot as [6][T] in LDS); -> false (frame dropped, nothing written) where a feature is not finite
+static inline IRRL_EVAL_FN bool irrl_eval_recurrence_state(const double *x6, const irrl_eval_recurrence_spec &s, double *u, size_t su) {
+  for (int k = 0; k < IRRL_EVAL_ENSEMBLE_DIM; k++)
+    if (!irrl_eval_ensemble_finite(x6[k])) return false;
+  for (int k = 0; k < IRRL_EVAL_ENSEMBLE_DIM; k++) {
+    const double sum = s.lb[k] + s.ub[k];
+    const double mid = sum / 2.0;
+    const double width = s.ub[k] - s.lb[k];
+    const double centred = x6[k] - mid;
+    u[(size_t)k * su] = centred / width;
+  }
+  return true;
+}
+// d^2 = sum_k D_k D_k in index order, D_k = u_i[k] - u_j[k]; every product a statement of its own (no fused multiply-add).  si / sj: the
+// strides between the six words of u_i / u_j.  The same bits with i and j exchanged (D_k changes its sign alone).
+static inline IRRL_EVAL_FN double irrl_eval_recurrence_dist2(const double *ui, size_t si, const double *uj, size_t sj) {
+  double d2 = 0.0;
+  for (int k = 0; k < IRRL_EVAL_ENSEMBLE_DIM; k++) {
+    const double delta = ui[(size_t)k * si] - uj[(size_t)k * sj];
+    const double sq = delta * delta;
+    d2 = d2 + sq;
+  }
+  return d2;
+}
+// q = c >= steps ? steps : (int)floor(c) with c = sqrt(d^2) / eps; a d^2 that is not a number (states that overflowed) gives `steps` too.
+// Monotone in d^2: sqrt and the division are correctly rounded on host and device.
+static inline IRRL_EVAL_FN int irrl_eval_recurrence_level(double d2, double eps, int steps) {
+  const double d = sqrt(d2);
+  const double c = d / eps;
+  if (!(c < (double)steps)) return steps;
+  return (int)floor(c);
+}
+// The smallest d^2 whose level reaches `radius` (+inf where none does): level(d2) < radius  <=>  d2 < threshold for every d2 >= 0, because the
+// level is monotone.  Bisection over the bit patterns of the non-negative doubles, which are ordered like their values; host code, run once per
+// call, so that the kernel decides R_ij without a square root and a division where nobody asks for q itself.
+static inline double irrl_eval_recurrence_threshold(double eps, int steps, int radius) {
+  uint64_t lo = 0, hi = 0x7FF0000000000000ull;               // level(0) = 0 < radius <= steps = level(+inf)
+  while (hi - lo > 1) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    double d2;
+    memcpy(&d2, &mid, sizeof d2);
+    if (irrl_eval_recurrence_level(d2, eps, steps) < radius) lo = mid; else hi = mid;
+  }
+  double t;
+  memcpy(&t, &hi, sizeof t);
+  return t;
+}
+// what is wrong with a spec, or NULL: the refusals of irrl_eval_recurrence that concern the spec alone (matrix_env needs num_envs: the caller's)
+static inline const char *irrl_eval_recurrence_spec_error(const irrl_eval_recurrence_spec &s) {
+  for (int k = 0; k < IRRL_EVAL_ENSEMBLE_DIM; k++)
+    if (!irrl_eval_ensemble_finite(s.lb[k]) || !irrl_eval_ensemble_finite(s.ub[k]) || !(s.ub[k] > s.lb[k])) return "lb_k < ub_k, both finite";
+  if (!(s.eps > 0.0) || !irrl_eval_ensemble_finite(s.eps)) return "eps > 0, finite";
+  if (s.steps < 1 || s.steps > 255) return "steps lies in 1 .. 255";
+  if (s.radius < 1 || s.radius > s.steps) return "radius lies in 1 .. steps";
+  if (s.theiler < 0 || s.lmin < 1 || s.vmin < 1) return "theiler >= 0, lmin >= 1, vmin >= 1";
+  if (s.lags < 0) return "lags lies in 0 .. frames";
+  if (s.matrix_count < 0 || s.matrix_count > IRRL_EVAL_RECURRENCE_MAX_MATRICES) return "matrix_count lies in 0 .. 8";
   return NULL;
 }

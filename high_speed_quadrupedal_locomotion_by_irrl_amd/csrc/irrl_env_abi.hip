@@ -22,6 +22,7 @@
 #include "../../include/irrl_env.h"
 #include "eval_rollout.hpp"   // the evaluation loop's kernels (irrl_lstm_eval_rollout below)
 #include "eval_ensemble.hpp"  // the ensemble analysis: argument block and launcher of csrc/eval_ensemble.hip (irrl_eval_ensemble below)
+#include "eval_recurrence.hpp"  // the recurrence analysis: argument block and launcher of csrc/eval_recurrence.hip (irrl_eval_recurrence below)
 
 #include <cmath>
 #include <string>
@@ -1352,6 +1353,34 @@ int irrl_eval_ensemble(const float *rec_body, int rows, int num_envs, int condit
   a.frame_first = frame_first; a.frame_every = frame_every; a.C = conditions; a.F = frames; a.mask = mask; a.spec = *spec;
   a.entropy = entropy; a.counts = counts; a.hist = spec->hist_bins > 0 ? hist : nullptr; a.moments = moments;
   HIP_TRY(irrl_eval_ensemble_launch(a, (hipStream_t)hip_stream));
+  return 0;
+}
+
+// ---- recurrence analysis of a body recorder (kernel and launcher: csrc/eval_recurrence.hip; per-pair arithmetic: csrc/eval_elements.hpp) ----
+int irrl_eval_recurrence(const float *rec_body, int rows, int num_envs, int frame_first, int frame_every, int frames,
+                         const irrl_eval_recurrence_spec *spec, uint32_t *counts, uint32_t *lag, uint8_t *matrix, void *hip_stream) {
+  const std::string w = "irrl_eval_recurrence: ";
+  if (!rec_body || !spec || !counts) { g_err = w + "NULL rec_body, spec or counts"; return 1; }
+  if (num_envs < 1) { g_err = w + "num_envs >= 1"; return 1; }
+  if (frames < 0 || frames > IRRL_EVAL_RECURRENCE_MAX_FRAMES) {
+    g_err = w + "frames lies in 0 .. 2048 (one workgroup keeps a robot's states in LDS)"; return 1;
+  }
+  if (frame_first < 0 || frame_every < 1) { g_err = w + "frame_first >= 0, frame_every >= 1"; return 1; }
+  if (frames > 0 && irrl_eval_recurrence_row(frame_first, frame_every, frames - 1) >= (long long)rows) {
+    g_err = w + "frame_first + (frames - 1) * frame_every reaches past the recorder's rows"; return 1;
+  }
+  if (const char *bad = irrl_eval_recurrence_spec_error(*spec)) { g_err = w + "spec: " + bad; return 1; }
+  if (spec->lags > frames) { g_err = w + "spec: lags lies in 0 .. frames"; return 1; }
+  if (spec->lags > 0 && !lag) { g_err = w + "lags > 0 with a NULL lag"; return 1; }
+  if (spec->matrix_count > 0 && !matrix) { g_err = w + "matrix_count > 0 with a NULL matrix"; return 1; }
+  for (int s = 0; s < spec->matrix_count; s++)
+    if (spec->matrix_env[s] < 0 || spec->matrix_env[s] >= num_envs) { g_err = w + "a matrix_env lies outside 0 .. num_envs - 1"; return 1; }
+  if (frames == 0) return 0;
+  RecurrenceArgs a;
+  a.rec_body = rec_body; a.N = num_envs; a.T = frames; a.frame_first = frame_first; a.frame_every = frame_every; a.spec = *spec;
+  a.threshold = irrl_eval_recurrence_threshold(spec->eps, spec->steps, spec->radius);
+  a.counts = counts; a.lag = spec->lags > 0 ? lag : nullptr; a.matrix = spec->matrix_count > 0 ? matrix : nullptr;
+  HIP_TRY(irrl_eval_recurrence_launch(a, (hipStream_t)hip_stream));
   return 0;
 }
 

@@ -852,6 +852,258 @@ def poincare_section(body_rows, every, offset=0):
     return ensemble_features(np.asarray(body_rows)[offset::every])
 
 
+# ---- the recurrence analysis of a body recorder: the time x time matrix of quantised state distances and its measures per robot ----
+# lb, ub, eps, steps: Data_Visualization_Code/Figure4.py:495-509 (the recurrence plot).  radius, theiler, lmin, vmin are THIS build's choices: the
+# reference draws the matrix and computes no measures.
+RECURRENCE_SPEC_REFERENCE = dict(lb=(0.2, -1.0, -1.0, -5.0, -5.0, -5.0), ub=(0.4, 1.0, 1.0, 5.0, 5.0, 5.0), eps=0.001, steps=40,
+                                 radius=10, theiler=10, lmin=2, vmin=2)
+RECURRENCE_MAX_FRAMES = 2048     # IRRL_EVAL_RECURRENCE_MAX_FRAMES
+RECURRENCE_MAX_MATRICES = 8      # IRRL_EVAL_RECURRENCE_MAX_MATRICES
+RECURRENCE_COUNTS = ("kept", "rec", "diag_points", "diag_lines", "diag_max", "vert_points", "vert_lines", "vert_max", "rec_full")
+RECURRENCE_EDGE = 1e-9           # recurrence_edges: how close to a level boundary (in levels) a pair counts as "on an edge"
+
+
+def recurrence_spec(spec):
+    """a spec mapping (keys of RECURRENCE_SPEC_REFERENCE) -> dict of the float64 [6] arrays lb, ub, the float eps and the ints steps, radius,
+    theiler, lmin, vmin, refused like irrl_eval_recurrence refuses its struct (what depends on the call -- frames, lags, the matrix robots -- is
+    refused by the functions that take them)"""
+    s = {k: np.array(spec[k], np.float64).reshape(6) for k in ("lb", "ub")}
+    s["eps"] = float(spec["eps"])
+    for k in ("steps", "radius", "theiler", "lmin", "vmin"):
+        s[k] = int(spec[k])
+    if not (np.all(np.isfinite(s["lb"])) and np.all(np.isfinite(s["ub"])) and np.all(s["ub"] > s["lb"])):
+        raise ValueError("recurrence spec: lb_k < ub_k, both finite")
+    if not (np.isfinite(s["eps"]) and s["eps"] > 0):
+        raise ValueError("recurrence spec: eps > 0, finite")
+    if s["steps"] < 1 or s["steps"] > 255:
+        raise ValueError("recurrence spec: steps lies in 1 .. 255")
+    if s["radius"] < 1 or s["radius"] > s["steps"]:
+        raise ValueError("recurrence spec: radius lies in 1 .. steps")
+    if s["theiler"] < 0 or s["lmin"] < 1 or s["vmin"] < 1:
+        raise ValueError("recurrence spec: theiler >= 0, lmin >= 1, vmin >= 1")
+    return s
+
+
+def _recurrence_frames(rows, frame_first, frame_every, frames):
+    frame_first, frame_every, frames = _ensemble_frames(rows, frame_first, frame_every, frames)
+    if frames > RECURRENCE_MAX_FRAMES:
+        raise ValueError("frames lies in 0 .. %d" % RECURRENCE_MAX_FRAMES)
+    return frame_first, frame_every, frames
+
+
+def _recurrence_lags(lags, frames):
+    lags = frames if lags is None else int(lags)
+    if lags < 0 or lags > frames:
+        raise ValueError("lags lies in 0 .. frames")
+    return lags
+
+
+def recurrence_states(body, spec, frame_first=0, frame_every=1, frames=None):
+    """body [rows, N, 13] -> (u [N, T, 6] float64, kept bool [N, T]): frame i is row frame_first + i * frame_every, x = ensemble_features(row),
+    kept iff the six features are finite, u = (x - (lb + ub) / 2.0) / (ub - lb) (irrl_eval_recurrence_state; zeros where dropped)"""
+    s = recurrence_spec(spec)
+    body = np.asarray(body)
+    frame_first, frame_every, T = _recurrence_frames(body.shape[0], frame_first, frame_every, frames)
+    x = ensemble_features(body[frame_first:frame_first + T * frame_every:frame_every][:T])
+    kept = np.all(np.isfinite(x), -1)
+    mid = (s["lb"] + s["ub"]) / 2.0
+    width = s["ub"] - s["lb"]
+    with np.errstate(over="ignore"):
+        u = (np.where(kept[..., None], x, 0.0) - mid) / width
+    u = np.where(kept[..., None], u, 0.0)
+    return np.ascontiguousarray(u.transpose(1, 0, 2)), np.ascontiguousarray(kept.T)
+
+
+def _recurrence_distances(u_n):
+    """one robot's states [T, 6] -> the f64 distance matrix d = sqrt(d2) [T, T], d2 summed over the features in index order, every product
+    rounded on its own (irrl_eval_recurrence_dist2)"""
+    T = u_n.shape[0]
+    d2 = np.zeros((T, T))
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k in range(6):
+            delta = u_n[:, None, k] - u_n[None, :, k]
+            sq = delta * delta
+            d2 = d2 + sq
+        return np.sqrt(d2)
+
+
+def recurrence_levels_numpy(body, spec, frame_first=0, frame_every=1, frames=None):
+    """The float64 twin of the element functions of irrl_eval_recurrence (csrc/eval_elements.hpp), statement for statement: body [rows, N, 13] ->
+    q uint8 [N, T, T], q_ij = c >= steps ? steps : floor(c) with c = sqrt(d2) / eps, `steps` for a pair with a dropped frame (so the diagonal is
+    0 for a kept frame and `steps` for a dropped one: recurrence_kept)"""
+    s = recurrence_spec(spec)
+    u, kept = recurrence_states(body, s, frame_first, frame_every, frames)
+    N, T = kept.shape
+    q = np.empty((N, T, T), np.uint8)
+    for n in range(N):
+        with np.errstate(invalid="ignore", over="ignore"):
+            c = _recurrence_distances(u[n]) / s["eps"]
+            level = np.where(c < s["steps"], np.floor(np.where(c < s["steps"], c, 0.0)), s["steps"])
+        both = kept[n][:, None] & kept[n][None, :]
+        q[n] = np.where(both, level, s["steps"]).astype(np.uint8)
+    return q
+
+
+def recurrence_kept(q):
+    """q [..., T, T] -> kept bool [..., T]: the diagonal is 0 for a kept frame and `steps` >= 1 for a dropped one"""
+    return np.diagonal(np.asarray(q), axis1=-2, axis2=-1) == 0
+
+
+def recurrence_edges(body, spec, frame_first=0, frame_every=1, frames=None, tol=RECURRENCE_EDGE):
+    """body [rows, N, 13] -> bool [N, T, T]: is the pair "on an edge" -- both frames kept and c = d / eps within tol of one of the level boundaries
+    1 .. steps (there is none at 0: c >= 0) --, so that two correct f64 evaluations of the features (different atan2 / asin / fused
+    multiply-adds) may put it into different levels"""
+    s = recurrence_spec(spec)
+    u, kept = recurrence_states(body, s, frame_first, frame_every, frames)
+    N, T = kept.shape
+    out = np.zeros((N, T, T), bool)
+    for n in range(N):
+        with np.errstate(invalid="ignore", over="ignore"):
+            c = _recurrence_distances(u[n]) / s["eps"]
+            r = np.round(c)
+            out[n] = (np.abs(c - r) < tol) & (r >= 1) & (r <= s["steps"]) & kept[n][:, None] & kept[n][None, :]
+    return out
+
+
+def _run_lengths(flags):
+    """a 1-D bool array -> the lengths of its maximal runs of True"""
+    d = np.diff(np.concatenate([[0], np.asarray(flags, np.int8), [0]]))
+    return np.flatnonzero(d == -1) - np.flatnonzero(d == 1)
+
+
+def recurrence_from_levels(q, kept, spec, lags=None):
+    """The integer stage of the twin: q uint8 [N, T, T] (or [T, T]) and kept bool [N, T] (None: recurrence_kept(q)) -> (counts uint32 [N, 9],
+    lag uint32 [N, lags]) as include/irrl_env.h defines them (RECURRENCE_COUNTS; lags None: T).  R_ij = q_ij < radius, w = max(theiler, 1); a
+    diagonal line is a maximal run along i of R_{i,i+tau} for a fixed tau >= w, a vertical line a maximal run along i for a fixed j in the full
+    matrix with the band |i - j| < w removed; the matrix border ends a line."""
+    s = recurrence_spec(spec)
+    q = np.asarray(q)
+    single = q.ndim == 2
+    q = q[None] if single else q
+    N, T = q.shape[0], q.shape[1]
+    kept = recurrence_kept(q) if kept is None else np.asarray(kept, bool).reshape(N, T)
+    lags = _recurrence_lags(lags, T)
+    w = max(s["theiler"], 1)
+    counts, lag = np.zeros((N, 9), np.uint32), np.zeros((N, lags), np.uint32)
+    ii = np.arange(T)
+    band = np.abs(ii[:, None] - ii[None, :]) >= w
+    for n in range(N):
+        R = q[n] < s["radius"]
+        for l in range(lags):
+            lag[n, l] = np.count_nonzero(np.diagonal(R, l))
+        sep = np.zeros(1, bool)
+        diag = [np.concatenate([np.diagonal(R, tau), sep]) for tau in range(w, T)]
+        runs = _run_lengths(np.concatenate(diag)) if diag else np.zeros(0, np.int64)
+        Rb = R & band
+        vruns = _run_lengths(np.concatenate([Rb.T, np.zeros((T, 1), bool)], 1).reshape(-1))
+        long_d, long_v = runs[runs >= s["lmin"]], vruns[vruns >= s["vmin"]]
+        counts[n] = [np.count_nonzero(kept[n]), runs.sum(), long_d.sum(), len(long_d), runs.max() if len(runs) else 0,
+                     long_v.sum(), len(long_v), vruns.max() if len(vruns) else 0, np.count_nonzero(Rb)]
+    return (counts[0], lag[0]) if single else (counts, lag)
+
+
+def recurrence_numpy(body, spec, frame_first=0, frame_every=1, frames=None, lags=None, matrix_env=()):
+    """The twin of irrl_eval_recurrence, both stages: -> dict(counts uint32 [N, 9], lag uint32 [N, lags] (lags None: T), matrix uint8 [len(matrix_env),
+    T, T] -- the levels of the listed robots -- or None)"""
+    q = recurrence_levels_numpy(body, spec, frame_first, frame_every, frames)
+    counts, lag = recurrence_from_levels(q, None, spec, lags)
+    env = _recurrence_matrix_env(matrix_env, q.shape[0])
+    return dict(counts=counts, lag=lag, matrix=q[env] if len(env) else None)
+
+
+def _recurrence_matrix_env(matrix_env, n):
+    env = [int(e) for e in matrix_env]
+    if len(env) > RECURRENCE_MAX_MATRICES:
+        raise ValueError("matrix_count lies in 0 .. %d" % RECURRENCE_MAX_MATRICES)
+    if any(e < 0 or e >= n for e in env):
+        raise ValueError("a matrix_env lies outside 0 .. num_envs - 1")
+    return env
+
+
+def recurrence_struct(spec, lags=0, matrix_env=()):
+    """-> _lib.EvalRecurrenceSpec of a spec, the number of lag words and the robots whose matrices are wanted"""
+    from . import _lib
+    s = recurrence_spec(spec)
+    st = _lib.EvalRecurrenceSpec(eps=s["eps"], lags=int(lags), matrix_count=len(matrix_env), **{k: s[k] for k in ("steps", "radius", "theiler", "lmin", "vmin")})
+    st.lb, st.ub = (C.c_double * 6)(*s["lb"]), (C.c_double * 6)(*s["ub"])
+    st.matrix_env = (C.c_int * 8)(*(list(matrix_env) + [0] * (8 - len(matrix_env))))
+    return st
+
+
+def recurrence_device(rec_body, spec, frame_first=0, frame_every=1, frames=None, lags=None, matrix_env=()):
+    """recurrence_numpy on the device: rec_body a float32 device tensor [rows, N, 13] (PolicyEvaluator.run(record=("body",))) -- ONE call of
+    irrl_eval_recurrence on torch's current stream, one workgroup per robot, no synchronisation -> dict of device tensors counts int32 [N, 9]
+    (RECURRENCE_COUNTS), lag int32 [N, lags] (lags None: T; None with lags = 0), matrix uint8 [len(matrix_env), T, T] (None without robots)."""
+    import torch
+    from . import _lib
+    from ._lib import ptr
+    s = recurrence_spec(spec)
+    if rec_body.dim() != 3 or rec_body.shape[2] != 13 or rec_body.dtype != torch.float32 or not rec_body.is_cuda:
+        raise ValueError("rec_body is a float32 device tensor [rows, N, 13]")
+    rec_body = _lib.contig(rec_body)
+    rows, n = int(rec_body.shape[0]), int(rec_body.shape[1])
+    frame_first, frame_every, T = _recurrence_frames(rows, frame_first, frame_every, frames)
+    lags = _recurrence_lags(lags, T)
+    env = _recurrence_matrix_env(matrix_env, n)
+    st = recurrence_struct(s, lags, env)
+    dev = rec_body.device
+    out = dict(counts=torch.zeros(n, 9, device=dev, dtype=torch.int32), lag=torch.zeros(n, lags, device=dev, dtype=torch.int32) if lags > 0 else None,
+               matrix=torch.zeros(len(env), T, T, device=dev, dtype=torch.uint8) if env else None)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().irrl_eval_recurrence(ptr(rec_body), rows, n, frame_first, frame_every, T, C.cast(C.pointer(st), C.c_void_p),
+                                                    ptr(out["counts"]), ptr(out["lag"]), ptr(out["matrix"]), _lib.stream_ptr(dev)))
+    return out
+
+
+def recurrence_to_numpy(res):
+    """a result of recurrence_device -> the twin's dict of numpy arrays (synchronises; the counters as uint32)"""
+    out = {}
+    for k, v in res.items():
+        a = None if v is None else (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v))
+        out[k] = a.view(np.uint32) if a is not None and k in ("counts", "lag") and a.dtype == np.int32 else a
+    return out
+
+
+def recurrence_measures(counts, T, spec):
+    """counts [..., 9] of T frames -> dict of float64 arrays [...]: RR = REC / points (points = the pairs i < j with j - i >= w, (T - w)(T - w + 1) / 2),
+    DET = DIAG_POINTS / REC, L = DIAG_POINTS / DIAG_LINES, LMAX = DIAG_MAX, LAM = VERT_POINTS / REC_FULL, TT = VERT_POINTS / VERT_LINES; NaN
+    where a denominator is 0"""
+    s = recurrence_spec(spec)
+    c = np.asarray(counts).astype(np.float64)
+    w = max(s["theiler"], 1)
+    points = float(max(int(T) - w, 0) * (max(int(T) - w, 0) + 1) // 2)
+    def ratio(a, b):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(b > 0, a / np.where(b > 0, b, 1.0), np.nan)
+    return dict(RR=ratio(c[..., 1], np.full(c.shape[:-1], points)), DET=ratio(c[..., 2], c[..., 1]), L=ratio(c[..., 2], c[..., 3]), LMAX=c[..., 4],
+                LAM=ratio(c[..., 5], c[..., 8]), TT=ratio(c[..., 5], c[..., 6]))
+
+
+def recurrence_period(lag, T, min_lag, control_dt):
+    """lag [..., lags] (the recurrence count per time lag of T frames) -> dict(lag int64 [...], period_s, period_fraction float64 [...]): the
+    smallest l >= min_lag that maximises lag[l] / (T - l) -- the stride period where the gait is regular --, l * control_dt and that fraction;
+    -1 / NaN / NaN where no lag word lies at or behind min_lag.  Hand in lag words up to about T / 2: at the far end a diagonal has a handful of
+    points and its fraction says little."""
+    lag = np.asarray(lag).astype(np.float64)
+    lags, min_lag = lag.shape[-1], max(int(min_lag), 0)
+    if lags <= min_lag:
+        shape = lag.shape[:-1]
+        return dict(lag=np.full(shape, -1, np.int64), period_s=np.full(shape, np.nan), period_fraction=np.full(shape, np.nan))
+    frac = lag[..., min_lag:] / (int(T) - np.arange(min_lag, lags))
+    best = np.argmax(frac, -1)                                   # (the first of equal maxima)
+    return dict(lag=best + min_lag, period_s=(best + min_lag) * float(control_dt), period_fraction=np.take_along_axis(frac, best[..., None], -1)[..., 0])
+
+
+def recurrence_row(counts, lag, T, spec, control_dt):
+    """one robot's counts [9] and lag [lags] -> what robustness_sweep hands out: dict(RR, DET, L, LMAX, LAM, TT, period_s, period_fraction, kept)"""
+    s = recurrence_spec(spec)
+    m = recurrence_measures(counts, T, s)
+    p = recurrence_period(lag, T, max(s["theiler"], 1), control_dt)
+    out = {k: float(v) for k, v in m.items()}
+    out.update(period_s=float(p["period_s"]), period_fraction=float(p["period_fraction"]), kept=int(np.asarray(counts)[0]))
+    return out
+
+
 # ---- the device loop ----
 def resolve_persistent(persistent, supported):
     """the `persistent` keyword of PolicyEvaluator.run / robustness_sweep (False, True, "auto"; the command line's "off" / "on" too) -> bool;
@@ -1125,7 +1377,7 @@ def load_policy(model_or_policy, device):
 
 def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=1000, steps=2000, cmd_hz=1.0, vel_hz=None, act_hz=None, clip=True,
                      mu_warm=0.8, device=None, persistent=PERSISTENT_DEFAULT, levels=None, level_steps=None, heading=None, gait=False,
-                     mass=None, g=9.81):
+                     mass=None, g=9.81, recurrence=None, recurrence_frames=None, record_body=False):
     """The reference's robustness grid in one pool: len(mus) x len(delays) x len(cmds) Manual-mode envs (condition index = (i_mu * len(delays) +
     i_delay) * len(cmds) + i_cmd), `warm_steps` control steps on friction mu_warm, then `steps` on the condition's own friction over which the
     statistics are taken.  env_cfg: the `environment:` mapping of a config.  persistent: PolicyEvaluator.run's keyword (same statistics bit for bit
@@ -1136,7 +1388,13 @@ def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=100
     statistics buckets per level; -> one row per (condition, level), taken over the SECOND half of the level, with the keys `level` and
     `cmd_level` (the commanded v_x of that level).
     gait: every row gains the keys of gait_from_sums over the same frames -- cot, power_mean, duty0 .. 3, stride_hz0 .. 3, ... -- with `mass`
-    (None: each env's own total) and g; off, the rows are what they were."""
+    (None: each env's own total) and g; off, the rows are what they were.
+    recurrence: a spec (RECURRENCE_SPEC_REFERENCE) -- the body recorder is kept on the device for the run and every row gains `recurrence` =
+    dict(RR, DET, L, LMAX, LAM, TT, period_s, period_fraction, kept) (recurrence_row: the measures of irrl_eval_recurrence and the stride period
+    out of the lag words 0 .. T / 2 from the Theiler window on) over the LAST recurrence_frames = T frames of the run (default: min(steps, 800));
+    with a staircase over the last T frames of each level's second half (refused if they do not fit); the rows of the first 8 conditions also
+    carry `matrix` uint8 [T, T], the levels of the recurrence plot.  record_body: every row carries `body` [steps, 13] (staircase: [level_steps,
+    13], the level's frames), whose last T frames the recurrence analysis saw.  Without these keywords the rows are what they were, key for key."""
     import torch
     import yaml
     from . import __BLACKPANTHER_V55_RESOURCE_DIRECTORY__ as rsc
@@ -1144,6 +1402,16 @@ def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=100
     grid = [(float(m), int(d), float(c)) for m in mus for d in delays for c in cmds]
     if not grid:
         raise ValueError("empty sweep")
+    if recurrence is not None:
+        recurrence = recurrence_spec(recurrence)
+        window = (int(level_steps) // 2 if level_steps is not None else 0) if levels is not None else int(steps)
+        T_rec = min(window, 800) if recurrence_frames is None else int(recurrence_frames)
+        if T_rec < 1 or T_rec > RECURRENCE_MAX_FRAMES:
+            raise ValueError("recurrence_frames lies in 1 .. %d" % RECURRENCE_MAX_FRAMES)
+        if T_rec > window:
+            raise ValueError("recurrence_frames = %d does not fit %s" % (T_rec, "the second half of a level" if levels is not None else "the run's steps"))
+    elif recurrence_frames is not None:
+        raise ValueError("recurrence_frames needs a recurrence spec")
     cfg = dict(env_cfg.get("environment", env_cfg))
     cfg["num_envs"] = len(grid)
     cfg["Manual"] = True
@@ -1170,23 +1438,46 @@ def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=100
         coeff[:, 0] = [g[0] for g in grid]                     # (the setter's copy is ordered on the pool's stream, behind the warm-up)
         env.SetContactCoefficient(coeff)
     ev.zero_statistics()
-    ev.run(steps, persistent=persistent)
+    if recurrence is None and not record_body:
+        ev.run(steps, persistent=persistent)
+        extra = lambda i, l: {}
+    else:
+        rec = ev.run(steps, record=("body",), persistent=persistent)
+        span = steps if levels is None else level_steps               # a row's frames: the run, or its level
+        parts = []
+        if recurrence is not None:
+            shown = list(range(min(len(grid), RECURRENCE_MAX_MATRICES)))
+            for l in range(1 if levels is None else levels):
+                parts.append(recurrence_to_numpy(recurrence_device(rec["body"], recurrence, frame_first=(l + 1) * span - T_rec, frames=T_rec, lags=T_rec // 2 + 1,
+                                                                   matrix_env=shown)))
+        body = rec["body"].cpu().numpy() if record_body else None
+        rec = None
+
+        def extra(i, l):
+            out = {}
+            if parts:
+                out["recurrence"] = recurrence_row(parts[l]["counts"][i], parts[l]["lag"][i], T_rec, recurrence, ev._dt)
+                if i < len(shown):
+                    out["matrix"] = parts[l]["matrix"][i]
+            if body is not None:
+                out["body"] = body[l * span:(l + 1) * span, i]
+            return out
     number = lambda k, x: int(x) if k in ("falls", "frames", "gait_frames") else float(x)
     if levels is None:
         st = ev.statistics()
         if gait:
             st.update(ev.gait_statistics(mass, g))
-        return [dict(mu=m, delay=d, cmd=c, **{k: number(k, v[i]) for k, v in st.items()}) for i, (m, d, c) in enumerate(grid)]
+        return [dict(mu=m, delay=d, cmd=c, **{k: number(k, v[i]) for k, v in st.items()}, **extra(i, 0)) for i, (m, d, c) in enumerate(grid)]
     st = ev.bucket_statistics()
     if gait:
         st.update(ev.bucket_gait_statistics(mass, g))
-    return [dict(mu=m, delay=d, cmd=c, level=l + 1, cmd_level=(l + 1) / levels * c, **{k: number(k, v[2 * l + 1, i]) for k, v in st.items()})
+    return [dict(mu=m, delay=d, cmd=c, level=l + 1, cmd_level=(l + 1) / levels * c, **{k: number(k, v[2 * l + 1, i]) for k, v in st.items()}, **extra(i, l))
             for i, (m, d, c) in enumerate(grid) for l in range(levels)]
 
 
 def perturbation_study(model_or_policy, env_cfg, mus, delays, cmd, explorations, noise, warm_steps=1000, frames=1000, seed=0, record_body=False,
                        persistent=PERSISTENT_DEFAULT, bucket_steps=None, cmd_hz=1.0, vel_hz=None, act_hz=None, clip=True, mu_warm=0.8, device=None, kicks=None,
-                       gait=False, mass=None, g=9.81, ensemble=None, frame_chunk=None, ensemble_survivors=False):
+                       gait=False, mass=None, g=9.81, recurrence=None, recurrence_frames=None, ensemble=None, frame_chunk=None, ensemble_survivors=False):
     """The reference's perturbation exploration (Exp_Raw_Data/Param-*.txt: NoE explorations of FoE control steps from a base state displaced by
     z_noise, roll_noise, pitch_noise and the *_dot_noise amplitudes, per friction and observation delay) in ONE Manual-mode pool of
     len(mus) x len(delays) x explorations envs, env index = (i_mu * len(delays) + i_delay) * explorations + i_exploration, command `cmd` (v_x).
@@ -1204,7 +1495,10 @@ def perturbation_study(model_or_policy, env_cfg, mus, delays, cmd, explorations,
     for bit), each call's recorder is analysed (and copied out with record_body) and released before the next call takes its place, so the
     device memory of the recorder is K, not `frames`, rows.  ensemble_survivors: analyse only the explorations without a post-kick fall (the
     mask is known after the last frame, so the whole recorder is kept: refused together with frame_chunk).
-    ensemble None (the default): the return value is what it was, key for key."""
+    ensemble None (the default): the return value is what it was, key for key.
+    recurrence: a spec (RECURRENCE_SPEC_REFERENCE) -- every row gains `recurrence`, a dict of [E] arrays RR, DET, L, LMAX, LAM, TT, period_s,
+    period_fraction, kept (recurrence_measures / recurrence_period per exploration, irrl_eval_recurrence on the device) over the last
+    recurrence_frames = T post-kick frames (default: min(frames, 800)); it needs the whole run's recorder: refused together with frame_chunk."""
     import torch
     import yaml
     from . import __BLACKPANTHER_V55_RESOURCE_DIRECTORY__ as rsc
@@ -1221,6 +1515,15 @@ def perturbation_study(model_or_policy, env_cfg, mus, delays, cmd, explorations,
             raise ValueError("ensemble_survivors needs the whole run's recorder: it does not go with frame_chunk")
     conditions = [(float(m), int(d)) for m in mus for d in delays]
     E, warm_steps, frames = int(explorations), int(warm_steps), int(frames)
+    if recurrence is not None:
+        recurrence = recurrence_spec(recurrence)
+        if frame_chunk is not None:
+            raise ValueError("recurrence needs the whole run's recorder: it does not go with frame_chunk")
+        T_rec = min(frames, 800) if recurrence_frames is None else int(recurrence_frames)
+        if T_rec < 1 or T_rec > min(frames, RECURRENCE_MAX_FRAMES):
+            raise ValueError("recurrence_frames lies in 1 .. min(frames, %d)" % RECURRENCE_MAX_FRAMES)
+    elif recurrence_frames is not None:
+        raise ValueError("recurrence_frames needs a recurrence spec")
     bucket_steps = frames if bucket_steps is None else int(bucket_steps)
     if not conditions or E < 1 or frames < 1:
         raise ValueError("empty study")
@@ -1249,7 +1552,7 @@ def perturbation_study(model_or_policy, env_cfg, mus, delays, cmd, explorations,
     ev.run(bucket_steps, persistent=persistent)
     if mu_warm is not None:                                    # (the setter's copy is ordered on the pool's stream, behind the warm-up)
         env.SetContactCoefficient(contact_material(mu_rows))
-    want_body = record_body or ensemble is not None
+    want_body = record_body or ensemble is not None or recurrence is not None
     chunk = frames if frame_chunk is None else min(frame_chunk, frames)
     body_parts, ens_parts, rec = [], [], None
     for first in range(0, frames, chunk):
@@ -1268,6 +1571,12 @@ def perturbation_study(model_or_policy, env_cfg, mus, delays, cmd, explorations,
             up = torch.from_numpy((st["falls"][1:].sum(0) == 0).astype(np.uint8)).to(ev.dev)
             ens_parts.append(ensemble_to_numpy(ensemble_device(rec["body"], len(conditions), ensemble, mask=up)))
         ens = {k: (None if ens_parts[0][k] is None else np.concatenate([p[k] for p in ens_parts], 1)) for k in ens_parts[0]}
+    rqa = None
+    if recurrence is not None:                                 # (one chunk: rec is the whole run's recorder)
+        res = recurrence_to_numpy(recurrence_device(rec["body"], recurrence, frame_first=frames - T_rec, frames=T_rec, lags=T_rec // 2 + 1))
+        rqa = recurrence_measures(res["counts"], T_rec, recurrence)
+        per = recurrence_period(res["lag"], T_rec, max(recurrence["theiler"], 1), ev._dt)
+        rqa.update(period_s=per["period_s"], period_fraction=per["period_fraction"], kept=res["counts"][:, 0].astype(np.int64))
     rec = None
     out = []
     for i, (m, d) in enumerate(conditions):
@@ -1281,21 +1590,26 @@ def perturbation_study(model_or_policy, env_cfg, mus, delays, cmd, explorations,
             row["gait"] = {k: v[:, sl] for k, v in gt.items()}
         if ens is not None:
             row["ensemble"] = ensemble_row(ens, i, ev._dt)
+        if rqa is not None:
+            row["recurrence"] = {k: v[sl] for k, v in rqa.items()}
         out.append(row)
     return out
 
 
-def perturbation_table(rows, gait=False, ensemble=False):
+def perturbation_table(rows, gait=False, ensemble=False, recurrence=False):
     """one line per (mu, delay) of a perturbation_study: the surviving fraction, and the ensemble mean of v_x / z / pitch of the survivors in the
     bucket in front of the kick and in the last one; gait (rows of a study with gait=True): the cost of transport and the mean duty factor too;
     ensemble (rows of a study with an ensemble spec): the entropy of the first and of the last frame, its decay rate kappa (nats/s) and the
-    time at which it reaches its floor (entropy_rate; NaN for fewer than 3 frames)"""
+    time at which it reaches its floor (entropy_rate; NaN for fewer than 3 frames); recurrence (rows of a study with a recurrence spec): the
+    medians over the survivors of RR, DET, LMAX and period_s"""
     out = ["%-6s %-5s %-5s %-5s %-9s " % ("mu", "delay", "cmd", "E", "surviving") + " ".join("%-12s" % k for k in ("vx_before", "vx_last", "z_before", "z_last",
                                                                                                               "pitch_before", "pitch_last"))]
     if gait:
         out[0] += " " + " ".join("%-12s" % k for k in ("cot_before", "cot_last", "duty_before", "duty_last"))
     if ensemble:
         out[0] += " " + " ".join("%-12s" % k for k in ("H0", "H_last", "kappa", "t_floor"))
+    if recurrence:
+        out[0] += " " + " ".join("%-12s" % k for k in RECURRENCE_TABLE_KEYS)
     for r in rows:
         up = r["falls"] == 0
         m = lambda k, b: float(r["stats"][k][b, up].mean()) if up.any() else float("nan")
@@ -1308,12 +1622,19 @@ def perturbation_table(rows, gait=False, ensemble=False):
             e = r["ensemble"]
             fit = entropy_rate(e["t"], e["entropy"], stride=max(1, len(e["t"]) // 500)) if len(e["t"]) >= 3 else dict(kappa=float("nan"), t_floor=float("nan"))
             out[-1] += " " + " ".join("%+12.4f" % v for v in (e["entropy"][0], e["entropy"][-1], fit["kappa"], fit["t_floor"]))
+        if recurrence:
+            med = lambda v: float(np.nanmedian(v[up])) if up.any() and np.any(np.isfinite(v[up])) else float("nan")
+            out[-1] += " " + " ".join("%+12.4f" % med(r["recurrence"][k]) for k in RECURRENCE_TABLE_KEYS)
     return "\n".join(out)
 
 
-def sweep_table(rows, gait=False):
+RECURRENCE_TABLE_KEYS = ("RR", "DET", "LMAX", "period_s")
+
+
+def sweep_table(rows, gait=False, recurrence=False):
     """one line per row of a robustness_sweep; gait (rows of a sweep with gait=True): the cost of transport, the mean mechanical power, the four
-    duty factors, the stride frequency (mean over the legs) and the flight fraction too"""
+    duty factors, the stride frequency (mean over the legs) and the flight fraction too; recurrence (rows of a sweep with a recurrence spec): the
+    recurrence rate, the determinism, the longest diagonal line and the stride period too"""
     keys = ("vx_body_mean", "vx_body_std", "z_mean", "z_std", "roll_std", "pitch_mean", "pitch_std", "yaw_rate_mean")
     staircase = bool(rows) and "level" in rows[0]              # one row per (condition, level): the level and its commanded v_x as well
     lead = ("mu", "delay", "cmd") + (("level", "cmd_level") if staircase else ()) + ("falls",)
@@ -1321,10 +1642,14 @@ def sweep_table(rows, gait=False):
     gkeys = ("cot", "power_mean", "duty0", "duty1", "duty2", "duty3", "stride_hz", "flight")
     if gait:
         out[0] += " " + " ".join("%-12s" % k for k in gkeys)
+    if recurrence:
+        out[0] += " " + " ".join("%-12s" % k for k in RECURRENCE_TABLE_KEYS)
     for r in rows:
         lvl = "%-5d %-9g " % (r["level"], r["cmd_level"]) if staircase else ""
         out.append("%-6g %-5d %-5g %s%-5d " % (r["mu"], r["delay"], r["cmd"], lvl, r["falls"]) + " ".join("%+12.4f" % r[k] for k in keys))
         if gait:
             g = dict(r, stride_hz=float(np.mean([r["stride_hz%d" % l] for l in range(4)])))
             out[-1] += " " + " ".join("%+12.4f" % g[k] for k in gkeys)
+        if recurrence:
+            out[-1] += " " + " ".join("%+12.4f" % r["recurrence"][k] for k in RECURRENCE_TABLE_KEYS)
     return "\n".join(out)

@@ -638,6 +638,49 @@ int irrl_eval_ensemble(const float *rec_body, int rows, int num_envs, int condit
                        const uint8_t *mask, const irrl_eval_ensemble_spec *spec, double *entropy, uint32_t *counts, uint32_t *hist, double *moments,
                        void *hip_stream);
 
+/* RECURRENCE ANALYSIS OF A BODY RECORDER: per robot the time x time matrix of quantised state distances and the recurrence measures read off it
+ * -- the reference's recurrence plot (Data_Visualization_Code/Figure4.py:479-570, the rule at :495-509) and, from the same distance evaluations,
+ * recurrence rate, determinism, laminarity, the longest line and the recurrence count per time lag (whose first peak is the stride period).
+ * rec_body as for irrl_eval_ensemble, device f32 [rows, num_envs, 13].  Semantics in ONE text, csrc/eval_elements.hpp:
+ *   frame i = 0 .. frames - 1 (T = frames) of robot e is recorder row frame_first + i * frame_every;
+ *   x_i = irrl_eval_ensemble_features(row), unchanged; a frame is KEPT iff its six features are finite;
+ *   u_i[k] = (x_i[k] - (lb[k] + ub[k]) / 2.0) / (ub[k] - lb[k])                                (irrl_eval_recurrence_state)
+ *   d2 = sum_k D_k * D_k in index order, D_k = u_i[k] - u_j[k], every product rounded on its own  (irrl_eval_recurrence_dist2)
+ *   c = sqrt(d2) / eps,  q_ij = c >= steps ? steps : (int)floor(c)                             (irrl_eval_recurrence_level)
+ *   a pair with a dropped frame has q = steps;  R_ij = q_ij < radius;  w = max(theiler, 1),  R'_ij = R_ij && |i - j| >= w.
+ * Outputs per robot, all integers (any order of the reductions gives the same words):
+ *   counts[e, 9] u32:  0 KEPT         kept frames
+ *                      1 REC          pairs i < j, j - i >= w, with R_ij
+ *                      2 DIAG_POINTS  those of REC on diagonal lines of length >= lmin; a diagonal line is a maximal run of consecutive i with
+ *                                     R_{i,i+tau} for a fixed tau >= w, the matrix border ends a line like a non-recurrent point
+ *                      3 DIAG_LINES   the number of such lines
+ *                      4 DIAG_MAX     the longest diagonal line of any length, 0 if none
+ *                      5 VERT_POINTS  points of R' on vertical lines of length >= vmin; a vertical line is a run over consecutive i for a fixed
+ *                                     j in the FULL matrix with the band |i - j| < w removed
+ *                      6 VERT_LINES   7 VERT_MAX
+ *                      8 REC_FULL     points of R' over the full matrix (= 2 REC)
+ *   lag[e, l] u32, l = 0 .. lags - 1 (lags <= frames; NULL or lags = 0: off) = the number of i with i + l < T and R_{i,i+l}; independent of
+ *                      theiler; lag[e, 0] = KEPT
+ *   matrix[s, i, j] u8 [matrix_count, T, T] (NULL or matrix_count = 0: off) = q_ij of robot matrix_env[s], the full symmetric matrix, the
+ *                      diagonal 0 for kept frames and `steps` for dropped ones; a robot may be listed more than once.
+ * One workgroup per robot, no global atomics, no floating-point atomics, every output word has one writer.  Stateless and stream-ordered, no env
+ * handle.  frames == 0 is accepted and does nothing.
+ * Refused before any HIP call, with "irrl_eval_recurrence: " in front of the text: a NULL rec_body, spec or counts; num_envs < 1; frames outside
+ * 0 .. IRRL_EVAL_RECURRENCE_MAX_FRAMES; frame_first < 0, frame_every < 1, frame_first + (frames - 1) * frame_every >= rows; ub_k <= lb_k or a
+ * bound that is not finite; eps <= 0 or not finite; steps outside 1 .. 255; radius outside 1 .. steps; theiler < 0, lmin < 1, vmin < 1; lags
+ * outside 0 .. frames; lags > 0 with a NULL lag; matrix_count outside 0 .. IRRL_EVAL_RECURRENCE_MAX_MATRICES; matrix_count > 0 with a NULL
+ * matrix; a matrix_env outside 0 .. num_envs - 1. */
+#define IRRL_EVAL_RECURRENCE_MAX_FRAMES 2048
+#define IRRL_EVAL_RECURRENCE_MAX_MATRICES 8
+#define IRRL_EVAL_RECURRENCE_COUNTS 9
+typedef struct irrl_eval_recurrence_spec {
+  double lb[6], ub[6]; double eps;
+  int steps, radius, theiler, lmin, vmin, lags, matrix_count;
+  int matrix_env[8];
+} irrl_eval_recurrence_spec;
+int irrl_eval_recurrence(const float *rec_body, int rows, int num_envs, int frame_first, int frame_every, int frames,
+                         const irrl_eval_recurrence_spec *spec, uint32_t *counts, uint32_t *lag, uint8_t *matrix, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

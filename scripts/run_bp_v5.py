@@ -14,6 +14,9 @@ reference's own (run_bp_v5.py:8-13), resolved by the compat packages at the repo
         --perturb z=0.02,roll=0.25,pitch=0.25,z_dot=1,roll_dot=1,pitch_dot=1 --explorations 10000 --perturb_at 1000 --steps 1000 \
         --out explorations.npz                                                             # perturbation exploration, device-resident
     ... --perturb ... --entropy [--entropy_chunk 100]                                      # + entropy, cells, histograms per frame (Figure3/4.py)
+    python scripts/run_bp_v5.py --test --sweep --model data/..._final.pkl --sweep_cmd 5 --recurrence [--recurrence_frames 800 --recurrence_radius 10] \
+        --out sweep.json                                                                   # + recurrence rate, determinism, longest line and stride
+                                                                                           # period per condition; the matrices of the first 8 to --out
     python scripts/run_bp_v5.py --test --sweep --step --gait --model data/..._final.pkl --persistent on   # cost of transport, duty factors and
                                                                                            # touchdown rate per (friction, command level)
 
@@ -109,7 +112,23 @@ def parse_args(argv):
                         "occupied cells, per-feature histograms, mean and standard deviation); the table gains H0, H_last, kappa and t_floor, --out the arrays")
     p.add_argument("--entropy_chunk", type=int, default=None,
                    help="--entropy: run the post-kick frames in calls of at most this many steps, so that the body recorder on the device holds that many rows")
+    p.add_argument("--recurrence", dest="flag_recurrence", action="store_true", default=False,
+                   help="--sweep: the reference's recurrence plot in numbers, per robot on the device (evaluate.RECURRENCE_SPEC_REFERENCE): the table gains "
+                        "RR, DET, LMAX and period_s (--perturb: their medians over the survivors); --out also gets the level matrices of the first 8 conditions")
+    p.add_argument("--recurrence_frames", type=int, default=None, help="--recurrence: the last so many frames of the run are analysed (default: min(steps, 800))")
+    p.add_argument("--recurrence_radius", type=int, default=None, help="--recurrence: the recurrence radius in levels of 0.001 (default 10)")
     return p.parse_args(argv)
+
+
+def recurrence_keywords(args):
+    """--recurrence [--recurrence_frames T --recurrence_radius r] -> the keywords of robustness_sweep / perturbation_study"""
+    from high_speed_quadrupedal_locomotion_by_irrl_amd.evaluate import RECURRENCE_SPEC_REFERENCE
+    if not args.flag_recurrence:
+        return {}
+    spec = dict(RECURRENCE_SPEC_REFERENCE)
+    if args.recurrence_radius is not None:
+        spec["radius"] = args.recurrence_radius
+    return dict(recurrence=spec, recurrence_frames=args.recurrence_frames)
 
 
 def run_test(args, cfg):
@@ -197,11 +216,11 @@ def run_sweep(args, cfg):
                             cmd_hz=args.cmd_filter_freq, vel_hz=none_if_off(args.vel_filter_freq), act_hz=none_if_off(args.act_filter_freq),
                             persistent=PERSISTENT_DEFAULT if args.persistent is None else args.persistent,
                             levels=4 if args.flag_step else None, level_steps=args.step_steps if args.flag_step else None,
-                            heading=heading_hold(n) if args.flag_dir_fd else None, **gait)
-    print(sweep_table(rows, gait=True) if args.flag_gait else sweep_table(rows))
+                            heading=heading_hold(n) if args.flag_dir_fd else None, **gait, **recurrence_keywords(args))
+    print(sweep_table(rows, gait=args.flag_gait, recurrence=args.flag_recurrence))
     if args.out:
-        with open(args.out, "w") as f:
-            json.dump(rows, f, indent=1)
+        with open(args.out, "w") as f:                                 # (--recurrence: the level matrices of the first 8 conditions as nested lists)
+            json.dump([{k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in r.items()} for r in rows], f, indent=1)
         print("table written to", args.out)
     return rows
 
@@ -220,8 +239,8 @@ def run_perturb(args, cfg):
                               warm_steps=args.perturb_at, frames=args.steps, seed=args.perturb_seed, bucket_steps=bucket, cmd_hz=args.cmd_filter_freq,
                               vel_hz=none_if_off(args.vel_filter_freq), act_hz=none_if_off(args.act_filter_freq),
                               persistent=PERSISTENT_DEFAULT if args.persistent is None else args.persistent,
-                              **(dict(gait=True, mass=args.gait_mass, g=args.gait_g) if args.flag_gait else {}), **entropy)
-    print(perturbation_table(rows, gait=args.flag_gait, ensemble=args.flag_entropy))
+                              **(dict(gait=True, mass=args.gait_mass, g=args.gait_g) if args.flag_gait else {}), **entropy, **recurrence_keywords(args))
+    print(perturbation_table(rows, gait=args.flag_gait, ensemble=args.flag_entropy, recurrence=args.flag_recurrence))
     if args.out:
         out = dict(mu=np.array([r["mu"] for r in rows]), delay=np.array([r["delay"] for r in rows]), cmd=np.array([r["cmd"] for r in rows]),
                    surviving=np.array([r["surviving"] for r in rows]), falls=np.stack([r["falls"] for r in rows]), kicks=np.stack([r["kicks"] for r in rows]))
@@ -232,6 +251,8 @@ def run_perturb(args, cfg):
         for k in (rows[0]["ensemble"] if args.flag_entropy else ()):
             if rows[0]["ensemble"][k] is not None:
                 out["ensemble_" + k] = np.stack([r["ensemble"][k] for r in rows])  # [condition, frame, ...]
+        for k in (rows[0]["recurrence"] if args.flag_recurrence else ()):
+            out["recurrence_" + k] = np.stack([r["recurrence"][k] for r in rows])  # [condition, exploration]
         np.savez_compressed(args.out, **out)
         print("kicks and statistics written to", args.out)
     return rows

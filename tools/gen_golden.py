@@ -320,9 +320,32 @@ def gen_checkpoint():
     print("wrote bp5_155_checkpoint.npz", len(params), "arrays")
 
 
+def gen_recurrence_windows():
+    """tests/golden/raisim_recurrence_windows.npz: frames 2000 .. 2799 of the four RaiSim recordings behind the reference's recurrence plot
+    (Exp_Raw_Data/body-center-<date>.bin, the windows of Data_Visualization_Code/Figure4.py:483-499), decoded as raisim_body_logs.json says
+    (one segment of seg_len = 10000 frames stored as [13, 10000] float32 -> rows of 13), float32 [4, 800, 13], with their names and the
+    friction, observation delay and command of their Param-<date>.txt.  Data only."""
+    import yaml
+    src = os.path.join(os.path.dirname(os.path.dirname(REF)), "Exp_Raw_Data")
+    dates = ["2021-07-23-09-19-38", "2021-07-23-09-19-15", "2021-07-23-09-23-35", "2021-07-23-09-23-05"]
+    first, last = 2000, 2800
+    body, mu, delay, cmd = [], [], [], []
+    for d in dates:
+        cfg = yaml.safe_load(open(os.path.join(src, "Param-%s.txt" % d)))
+        raw = np.fromfile(os.path.join(src, "body-center-%s.bin" % d), dtype=np.float32)
+        assert int(cfg["seg_len"]) == 10000 and raw.size == 13 * 10000 and int(cfg["NoE"]) == 1 and int(cfg["Num_Of_Env"]) == 1, d
+        body.append(np.ascontiguousarray(raw.reshape(13, 10000).T[first:last]))
+        mu.append(float(cfg["Mu_Min"])); delay.append(int(cfg["delay"])); cmd.append(float(cfg["V_Min"]))
+    np.savez_compressed(os.path.join(OUT, "raisim_recurrence_windows.npz"), body=np.stack(body).astype(np.float32), names=np.array(dates),
+                        mu=np.array(mu), delay=np.array(delay, np.int64), cmd=np.array(cmd), first_frame=np.int64(first), frame_dt=np.float64(0.002))
+    print("wrote raisim_recurrence_windows.npz", np.stack(body).shape, mu, delay, cmd)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["task", "lstm", "lstm_syn", "ppo", "actor", "ckpt"]
+    which = sys.argv[1:] or ["task", "lstm", "lstm_syn", "ppo", "actor", "ckpt", "recurrence"]
+    if "recurrence" in which:
+        gen_recurrence_windows()
     if "ckpt" in which:
         gen_checkpoint()
     if "actor" in which:
