@@ -129,6 +129,12 @@ SIGNATURES = {
     # the recurrence analysis of a body recorder: rec_body, rows, num_envs, frame_first, frame_every, frames |
     # `const irrl_eval_recurrence_spec *` (EvalRecurrenceSpec below) | counts, lag, matrix | stream
     "irrl_eval_recurrence": (C.c_int, [vp] + [C.c_int] * 5 + [vp] + [vp] * 3 + [vp]),
+    # the footfall analysis of a gait recorder: rec_gait, rec_done | rows, num_envs, frame_first, frame_every, frames |
+    # `const irrl_eval_footfall_spec *` (EvalFootfallSpec below) | counts, support, phase, pattern | stream
+    "irrl_eval_footfall": (C.c_int, [vp, vp] + [C.c_int] * 5 + [vp] + [vp] * 4 + [vp]),
+    # the motor plane of a gait recorder: rec_gait, rec_done | rows, num_envs, conditions, robots, frame_first, frame_every, frames |
+    # `const irrl_eval_motor_spec *` (EvalMotorSpec below) | counts, hist, fold | stream
+    "irrl_eval_motor_plane": (C.c_int, [vp, vp] + [C.c_int] * 7 + [vp] + [vp] * 3 + [vp]),
 }
 
 
@@ -162,6 +168,18 @@ class EvalRecurrenceSpec(C.Structure):
     matrices are wanted); C.byref(...)"""
     _fields_ = [("lb", C.c_double * 6), ("ub", C.c_double * 6), ("eps", C.c_double), ("steps", C.c_int), ("radius", C.c_int), ("theiler", C.c_int),
                 ("lmin", C.c_int), ("vmin", C.c_int), ("lags", C.c_int), ("matrix_count", C.c_int), ("matrix_env", C.c_int * 8)]
+
+
+class EvalFootfallSpec(C.Structure):
+    """struct irrl_eval_footfall_spec of include/irrl_env.h (a HOST struct: the dilation's reach and the hold in frames, the phase bins)"""
+    _fields_ = [("reach", C.c_int), ("hold", C.c_int), ("phase_bins", C.c_int)]
+
+
+class EvalMotorSpec(C.Structure):
+    """struct irrl_eval_motor_spec of include/irrl_env.h (a HOST struct: the motor envelope, the knee's gear ratio, the saturation band, the
+    histogram's ranges and bins, the fold's period in frames)"""
+    _fields_ = [(k, C.c_double) for k in ("tau_max", "w_crit", "w_max", "knee_ratio", "sat", "t_lo", "t_hi", "w_lo", "w_hi")] + \
+               [(k, C.c_int) for k in ("t_bins", "w_bins", "period")]
 
 
 def load():

@@ -101,6 +101,11 @@ ENV_FLAGS_W2 = ["-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=iterativ
 EVAL_UNIT_FLAGS = ["-DIRRL_LANES_PER_ROBOT=16", "-DIRRL_EVAL_UNIT"]
 
 
+# the translation units that go through the plain compiler driver, in link order behind the env objects: the C-ABI + LSTM kernels and one unit
+# per analysis of a recorder.  build() and tools/build_variants.py both take them from here (the C-ABI unit references every launcher).
+PLAIN_UNITS = ["irrl_env_abi.hip", "eval_ensemble.hip", "eval_recurrence.hip", "eval_footfall.hip"]
+
+
 def llvm_bin():
     for cand in (os.environ.get("ROCM_LLVM_BIN"), "/opt/rocm/lib/llvm/bin"):
         if cand and os.path.exists(os.path.join(cand, "clang")):
@@ -185,15 +190,13 @@ def build(force=False, verbose=False, extra_flags=()):
     # the env kernels in both lane layouts (same source, different lane-primitive header; the 4-lane layout once more for two waves per
     # SIMD; the 16-lane layout once more for the run-time-solver twins of the rollout kernels alone, and once more for the persistent evaluation
     # kernel alone) through the ISA pass, then the C-ABI +
-    # LSTM kernels, the ensemble analysis and the recurrence analysis (a translation unit each) through the plain driver
+    # LSTM kernels and the analyses of the recorders (PLAIN_UNITS, a translation unit each) through the plain driver
     units = [("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=16"] + ENV_FLAGS, "env_kernels_l16.o"),
              ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=16", "-DIRRL_ROLLOUT_RT_UNIT"] + ENV_FLAGS, "env_kernels_l16rt.o"),
              ("env_kernels.hip", EVAL_UNIT_FLAGS + ENV_FLAGS, "env_kernels_l16ev.o"),
              ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=4"] + ENV_FLAGS, "env_kernels_l4.o"),
-             ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=4", "-DIRRL_L4_WAVES2"] + ENV_FLAGS_W2, "env_kernels_l4w2.o"),
-             ("irrl_env_abi.hip", ['-DIRRL_SRC_HASH="%s"' % want], "irrl_env_abi.o"),
-             ("eval_ensemble.hip", [], "eval_ensemble.o"),
-             ("eval_recurrence.hip", [], "eval_recurrence.o")]
+             ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=4", "-DIRRL_L4_WAVES2"] + ENV_FLAGS_W2, "env_kernels_l4w2.o")]
+    units += [(src, ['-DIRRL_SRC_HASH="%s"' % want] if src == "irrl_env_abi.hip" else [], os.path.splitext(src)[0] + ".o") for src in PLAIN_UNITS]
     from concurrent.futures import ThreadPoolExecutor
     def one(u):
         src, flags, obj = u

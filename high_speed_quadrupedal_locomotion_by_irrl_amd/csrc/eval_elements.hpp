@@ -422,3 +422,94 @@ static inline const char *irrl_eval_recurrence_spec_error(const irrl_eval_recurr
   if (s.matrix_count < 0 || s.matrix_count > IRRL_EVAL_RECURRENCE_MAX_MATRICES) return "matrix_count lies in 0 .. 8";
   return NULL;
 }
+
+// ---- the footfall analysis of a gait recorder: contact flag, dilation, hold, phase bin (irrl_eval_footfall, include/irrl_env.h) ----
+// the raw contact flag of one recorder word (column 24 + leg of a rec_gait row): anything but zero, a NaN included
+static inline IRRL_EVAL_FN bool irrl_eval_footfall_flag(float word) { return word != 0.0f; }
+// THE FILTER RULE in its sequential, normative form: c[T] raw flags (0 / 1) of one leg over the robot's window -> f[T].
+//   dilate: d[k] = any c[k'] with |k' - k| <= reach, 0 <= k' < T
+//   hold:   f = d; in increasing j = 0 .. T - hold - 2: if f[j] && !f[j+1], f[j+1] = any of f[j+1 .. j+hold]
+// reach = 2, hold = 10: Data_Visualization_Code/Figure2.py:97-116 for every T >= 5.
+static inline IRRL_EVAL_FN void irrl_eval_footfall_filter(const uint8_t *c, int T, int reach, int hold, uint8_t *f) {
+  for (int k = 0; k < T; k++) {
+    const int k0 = k - reach < 0 ? 0 : k - reach;
+    const int k1 = k + reach > T - 1 ? T - 1 : k + reach;
+    uint8_t d = 0;
+    for (int i = k0; i <= k1; i++)
+      if (c[i] != 0) d = 1;
+    f[k] = d;
+  }
+  for (int j = 0; j <= T - hold - 2; j++) {
+    if (f[j] == 0 || f[j + 1] != 0) continue;
+    uint8_t any = 0;
+    for (int i = j + 1; i <= j + hold; i++)
+      if (f[i] != 0) any = 1;
+    f[j + 1] = any;
+  }
+}
+// THE CLOSED FORM of the hold for one gap of d: a = the last frame in front of the gap with d (-1: none), b = the first frame behind it with d
+// (>= T: none).  -> the frames a < k < end are filled, the frames end <= k < b are not: f[k] = k <= T - hold - 1 && b - a <= hold for the frames
+// of the gap, so a gap of at most hold - 1 frames is filled up to the window's last `hold` frames, and a leading or trailing gap never.
+static inline IRRL_EVAL_FN int irrl_eval_footfall_fill_end(int T, int hold, int a, int b) {
+  if (a < 0 || b >= T || b - a > hold) return a + 1;
+  const int last = T - hold;                               // the first frame the rule no longer reaches
+  const int end = b < last ? b : last;
+  return end > a + 1 ? end : a + 1;
+}
+// the phase bin of a touchdown at frame t inside the stride [a, b) of leg 0 (a <= t < b): (t - a) * bins / (b - a), integer division
+static inline IRRL_EVAL_FN int irrl_eval_footfall_phase_bin(int t, int a, int b, int bins) { return (t - a) * bins / (b - a); }
+// what is wrong with a spec, or NULL
+static inline const char *irrl_eval_footfall_spec_error(const irrl_eval_footfall_spec &s) {
+  if (s.reach < 0 || s.reach > IRRL_EVAL_FOOTFALL_MAX_REACH) return "reach lies in 0 .. 8";
+  if (s.hold < 0 || s.hold > IRRL_EVAL_FOOTFALL_MAX_HOLD) return "hold lies in 0 .. 64";
+  if (s.phase_bins < 0 || s.phase_bins > IRRL_EVAL_FOOTFALL_MAX_BINS) return "phase_bins lies in 0 .. 64";
+  return NULL;
+}
+
+// ---- the motor plane of a gait recorder: sample, envelope, classes (irrl_eval_motor_plane, include/irrl_env.h) ----
+// One recorder pair (joint torque, joint rate) of joint j -> motor-side torque m and speed w; -> false (sample dropped) unless both are finite
+static inline IRRL_EVAL_FN bool irrl_eval_motor_sample(float tq, float qd, int j, double knee_ratio, double *m, double *w) {
+  const double ratio = (j % 3 == 2) ? knee_ratio : 1.0;
+  *m = (double)tq / ratio;
+  *w = (double)qd * ratio;
+  return irrl_eval_ensemble_finite(*m) && irrl_eval_ensemble_finite(*w);
+}
+// The upper envelope at motor speed w, the f64 restatement of the env's torque clamp (csrc/env_core.hpp torque_clamp1): tau_max up to w_crit,
+// from there a straight line through zero at w_max.  Every product a statement of its own.  low(w) = -up(-w).
+static inline IRRL_EVAL_FN double irrl_eval_motor_up(double w, const irrl_eval_motor_spec &s) {
+  if (!(w > s.w_crit)) return s.tau_max;
+  const double span = s.w_max - s.w_crit;
+  const double slope = s.tau_max / span;
+  const double over = w - s.w_crit;
+  const double drop = over * slope;
+  return s.tau_max - drop;
+}
+static inline IRRL_EVAL_FN double irrl_eval_motor_low(double w, const irrl_eval_motor_spec &s) { return -irrl_eval_motor_up(-w, s); }
+// the classes of one kept sample as bits: 1 SAT_UP, 2 SAT_LOW, 4 OUTSIDE, 8 MOTORING, 16 BRAKING (bit k = counter k + 1)
+static inline IRRL_EVAL_FN unsigned irrl_eval_motor_classes(double m, double w, const irrl_eval_motor_spec &s) {
+  const double up = irrl_eval_motor_up(w, s), low = irrl_eval_motor_low(w, s);
+  const double up_in = up - s.sat, up_out = up + s.sat;
+  const double low_in = low + s.sat, low_out = low - s.sat;
+  const double power = m * w;
+  unsigned bits = 0u;
+  if (m >= up_in) bits |= 1u;
+  if (m <= low_in) bits |= 2u;
+  if (m > up_out || m < low_out) bits |= 4u;
+  if (power > 0.0) bits |= 8u;
+  if (power < 0.0) bits |= 16u;
+  return bits;
+}
+// what is wrong with a spec, or NULL
+static inline const char *irrl_eval_motor_spec_error(const irrl_eval_motor_spec &s) {
+  if (!irrl_eval_ensemble_finite(s.tau_max) || !(s.tau_max > 0.0)) return "tau_max > 0, finite";
+  if (!irrl_eval_ensemble_finite(s.w_crit) || !irrl_eval_ensemble_finite(s.w_max) || !(s.w_max > s.w_crit)) return "w_crit < w_max, both finite";
+  if (!irrl_eval_ensemble_finite(s.knee_ratio) || !(s.knee_ratio > 0.0)) return "knee_ratio > 0, finite";
+  if (!irrl_eval_ensemble_finite(s.sat) || !(s.sat >= 0.0)) return "sat >= 0, finite";
+  if (s.t_bins < 0 || s.t_bins > IRRL_EVAL_MOTOR_MAX_BINS || s.w_bins < 0 || s.w_bins > IRRL_EVAL_MOTOR_MAX_BINS) return "t_bins, w_bins lie in 0 .. 64";
+  if (s.period < 0 || s.period > IRRL_EVAL_MOTOR_MAX_PERIOD) return "period lies in 0 .. 1024";
+  if (s.t_bins > 0 && s.w_bins > 0) {
+    if (!irrl_eval_ensemble_finite(s.t_lo) || !irrl_eval_ensemble_finite(s.t_hi) || !(s.t_hi > s.t_lo)) return "t_lo < t_hi, both finite";
+    if (!irrl_eval_ensemble_finite(s.w_lo) || !irrl_eval_ensemble_finite(s.w_hi) || !(s.w_hi > s.w_lo)) return "w_lo < w_hi, both finite";
+  }
+  return NULL;
+}

@@ -23,6 +23,7 @@
 #include "eval_rollout.hpp"   // the evaluation loop's kernels (irrl_lstm_eval_rollout below)
 #include "eval_ensemble.hpp"  // the ensemble analysis: argument block and launcher of csrc/eval_ensemble.hip (irrl_eval_ensemble below)
 #include "eval_recurrence.hpp"  // the recurrence analysis: argument block and launcher of csrc/eval_recurrence.hip (irrl_eval_recurrence below)
+#include "eval_footfall.hpp"    // the gait recorder's analyses: argument blocks and launchers of csrc/eval_footfall.hip
 
 #include <cmath>
 #include <string>
@@ -1381,6 +1382,50 @@ int irrl_eval_recurrence(const float *rec_body, int rows, int num_envs, int fram
   a.threshold = irrl_eval_recurrence_threshold(spec->eps, spec->steps, spec->radius);
   a.counts = counts; a.lag = spec->lags > 0 ? lag : nullptr; a.matrix = spec->matrix_count > 0 ? matrix : nullptr;
   HIP_TRY(irrl_eval_recurrence_launch(a, (hipStream_t)hip_stream));
+  return 0;
+}
+
+// ---- analyses of a gait recorder (kernels and launchers: csrc/eval_footfall.hip; per-sample rules: csrc/eval_elements.hpp) ----
+// what is wrong with the frame window of either call, or NULL (the three conditions of irrl_eval_recurrence)
+static const char *gait_window_error(int rows, int num_envs, int frame_first, int frame_every, int frames, int max_frames) {
+  if (num_envs < 1) return "num_envs >= 1";
+  if (frames < 0 || frames > max_frames) return "frames lies in 0 .. 16384";
+  if (frame_first < 0 || frame_every < 1) return "frame_first >= 0, frame_every >= 1";
+  if (frames > 0 && irrl_eval_recurrence_row(frame_first, frame_every, frames - 1) >= (long long)rows)
+    return "frame_first + (frames - 1) * frame_every reaches past the recorder's rows";
+  return nullptr;
+}
+
+int irrl_eval_footfall(const float *rec_gait, const uint8_t *rec_done, int rows, int num_envs, int frame_first, int frame_every, int frames,
+                       const irrl_eval_footfall_spec *spec, uint32_t *counts, uint32_t *support, uint32_t *phase, uint8_t *pattern, void *hip_stream) {
+  const std::string w = "irrl_eval_footfall: ";
+  if (!rec_gait || !spec || !counts) { g_err = w + "NULL rec_gait, spec or counts"; return 1; }
+  if (const char *bad = gait_window_error(rows, num_envs, frame_first, frame_every, frames, IRRL_EVAL_FOOTFALL_MAX_FRAMES)) { g_err = w + bad; return 1; }
+  if (const char *bad = irrl_eval_footfall_spec_error(*spec)) { g_err = w + "spec: " + bad; return 1; }
+  if (frames == 0) return 0;
+  FootfallArgs a;
+  a.rec_gait = rec_gait; a.rec_done = rec_done; a.N = num_envs; a.T = frames; a.frame_first = frame_first; a.frame_every = frame_every; a.spec = *spec;
+  a.counts = counts; a.support = support; a.phase = spec->phase_bins > 0 ? phase : nullptr; a.pattern = pattern;
+  HIP_TRY(irrl_eval_footfall_launch(a, (hipStream_t)hip_stream));
+  return 0;
+}
+
+int irrl_eval_motor_plane(const float *rec_gait, const uint8_t *rec_done, int rows, int num_envs, int conditions, int robots, int frame_first,
+                          int frame_every, int frames, const irrl_eval_motor_spec *spec, uint32_t *counts, uint32_t *hist, double *fold,
+                          void *hip_stream) {
+  const std::string w = "irrl_eval_motor_plane: ";
+  if (!rec_gait || !spec || !counts) { g_err = w + "NULL rec_gait, spec or counts"; return 1; }
+  if (const char *bad = gait_window_error(rows, num_envs, frame_first, frame_every, frames, IRRL_EVAL_MOTOR_MAX_FRAMES)) { g_err = w + bad; return 1; }
+  if (conditions < 1 || robots < 1 || (long long)conditions * (long long)robots != (long long)num_envs) {
+    g_err = w + "conditions >= 1, robots >= 1, conditions * robots == num_envs"; return 1;
+  }
+  if (const char *bad = irrl_eval_motor_spec_error(*spec)) { g_err = w + "spec: " + bad; return 1; }
+  if (frames == 0) return 0;
+  MotorPlaneArgs a;
+  a.rec_gait = rec_gait; a.rec_done = rec_done; a.N = num_envs; a.C = conditions; a.R = robots; a.T = frames; a.frame_first = frame_first;
+  a.frame_every = frame_every; a.spec = *spec; a.counts = counts;
+  a.hist = spec->t_bins > 0 && spec->w_bins > 0 ? hist : nullptr; a.fold = spec->period > 0 ? fold : nullptr;
+  HIP_TRY(irrl_eval_motor_plane_launch(a, (hipStream_t)hip_stream));
   return 0;
 }
 

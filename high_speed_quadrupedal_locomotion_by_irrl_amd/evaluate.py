@@ -33,6 +33,10 @@ Gait measurements (set_scenario's gait / measure_gait, run's "gait" recorder; ga
 every env step that does not end in `done`, the joint mechanical power sum_j tq_j qd_j, torque sums, contact flags and ground impulses of the pool
 are added to f64 sums [B, 20, N] in the statistics' buckets (Figure2.py:62-63, :198-222 of the reference: power and cost of transport per command
 level); see gait_from_sums for what comes out.
+
+Analyses of the gait recorder (footfall_numpy / footfall_device / footfall_row, motor_plane_numpy / motor_plane_device / motor_plane_row,
+robustness_sweep's footfall / motor): the reference's debounced contact flags (Figure2.py:97-116) with stride, stance, swing and leg-phase
+statistics, and its motor torque-speed plane (Figure5.py) per condition and joint, on the device; include/irrl_env.h has the rules.
 """
 import ctypes as C
 import math
@@ -381,7 +385,9 @@ def gait_from_sums(sums, stats_sums, mass, control_dt, g=9.81, vx_floor=COT_VX_F
     """gait sums [20, n] (GAIT_SLOTS) and the body statistics' sums [18, n] (STAT_SLOTS) of the same window -> dict of [n] arrays:
     power_mean, power_std (W, p = sum_j tq_j qd_j per control step: Figure2.py:62-63), power_pos, power_neg (mean positive / negative joint work
     rate), cot = power_mean / (mass g mean v_x) (Figure2.py:198-222; NaN where |mean v_x| < vx_floor m/s or no frame was added), duty0 .. duty3
-    (stance frames / frames), stride_hz0 .. stride_hz3 (touchdowns / window seconds, the window being frames * control_dt), flight (fraction of
+    (stance frames / frames), stride_hz0 .. stride_hz3 (touchdowns of the RAW contact flag / window seconds, the window being frames * control_dt:
+    a raw touchdown rate, several times the stride frequency, because the control-rate flag chatters while a foot is down -- the debounced stride
+    frequency is footfall_row's stride_hz<l>, out of irrl_eval_footfall), flight (fraction of
     frames with no leg in contact), grfz_bw (mean of sum_legs lam_w_z / control_dt over mass g; see include/irrl_env.h for the unit), tau2_mean,
     tau2_knee_mean (joint side; the knee motor sits behind a 1.55 reduction, Figure2.py:32-34), peak_tau, peak_qd, peak_grf, gait_frames.
     mass: [n] or a scalar (the reference's figure uses m = 10, g = 9.8)."""
@@ -1104,6 +1110,401 @@ def recurrence_row(counts, lag, T, spec, control_dt):
     return out
 
 
+# ---- the footfall analysis of a gait recorder: debounced contact flags, stride statistics, support patterns, leg phases ----
+# reach, hold: Data_Visualization_Code/Figure2.py:97-116 (Contact_filtered: a 5-frame moving average cast to bool, then every gap shorter than 10
+# frames filled); phase_bins is this build's choice
+FOOTFALL_SPEC_REFERENCE = dict(reach=2, hold=10, phase_bins=16)
+FOOTFALL_MAX_FRAMES = 16384      # IRRL_EVAL_FOOTFALL_MAX_FRAMES
+FOOTFALL_MAX_REACH, FOOTFALL_MAX_HOLD, FOOTFALL_MAX_BINS = 8, 64, 64
+FOOTFALL_NONE = 0xFFFFFFFF       # FIRST_TD / LAST_TD without a touchdown
+FOOTFALL_COUNTS = ("frames", "raw_stance", "raw_touchdowns", "stance", "touchdowns", "liftoffs", "first_td", "last_td", "stance_phases", "stance_sum",
+                   "stance_max", "swing_phases", "swing_sum", "swing_max")
+FOOTFALL_LEGS = ("FR", "FL", "HR", "HL")
+FOOTFALL_PATTERNS = 8            # robustness_sweep: the rows of the first 8 conditions carry `pattern` (and `hist`)
+
+
+def footfall_spec(spec):
+    """a spec mapping (keys of FOOTFALL_SPEC_REFERENCE) -> dict of ints, refused like irrl_eval_footfall refuses its struct"""
+    s = {k: int(spec[k]) for k in ("reach", "hold", "phase_bins")}
+    if s["reach"] < 0 or s["reach"] > FOOTFALL_MAX_REACH:
+        raise ValueError("footfall spec: reach lies in 0 .. %d" % FOOTFALL_MAX_REACH)
+    if s["hold"] < 0 or s["hold"] > FOOTFALL_MAX_HOLD:
+        raise ValueError("footfall spec: hold lies in 0 .. %d" % FOOTFALL_MAX_HOLD)
+    if s["phase_bins"] < 0 or s["phase_bins"] > FOOTFALL_MAX_BINS:
+        raise ValueError("footfall spec: phase_bins lies in 0 .. %d" % FOOTFALL_MAX_BINS)
+    return s
+
+
+def _gait_frames(rows, frame_first, frame_every, frames, most=FOOTFALL_MAX_FRAMES):
+    frame_first, frame_every, frames = _ensemble_frames(rows, frame_first, frame_every, frames)
+    if frames > most:
+        raise ValueError("frames lies in 0 .. %d" % most)
+    return frame_first, frame_every, frames
+
+
+def _gait_window(rec_gait, rec_done, frame_first, frame_every, frames):
+    """-> (the analysed rows of the recorder [T, N, 32], T_e int64 [N]): T_e = the first analysed frame with a non-zero rec_done, T if none"""
+    rec = np.asarray(rec_gait)
+    if rec.ndim != 3 or rec.shape[2] != GAIT_REC_DIM:
+        raise ValueError("rec_gait [rows, N, %d]" % GAIT_REC_DIM)
+    frame_first, frame_every, T = _gait_frames(rec.shape[0], frame_first, frame_every, frames)
+    sel = frame_first + frame_every * np.arange(T)
+    te = np.full(rec.shape[1], T, np.int64)
+    if rec_done is not None:
+        done = np.asarray(rec_done)
+        if done.shape != rec.shape[:2]:
+            raise ValueError("rec_done [rows, N]")
+        dn = done[sel] != 0
+        te = np.where(dn.any(0), dn.argmax(0), T).astype(np.int64)
+    return rec[sel], te
+
+
+def footfall_filter_numpy(c, reach, hold):
+    """THE FILTER RULE, sequential, statement for statement irrl_eval_footfall_filter (csrc/eval_elements.hpp): c [T] raw flags -> f bool [T]"""
+    c = np.asarray(c) != 0
+    T, reach, hold = len(c), int(reach), int(hold)
+    f = np.zeros(T, bool)
+    for k in range(T):
+        k0 = k - reach if k - reach > 0 else 0
+        k1 = k + reach if k + reach < T - 1 else T - 1
+        f[k] = c[k0:k1 + 1].any()
+    for j in range(0, T - hold - 1):
+        if not f[j] or f[j + 1]:
+            continue
+        f[j + 1] = f[j + 1:j + hold + 1].any()
+    return f
+
+
+def footfall_fill_end(T, hold, a, b):
+    """irrl_eval_footfall_fill_end: the gap between a (the last frame with d in front, -1: none) and b (the first behind, >= T: none) is filled
+    for a < k < the value returned"""
+    if a < 0 or b >= T or b - a > hold:
+        return a + 1
+    end = min(b, T - hold)
+    return end if end > a + 1 else a + 1
+
+
+def footfall_filter_closed_numpy(c, reach, hold):
+    """the closed form of the rule, as the kernel applies it: the dilation, then every gap of d through footfall_fill_end"""
+    c = np.asarray(c) != 0
+    T, reach, hold = len(c), int(reach), int(hold)
+    d = np.zeros(T, bool)
+    for s in range(-reach, reach + 1):
+        if s >= 0:
+            d[s:] |= c[:T - s] if s < T else False
+        else:
+            d[:T + s] |= c[-s:] if -s < T else False
+    f = d.copy()
+    on = np.flatnonzero(d)
+    for a, b in zip(on[:-1], on[1:]):
+        if b > a + 1:
+            f[a + 1:footfall_fill_end(T, hold, int(a), int(b))] = True
+    return f
+
+
+def _footfall_leg(c, f, out):
+    """one leg's raw flags c and filtered flags f (bool [T_e]) -> the 14 counters into out; -> the touchdown frames"""
+    T = len(c)
+    td = np.flatnonzero(~f[:-1] & f[1:]) + 1 if T > 1 else np.zeros(0, np.int64)
+    lo = np.flatnonzero(f[:-1] & ~f[1:]) + 1 if T > 1 else np.zeros(0, np.int64)
+    out[0], out[1], out[2] = T, int(c.sum()), int((~c[:-1] & c[1:]).sum()) if T > 1 else 0
+    out[3], out[4], out[5] = int(f.sum()), len(td), len(lo)
+    out[6], out[7] = (int(td[0]), int(td[-1])) if len(td) else (FOOTFALL_NONE, FOOTFALL_NONE)
+    at = np.searchsorted(td, lo) - 1                           # a liftoff's stance began at the last touchdown in front of it
+    stance = (lo - td[np.maximum(at, 0)])[at >= 0] if len(td) else np.zeros(0, np.int64)
+    at = np.searchsorted(lo, td) - 1                           # a touchdown's swing began at the last liftoff in front of it
+    swing = (td - lo[np.maximum(at, 0)])[at >= 0] if len(lo) else np.zeros(0, np.int64)
+    out[8], out[9], out[10] = len(stance), int(stance.sum()), int(stance.max()) if len(stance) else 0
+    out[11], out[12], out[13] = len(swing), int(swing.sum()), int(swing.max()) if len(swing) else 0
+    return td
+
+
+def footfall_numpy(rec_gait, rec_done, spec, frame_first=0, frame_every=1, frames=None):
+    """The twin of irrl_eval_footfall (include/irrl_env.h): rec_gait [rows, N, 32], rec_done [rows, N] or None -> dict(counts uint32 [N, 4, 14]
+    (FOOTFALL_COUNTS), support uint32 [N, 16], phase uint32 [N, 3, phase_bins] (None with phase_bins = 0), pattern uint8 [T, N]); the filter is
+    footfall_filter_numpy, the sequential rule"""
+    s = footfall_spec(spec)
+    rec, te = _gait_window(rec_gait, rec_done, frame_first, frame_every, frames)
+    T, N, bins = rec.shape[0], rec.shape[1], s["phase_bins"]
+    counts = np.zeros((N, 4, len(FOOTFALL_COUNTS)), np.uint32)
+    support = np.zeros((N, 16), np.uint32)
+    phase = np.zeros((N, 3, bins), np.uint32) if bins > 0 else None
+    pattern = np.zeros((T, N), np.uint8)
+    for e in range(N):
+        n = int(te[e])
+        c = rec[:n, e, 24:28] != 0
+        tds = []
+        out = np.zeros(len(FOOTFALL_COUNTS), np.int64)
+        for l in range(4):
+            f = footfall_filter_numpy(c[:, l], s["reach"], s["hold"])
+            tds.append(_footfall_leg(c[:, l], f, out))
+            counts[e, l] = out.astype(np.uint32)
+            pattern[:n, e] |= (f.astype(np.uint8) << l).astype(np.uint8)
+        support[e] = np.bincount(pattern[:n, e], minlength=16)
+        if bins > 0 and len(tds[0]) > 1:
+            for l in (1, 2, 3):
+                at = np.searchsorted(tds[0], tds[l], side="right") - 1
+                for t, i in zip(tds[l], at):
+                    if i >= 0 and i + 1 < len(tds[0]):
+                        a, b = int(tds[0][i]), int(tds[0][i + 1])
+                        phase[e, l - 1, (int(t) - a) * bins // (b - a)] += 1
+    return dict(counts=counts, support=support, phase=phase, pattern=pattern)
+
+
+def footfall_struct(spec):
+    from . import _lib
+    s = footfall_spec(spec)
+    return _lib.EvalFootfallSpec(reach=s["reach"], hold=s["hold"], phase_bins=s["phase_bins"])
+
+
+def _gait_device_args(rec_gait, rec_done):
+    import torch
+    from . import _lib
+    if rec_gait.dim() != 3 or rec_gait.shape[2] != GAIT_REC_DIM or rec_gait.dtype != torch.float32 or not rec_gait.is_cuda:
+        raise ValueError("rec_gait is a float32 device tensor [rows, N, %d]" % GAIT_REC_DIM)
+    rec_gait = _lib.contig(rec_gait)
+    if rec_done is not None:
+        if tuple(rec_done.shape) != tuple(rec_gait.shape[:2]) or rec_done.dtype not in (torch.bool, torch.uint8) or rec_done.device != rec_gait.device:
+            raise ValueError("rec_done is a bool / uint8 tensor [rows, N] on rec_gait's device")
+        rec_done = _lib.contig(rec_done)
+    return rec_gait, rec_done
+
+
+def footfall_device(rec_gait, rec_done, spec, frame_first=0, frame_every=1, frames=None, support=True, phase=True, pattern=True):
+    """footfall_numpy on the device: rec_gait a float32 device tensor [rows, N, 32] (PolicyEvaluator.run(record=("gait", "done"))), rec_done the
+    bool / uint8 recorder [rows, N] or None -- ONE call of irrl_eval_footfall on torch's current stream, one workgroup per robot, no
+    synchronisation -> dict of device tensors counts int32 [N, 4, 14], support int32 [N, 16], phase int32 [N, 3, phase_bins], pattern uint8
+    [T, N]; None for an output that is off (support / phase / pattern False, phase_bins = 0)"""
+    import torch
+    from . import _lib
+    from ._lib import ptr
+    s = footfall_spec(spec)
+    rec_gait, rec_done = _gait_device_args(rec_gait, rec_done)
+    rows, n = int(rec_gait.shape[0]), int(rec_gait.shape[1])
+    frame_first, frame_every, T = _gait_frames(rows, frame_first, frame_every, frames)
+    st = footfall_struct(s)
+    dev, bins = rec_gait.device, s["phase_bins"]
+    out = dict(counts=torch.zeros(n, 4, len(FOOTFALL_COUNTS), device=dev, dtype=torch.int32),
+               support=torch.zeros(n, 16, device=dev, dtype=torch.int32) if support else None,
+               phase=torch.zeros(n, 3, bins, device=dev, dtype=torch.int32) if phase and bins > 0 else None,
+               pattern=torch.zeros(T, n, device=dev, dtype=torch.uint8) if pattern else None)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().irrl_eval_footfall(ptr(rec_gait), ptr(rec_done), rows, n, frame_first, frame_every, T, C.cast(C.pointer(st), C.c_void_p),
+                                                  ptr(out["counts"]), ptr(out["support"]), ptr(out["phase"]), ptr(out["pattern"]), _lib.stream_ptr(dev)))
+    return out
+
+
+def _gait_to_numpy(res, unsigned):
+    out = {}
+    for k, v in res.items():
+        a = None if v is None else (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v))
+        out[k] = a.view(np.uint32) if a is not None and k in unsigned and a.dtype == np.int32 else a
+    return out
+
+
+def footfall_to_numpy(res):
+    """a result of footfall_device -> the twin's dict of numpy arrays (synchronises; the counters as uint32)"""
+    return _gait_to_numpy(res, ("counts", "support", "phase"))
+
+
+GAIT_PHASE_TOLERANCE = 0.125      # footfall_row: a leg is "with" or "half a stride from" leg 0 within 1 / 8 stride
+# the phase lags (in strides) of FL, HR, HL against FR that name a gait
+GAIT_LAGS = {"trot": (0.5, 0.5, 0.0), "pace": (0.5, 0.0, 0.5), "bound": (0.0, 0.5, 0.5), "pronk": (0.0, 0.0, 0.0)}
+
+
+def footfall_row(counts, support, phase, control_dt):
+    """one robot's counts [4, 14], support [16] (or None) and phase [3, bins] (or None) -> dict: per leg l duty<l> (STANCE / FRAMES), stride_s<l>
+    ((LAST_TD - FIRST_TD) / (TOUCHDOWNS - 1) frames, in seconds), stride_hz<l>, stance_s<l>, swing_s<l> (the mean complete phase), raw_hz<l> (the
+    raw flags' touchdown rate, what gait_from_sums calls stride_hz); their means over the legs duty, stride_hz, raw_hz; frames; flight (support[0]
+    / FRAMES); lag1 .. lag3, the circular mean of the phase bins' centres of legs 1 .. 3 against leg 0 in strides, 0 <= lag < 1; gait: "trot" /
+    "pace" / "bound" / "pronk" where the three lags sit within 1 / 8 stride of the pattern (legs FR, FL, HR, HL: trot has FL and HR half a
+    stride from FR and HL with it), else "other".  NaN where a denominator is 0."""
+    c = np.asarray(counts).astype(np.int64)
+    dt = float(control_dt)
+    div = lambda a, b: float(a) / float(b) if b > 0 else float("nan")
+    out = {"frames": int(c[0, 0])}
+    for l in range(4):
+        n, td = int(c[l, 0]), int(c[l, 4])
+        out["duty%d" % l] = div(c[l, 3], n)
+        out["stride_s%d" % l] = div(c[l, 7] - c[l, 6], td - 1) * dt if td > 1 else float("nan")
+        out["stride_hz%d" % l] = 1.0 / out["stride_s%d" % l] if td > 1 and c[l, 7] > c[l, 6] else float("nan")
+        out["stance_s%d" % l] = div(c[l, 9], c[l, 8]) * dt
+        out["swing_s%d" % l] = div(c[l, 12], c[l, 11]) * dt
+        out["raw_hz%d" % l] = div(c[l, 2], n * dt)
+    for k in ("duty", "stride_hz", "raw_hz"):
+        v = [out["%s%d" % (k, l)] for l in range(4)]
+        out[k] = float(np.mean(v))
+    out["flight"] = div(np.asarray(support)[0], c[0, 0]) if support is not None else float("nan")
+    lags = []
+    for l in range(3):
+        lag = float("nan")
+        if phase is not None:
+            h = np.asarray(phase)[l].astype(np.float64)
+            if h.sum() > 0:
+                ang = 2.0 * np.pi * (np.arange(len(h)) + 0.5) / len(h)
+                sx, sy = float((h * np.cos(ang)).sum()), float((h * np.sin(ang)).sum())
+                if math.hypot(sx, sy) > 1e-9 * h.sum():
+                    lag = (math.atan2(sy, sx) / (2.0 * np.pi) - 0.5 / len(h)) % 1.0
+        out["lag%d" % (l + 1)] = lag
+        lags.append(lag)
+    out["gait"] = "other"
+    if not any(x != x for x in lags):
+        off = lambda x, y: abs((x - y + 0.5) % 1.0 - 0.5)
+        for name, want in GAIT_LAGS.items():
+            if all(off(x, y) <= GAIT_PHASE_TOLERANCE for x, y in zip(lags, want)):
+                out["gait"] = name
+    return out
+
+
+# ---- the motor plane of a gait recorder: the joints against the motor's torque-speed envelope, the stride-folded loop ----
+MOTOR_MAX_FRAMES, MOTOR_MAX_BINS, MOTOR_MAX_PERIOD = 16384, 64, 1024
+MOTOR_COUNTS = ("samples", "sat_up", "sat_low", "outside", "motoring", "braking")
+MOTOR_KNEE_RATIO = 1.55
+_MOTOR_DOUBLES = ("tau_max", "w_crit", "w_max", "knee_ratio", "sat", "t_lo", "t_hi", "w_lo", "w_hi")
+_MOTOR_INTS = ("t_bins", "w_bins", "period")
+
+
+def motor_spec(env_cfg=None, tau_max=None, w_crit=None, w_max=None, knee_ratio=MOTOR_KNEE_RATIO, sat=0.01, t_lo=-20.0, t_hi=20.0, w_lo=-45.0, w_hi=45.0,
+               t_bins=40, w_bins=45, period=100):
+    """The spec of irrl_eval_motor_plane.  env_cfg: the `environment:` mapping of a config (MotorMaxTorque, MotorCriticalSpeed, MotorMaxSpeed: the
+    envelope the env's torque clamp applies) or None with the three given; sat: how close to the envelope (N m, motor side) a sample counts as
+    saturated; the ranges +-20 N m x +-45 rad/s are the axes of the reference's Figure 5, the period its phase_jagged fold's 100 frames.
+    -> dict, refused like the C call refuses its struct"""
+    cfg = {} if env_cfg is None else dict(env_cfg.get("environment", env_cfg))
+    pick = lambda v, key: float(cfg[key]) if v is None else float(v)
+    return motor_spec_check(dict(tau_max=pick(tau_max, "MotorMaxTorque"), w_crit=pick(w_crit, "MotorCriticalSpeed"), w_max=pick(w_max, "MotorMaxSpeed"),
+                                 knee_ratio=knee_ratio, sat=sat, t_lo=t_lo, t_hi=t_hi, w_lo=w_lo, w_hi=w_hi, t_bins=t_bins, w_bins=w_bins, period=period))
+
+
+def motor_spec_check(spec):
+    s = {k: float(spec[k]) for k in _MOTOR_DOUBLES}
+    s.update({k: int(spec[k]) for k in _MOTOR_INTS})
+    fin = math.isfinite
+    if not fin(s["tau_max"]) or not s["tau_max"] > 0.0:
+        raise ValueError("motor spec: tau_max > 0, finite")
+    if not fin(s["w_crit"]) or not fin(s["w_max"]) or not s["w_max"] > s["w_crit"]:
+        raise ValueError("motor spec: w_crit < w_max, both finite")
+    if not fin(s["knee_ratio"]) or not s["knee_ratio"] > 0.0:
+        raise ValueError("motor spec: knee_ratio > 0, finite")
+    if not fin(s["sat"]) or not s["sat"] >= 0.0:
+        raise ValueError("motor spec: sat >= 0, finite")
+    if not 0 <= s["t_bins"] <= MOTOR_MAX_BINS or not 0 <= s["w_bins"] <= MOTOR_MAX_BINS:
+        raise ValueError("motor spec: t_bins, w_bins lie in 0 .. %d" % MOTOR_MAX_BINS)
+    if not 0 <= s["period"] <= MOTOR_MAX_PERIOD:
+        raise ValueError("motor spec: period lies in 0 .. %d" % MOTOR_MAX_PERIOD)
+    if s["t_bins"] > 0 and s["w_bins"] > 0:
+        if not (fin(s["t_lo"]) and fin(s["t_hi"]) and s["t_hi"] > s["t_lo"]) or not (fin(s["w_lo"]) and fin(s["w_hi"]) and s["w_hi"] > s["w_lo"]):
+            raise ValueError("motor spec: t_lo < t_hi, w_lo < w_hi, all finite")
+    return s
+
+
+def motor_up(w, s):
+    """irrl_eval_motor_up on an array, statement for statement"""
+    span = s["w_max"] - s["w_crit"]
+    slope = s["tau_max"] / span
+    over = w - s["w_crit"]
+    drop = over * slope
+    return np.where(w > s["w_crit"], s["tau_max"] - drop, s["tau_max"])
+
+
+def motor_samples(rec, spec):
+    """recorder rows [..., 32] -> (m, w float64 [..., 12], kept bool [..., 12]): irrl_eval_motor_sample"""
+    ratio = np.where(np.arange(12) % 3 == 2, spec["knee_ratio"], 1.0)
+    rec = np.asarray(rec)
+    with np.errstate(invalid="ignore", over="ignore"):
+        m = rec[..., 0:12].astype(np.float64) / ratio
+        w = rec[..., 12:24].astype(np.float64) * ratio
+    return m, w, np.isfinite(m) & np.isfinite(w)
+
+
+def _motor_shape(n, conditions):
+    conditions = int(conditions)
+    if conditions < 1 or n % conditions:
+        raise ValueError("conditions * robots == num_envs, conditions >= 1")
+    return conditions, n // conditions
+
+
+def motor_plane_numpy(rec_gait, rec_done, spec, conditions=None, frame_first=0, frame_every=1, frames=None):
+    """The twin of irrl_eval_motor_plane (include/irrl_env.h): rec_gait [rows, N, 32], rec_done [rows, N] or None, env = condition * robots +
+    robot (conditions None: N, one robot each) -> dict(counts uint32 [C, 12, 6] (MOTOR_COUNTS), hist uint32 [C, 12, t_bins, w_bins] (None with a
+    zero bin count), fold float64 [C, 12, period, 3] (None with period = 0): count, sum m, sum w per phase, added robot by robot and frame by
+    frame in index order)"""
+    s = motor_spec_check(spec)
+    rec, te = _gait_window(rec_gait, rec_done, frame_first, frame_every, frames)
+    T, N = rec.shape[0], rec.shape[1]
+    Cn, R = _motor_shape(N, N if conditions is None else conditions)
+    m, w, kept = motor_samples(rec, s)                         # [T, N, 12]
+    kept &= (np.arange(T)[:, None] < te[None, :])[:, :, None]
+    with np.errstate(invalid="ignore", over="ignore"):
+        up, low = motor_up(w, s), -motor_up(-w, s)
+        power = m * w
+        classes = [kept, kept & (m >= up - s["sat"]), kept & (m <= low + s["sat"]), kept & ((m > up + s["sat"]) | (m < low - s["sat"])),
+                   kept & (power > 0.0), kept & (power < 0.0)]
+    counts = np.stack([k.reshape(T, Cn, R, 12).sum((0, 2)) for k in classes], -1).astype(np.uint32)
+    hist = fold = None
+    tb, wb, period = s["t_bins"], s["w_bins"], s["period"]
+    if tb > 0 and wb > 0:
+        bt, bw = ensemble_bins(m, s["t_lo"], s["t_hi"], tb), ensemble_bins(w, s["w_lo"], s["w_hi"], wb)
+        ok = kept & (bt >= 0) & (bw >= 0)
+        cj = (np.arange(N) // R)[None, :, None] * 12 + np.arange(12)[None, None, :]
+        cell = (cj * tb + bt) * wb + bw
+        hist = np.bincount(cell[ok], minlength=Cn * 12 * tb * wb).astype(np.uint32).reshape(Cn, 12, tb, wb)
+    if period > 0:
+        K = -(-T // period)
+        pad = K * period - T
+        z = lambda a: np.concatenate([np.where(kept, a, 0.0), np.zeros((pad, N, 12))], 0).reshape(K, period, Cn, R, 12)
+        one, mm, ww = z(np.ones_like(m)), z(m), z(w)
+        fold = np.zeros((Cn, 12, period, 3))
+        for r in range(R):                                     # robots in order, frames in order: ONE order of the f64 additions
+            for k in range(K):
+                for i, a in enumerate((one, mm, ww)):
+                    fold[:, :, :, i] = fold[:, :, :, i] + a[k, :, :, r, :].transpose(1, 2, 0)
+    return dict(counts=counts, hist=hist, fold=fold)
+
+
+def motor_struct(spec):
+    from . import _lib
+    s = motor_spec_check(spec)
+    return _lib.EvalMotorSpec(**s)
+
+
+def motor_plane_device(rec_gait, rec_done, spec, conditions=None, frame_first=0, frame_every=1, frames=None, hist=True, fold=True):
+    """motor_plane_numpy on the device: ONE call of irrl_eval_motor_plane on torch's current stream, one workgroup per (condition, joint), no
+    synchronisation -> dict of device tensors counts int32 [C, 12, 6], hist int32 [C, 12, t_bins, w_bins], fold float64 [C, 12, period, 3]; None
+    for an output that is off"""
+    import torch
+    from . import _lib
+    from ._lib import ptr
+    s = motor_spec_check(spec)
+    rec_gait, rec_done = _gait_device_args(rec_gait, rec_done)
+    rows, n = int(rec_gait.shape[0]), int(rec_gait.shape[1])
+    Cn, R = _motor_shape(n, n if conditions is None else conditions)
+    frame_first, frame_every, T = _gait_frames(rows, frame_first, frame_every, frames, MOTOR_MAX_FRAMES)
+    st = motor_struct(s)
+    dev = rec_gait.device
+    out = dict(counts=torch.zeros(Cn, 12, len(MOTOR_COUNTS), device=dev, dtype=torch.int32),
+               hist=torch.zeros(Cn, 12, s["t_bins"], s["w_bins"], device=dev, dtype=torch.int32) if hist and s["t_bins"] > 0 and s["w_bins"] > 0 else None,
+               fold=torch.zeros(Cn, 12, s["period"], 3, device=dev, dtype=torch.float64) if fold and s["period"] > 0 else None)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().irrl_eval_motor_plane(ptr(rec_gait), ptr(rec_done), rows, n, Cn, R, frame_first, frame_every, T,
+                                                     C.cast(C.pointer(st), C.c_void_p), ptr(out["counts"]), ptr(out["hist"]), ptr(out["fold"]),
+                                                     _lib.stream_ptr(dev)))
+    return out
+
+
+def motor_plane_to_numpy(res):
+    """a result of motor_plane_device -> the twin's dict of numpy arrays (synchronises; the counters as uint32)"""
+    return _gait_to_numpy(res, ("counts", "hist"))
+
+
+def motor_plane_row(counts):
+    """one condition's counts [12, 6] -> dict of float64 [12] arrays: saturated ((SAT_UP + SAT_LOW) / SAMPLES), outside, motoring, braking (NaN
+    for a joint without a sample), and samples int64 [12]"""
+    c = np.asarray(counts).astype(np.float64)
+    n = np.where(c[:, 0] > 0, c[:, 0], np.nan)
+    return dict(saturated=(c[:, 1] + c[:, 2]) / n, outside=c[:, 3] / n, motoring=c[:, 4] / n, braking=c[:, 5] / n, samples=np.asarray(counts)[:, 0].astype(np.int64))
+
+
 # ---- the device loop ----
 def resolve_persistent(persistent, supported):
     """the `persistent` keyword of PolicyEvaluator.run / robustness_sweep (False, True, "auto"; the command line's "off" / "on" too) -> bool;
@@ -1377,7 +1778,7 @@ def load_policy(model_or_policy, device):
 
 def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=1000, steps=2000, cmd_hz=1.0, vel_hz=None, act_hz=None, clip=True,
                      mu_warm=0.8, device=None, persistent=PERSISTENT_DEFAULT, levels=None, level_steps=None, heading=None, gait=False,
-                     mass=None, g=9.81, recurrence=None, recurrence_frames=None, record_body=False):
+                     mass=None, g=9.81, recurrence=None, recurrence_frames=None, record_body=False, footfall=None, motor=None, record_gait=False):
     """The reference's robustness grid in one pool: len(mus) x len(delays) x len(cmds) Manual-mode envs (condition index = (i_mu * len(delays) +
     i_delay) * len(cmds) + i_cmd), `warm_steps` control steps on friction mu_warm, then `steps` on the condition's own friction over which the
     statistics are taken.  env_cfg: the `environment:` mapping of a config.  persistent: PolicyEvaluator.run's keyword (same statistics bit for bit
@@ -1394,7 +1795,14 @@ def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=100
     out of the lag words 0 .. T / 2 from the Theiler window on) over the LAST recurrence_frames = T frames of the run (default: min(steps, 800));
     with a staircase over the last T frames of each level's second half (refused if they do not fit); the rows of the first 8 conditions also
     carry `matrix` uint8 [T, T], the levels of the recurrence plot.  record_body: every row carries `body` [steps, 13] (staircase: [level_steps,
-    13], the level's frames), whose last T frames the recurrence analysis saw.  Without these keywords the rows are what they were, key for key."""
+    13], the level's frames), whose last T frames the recurrence analysis saw.
+    footfall: a spec (FOOTFALL_SPEC_REFERENCE) / motor: a spec (motor_spec(env_cfg)) -- the gait recorder and the `done` recorder are kept on the
+    device for the run and every row gains `footfall` (footfall_row: debounced duty, stride period and frequency, stance and swing times, flight,
+    the legs' phase lags, the gait's name; plus `counts` [4, 14], `support` [16], `phase` [3, bins]) and / or `motor` (motor_plane_row: the
+    saturated, outside, motoring and braking fractions per joint; plus `counts` [12, 6], `fold` [period, 3]) over the frames the row's statistics
+    cover (staircase: the second half of the level); the rows of the first 8 conditions also carry `pattern` uint8 [frames] (the gait diagram)
+    and `hist` uint32 [12, t_bins, w_bins].  record_gait: every row carries `rec_gait` [frames, 32] and `rec_done` [frames], the words the two
+    analyses saw.  Without these keywords the rows are what they were, key for key."""
     import torch
     import yaml
     from . import __BLACKPANTHER_V55_RESOURCE_DIRECTORY__ as rsc
@@ -1438,13 +1846,31 @@ def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=100
         coeff[:, 0] = [g[0] for g in grid]                     # (the setter's copy is ordered on the pool's stream, behind the warm-up)
         env.SetContactCoefficient(coeff)
     ev.zero_statistics()
-    if recurrence is None and not record_body:
+    want_gait = footfall is not None or motor is not None or record_gait
+    if footfall is not None:
+        footfall = footfall_spec(footfall)
+    if motor is not None:
+        motor = motor_spec_check(motor)
+    if recurrence is None and not record_body and not want_gait:
         ev.run(steps, persistent=persistent)
         extra = lambda i, l: {}
     else:
-        rec = ev.run(steps, record=("body",), persistent=persistent)
+        rec = ev.run(steps, record=(("body",) if recurrence is not None or record_body else ()) + (("gait", "done") if want_gait else ()),
+                     persistent=persistent)
         span = steps if levels is None else level_steps               # a row's frames: the run, or its level
         parts = []
+        fparts, mparts, grec = [], [], None
+        first = lambda l: 0 if levels is None else l * span + span // 2      # the frames a row's statistics cover
+        count = steps if levels is None else span // 2
+        if count > FOOTFALL_MAX_FRAMES and (footfall is not None or motor is not None):
+            raise ValueError("footfall / motor: a row covers %d frames, more than %d" % (count, FOOTFALL_MAX_FRAMES))
+        for l in range(1 if levels is None else levels):
+            if footfall is not None:
+                fparts.append(footfall_to_numpy(footfall_device(rec["gait"], rec["done"], footfall, frame_first=first(l), frames=count)))
+            if motor is not None:
+                mparts.append(motor_plane_to_numpy(motor_plane_device(rec["gait"], rec["done"], motor, frame_first=first(l), frames=count)))
+        if record_gait:
+            grec = (rec["gait"].cpu().numpy(), rec["done"].cpu().numpy())
         if recurrence is not None:
             shown = list(range(min(len(grid), RECURRENCE_MAX_MATRICES)))
             for l in range(1 if levels is None else levels):
@@ -1455,6 +1881,19 @@ def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=100
 
         def extra(i, l):
             out = {}
+            if fparts:
+                f = fparts[l]
+                out["footfall"] = dict(footfall_row(f["counts"][i], f["support"][i], None if f["phase"] is None else f["phase"][i], ev._dt),
+                                       counts=f["counts"][i], support=f["support"][i], phase=None if f["phase"] is None else f["phase"][i])
+                if i < FOOTFALL_PATTERNS:
+                    out["pattern"] = f["pattern"][:, i]
+            if mparts:
+                m = mparts[l]
+                out["motor"] = dict(motor_plane_row(m["counts"][i]), counts=m["counts"][i], fold=None if m["fold"] is None else m["fold"][i])
+                if i < FOOTFALL_PATTERNS and m["hist"] is not None:
+                    out["hist"] = m["hist"][i]
+            if grec is not None:
+                out["rec_gait"], out["rec_done"] = grec[0][first(l):first(l) + count, i], grec[1][first(l):first(l) + count, i]
             if parts:
                 out["recurrence"] = recurrence_row(parts[l]["counts"][i], parts[l]["lag"][i], T_rec, recurrence, ev._dt)
                 if i < len(shown):
@@ -1631,9 +2070,15 @@ def perturbation_table(rows, gait=False, ensemble=False, recurrence=False):
 RECURRENCE_TABLE_KEYS = ("RR", "DET", "LMAX", "period_s")
 
 
-def sweep_table(rows, gait=False, recurrence=False):
+FOOTFALL_TABLE_KEYS = ("stride_hz_db", "duty_db", "gait", "sat_max")
+
+
+def sweep_table(rows, gait=False, recurrence=False, footfall=False):
     """one line per row of a robustness_sweep; gait (rows of a sweep with gait=True): the cost of transport, the mean mechanical power, the four
-    duty factors, the stride frequency (mean over the legs) and the flight fraction too; recurrence (rows of a sweep with a recurrence spec): the
+    duty factors, `stride_hz` (mean over the legs of gait_from_sums' stride_hz<l>: the RAW contact flags' touchdown rate, several times the
+    stride frequency because the flag chatters while a foot is down -- the debounced one is stride_hz_db) and the flight fraction too; footfall
+    (rows of a sweep with a footfall spec): stride_hz_db and duty_db, the debounced stride frequency and duty factor (footfall_row, mean over
+    the legs), the gait's name and, with a motor spec too, sat_max, the largest saturated fraction of a joint; recurrence (rows of a sweep with a recurrence spec): the
     recurrence rate, the determinism, the longest diagonal line and the stride period too"""
     keys = ("vx_body_mean", "vx_body_std", "z_mean", "z_std", "roll_std", "pitch_mean", "pitch_std", "yaw_rate_mean")
     staircase = bool(rows) and "level" in rows[0]              # one row per (condition, level): the level and its commanded v_x as well
@@ -1644,6 +2089,8 @@ def sweep_table(rows, gait=False, recurrence=False):
         out[0] += " " + " ".join("%-12s" % k for k in gkeys)
     if recurrence:
         out[0] += " " + " ".join("%-12s" % k for k in RECURRENCE_TABLE_KEYS)
+    if footfall:
+        out[0] += " " + " ".join("%-12s" % k for k in FOOTFALL_TABLE_KEYS)
     for r in rows:
         lvl = "%-5d %-9g " % (r["level"], r["cmd_level"]) if staircase else ""
         out.append("%-6g %-5d %-5g %s%-5d " % (r["mu"], r["delay"], r["cmd"], lvl, r["falls"]) + " ".join("%+12.4f" % r[k] for k in keys))
@@ -1652,4 +2099,7 @@ def sweep_table(rows, gait=False, recurrence=False):
             out[-1] += " " + " ".join("%+12.4f" % g[k] for k in gkeys)
         if recurrence:
             out[-1] += " " + " ".join("%+12.4f" % r["recurrence"][k] for k in RECURRENCE_TABLE_KEYS)
+        if footfall:
+            sat = float(np.nanmax(r["motor"]["saturated"])) if "motor" in r and not np.all(np.isnan(r["motor"]["saturated"])) else float("nan")
+            out[-1] += " %+12.4f %+12.4f %-12s %+12.4f" % (r["footfall"]["stride_hz"], r["footfall"]["duty"], r["footfall"]["gait"], sat)
     return "\n".join(out)

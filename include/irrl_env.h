@@ -681,6 +681,95 @@ typedef struct irrl_eval_recurrence_spec {
 int irrl_eval_recurrence(const float *rec_body, int rows, int num_envs, int frame_first, int frame_every, int frames,
                          const irrl_eval_recurrence_spec *spec, uint32_t *counts, uint32_t *lag, uint8_t *matrix, void *hip_stream);
 
+/* ANALYSES OF A GAIT RECORDER: debounced footfalls per robot and leg, and the motor's torque-speed plane per (condition, joint).  Both read
+ * rec_gait, device f32 [rows, num_envs, IRRL_EVAL_GAIT_REC_DIM] (tq 12 | qd 12 | in_contact 4 | f_z 4, above), and rec_done, device u8
+ * [rows, num_envs] or NULL for none.  Analysed frame i = 0 .. frames - 1 is recorder row frame_first + i * frame_every.  A `done` row holds the
+ * reset state, so robot e is analysed over i < T_e: T_e is the first analysed frame whose rec_done word is non-zero, `frames` if there is none.
+ * Stateless and stream-ordered, no env handle; no global atomics, no floating-point atomics, every output word has one writer; the words are the
+ * same bits from run to run.  Semantics in ONE text, csrc/eval_elements.hpp (irrl_eval_footfall_*, irrl_eval_motor_*).
+ *
+ * irrl_eval_footfall -- the reference never reads raw contact flags: Data_Visualization_Code/Figure2.py:97-116 (Contact_filtered) takes a 5-frame
+ * moving average cast to bool and then fills every contact gap shorter than 10 frames.  THE FILTER RULE (irrl_eval_footfall_filter), for leg l
+ * over the robot's window T = T_e with c[k] = (column 24 + l != 0):
+ *   dilate: d[k] = any c[k'] with |k' - k| <= reach and 0 <= k' < T;
+ *   hold:   f = d; then in increasing j = 0 .. T - hold - 2: if f[j] && !f[j+1], f[j+1] = any of f[j+1 .. j+hold].
+ * With reach = 2, hold = 10 this is Contact_filtered for every T >= 5 (below 5, np.convolve(mode='same') returns five samples and the reference
+ * has no defined answer).  THE CLOSED FORM the kernel uses (one writer per frame; irrl_eval_footfall_fill_end):
+ *   f[k] = d[k] || (k <= T - hold - 1 && a exists && b exists && b - a <= hold),  a = the last k' < k with d[k'],  b = the first k' > k with d[k'];
+ * so leading and trailing gaps are never filled, gaps of at most hold - 1 frames are filled, the last `hold` frames of a window are not filled.
+ * Outputs, all integers:
+ *   counts[e, leg, IRRL_EVAL_FOOTFALL_COUNTS] u32 (required):
+ *      0 FRAMES          T_e
+ *      1 RAW_STANCE      frames with c
+ *      2 RAW_TOUCHDOWNS  k >= 1 with !c[k-1] && c[k]
+ *      3 STANCE          frames with f
+ *      4 TOUCHDOWNS      rising edges of f, k >= 1 with !f[k-1] && f[k]
+ *      5 LIFTOFFS        falling edges of f, k >= 1 with f[k-1] && !f[k]
+ *      6 FIRST_TD, 7 LAST_TD   frame index of the first / last touchdown, 0xFFFFFFFF if none
+ *      8 STANCE_PHASES, 9 STANCE_SUM, 10 STANCE_MAX   complete stance phases (a touchdown and the next liftoff, both inside the window): their
+ *                        number, their summed length in frames (liftoff - touchdown), the longest
+ *      11 SWING_PHASES, 12 SWING_SUM, 13 SWING_MAX    complete swings (a liftoff and the next touchdown; touchdown - liftoff)
+ *      the stride period in frames is (LAST_TD - FIRST_TD) / (TOUCHDOWNS - 1)
+ *   support[e, 16] u32 (NULL: off)  the frames i < T_e whose support pattern p = sum_l f_l << l has that value; support[e, 0] is flight
+ *   phase[e, 3, phase_bins] u32 (NULL or phase_bins = 0: off)  for leg l = 1 .. 3 every touchdown of leg l at frame t with a <= t < b, a and b
+ *                        consecutive touchdowns of leg 0, counted in bin (t - a) * phase_bins / (b - a) (integer division) of row l - 1; touchdowns
+ *                        outside a complete stride of leg 0 are not counted
+ *   pattern[i, e] u8 [frames, num_envs] (NULL: off)  p of frame i, 0 for i >= T_e: the gait diagram
+ * One workgroup per robot; the flags live in LDS as 64-frame bit words.
+ *
+ * irrl_eval_motor_plane -- the reference's Figure 5 (Data_Visualization_Code/Figure5.py:250-289, :379-392): where the joints operate against
+ * the motor envelope, and the stride-folded torque-speed loop.  env index = condition * robots + robot.  THE SAMPLE of robot r, frame i < T_e,
+ * joint j (irrl_eval_motor_sample): ratio = (j % 3 == 2) ? knee_ratio : 1.0, m = (double)tq_j / ratio, w = (double)qd_j * ratio, kept iff both are
+ * finite.  THE ENVELOPE (irrl_eval_motor_up, the f64 restatement of the env's torque clamp):
+ *   up(w) = w > w_crit ? tau_max - (w - w_crit) * (tau_max / (w_max - w_crit)) : tau_max,   low(w) = -up(-w),  every product rounded on its own.
+ * Outputs:
+ *   counts[c, 12, IRRL_EVAL_MOTOR_COUNTS] u32 (required):  0 SAMPLES  1 SAT_UP (m >= up(w) - sat)  2 SAT_LOW (m <= low(w) + sat)
+ *      3 OUTSIDE (m > up(w) + sat || m < low(w) - sat)  4 MOTORING (m * w > 0)  5 BRAKING (m * w < 0)
+ *   hist[c, 12, t_bins, w_bins] u32 (NULL or a zero bin count: off)  the kept samples by irrl_eval_ensemble_bin(m, t_lo, t_hi, t_bins) and
+ *      irrl_eval_ensemble_bin(w, w_lo, w_hi, w_bins); a sample outside either range is dropped from hist only
+ *   fold[c, 12, period, 3] f64 (NULL or period = 0: off)  the count, sum of m and sum of w of the kept samples with i % period == p, added robot by
+ *      robot in index order and, within a robot, frame by frame in index order: the same bits on every machine (the reference's phase_jagged fold)
+ * One workgroup per (condition, joint); the 2-D histogram in LDS with integer LDS atomics; one thread per phase p walks its samples in order.
+ *
+ * Both refuse before any HIP call, with "irrl_eval_footfall: " / "irrl_eval_motor_plane: " in front of the text: a NULL rec_gait, spec or counts;
+ * num_envs < 1; frames outside 0 .. the limit; frame_first < 0, frame_every < 1, frame_first + (frames - 1) * frame_every >= rows; reach outside
+ * 0 .. IRRL_EVAL_FOOTFALL_MAX_REACH, hold outside 0 .. IRRL_EVAL_FOOTFALL_MAX_HOLD, phase_bins outside 0 .. IRRL_EVAL_FOOTFALL_MAX_BINS; t_bins or
+ * w_bins outside 0 .. IRRL_EVAL_MOTOR_MAX_BINS, period outside 0 .. IRRL_EVAL_MOTOR_MAX_PERIOD; w_max <= w_crit; tau_max, w_crit, w_max,
+ * knee_ratio or sat not finite, tau_max <= 0, knee_ratio <= 0, sat < 0; t_hi <= t_lo or w_hi <= w_lo (or a bound not finite) with bins on;
+ * robots < 1, conditions < 1, conditions * robots != num_envs.  frames == 0 is accepted and does nothing. */
+#define IRRL_EVAL_FOOTFALL_MAX_FRAMES 16384
+#define IRRL_EVAL_FOOTFALL_MAX_REACH 8
+#define IRRL_EVAL_FOOTFALL_MAX_HOLD 64
+#define IRRL_EVAL_FOOTFALL_MAX_BINS 64
+#define IRRL_EVAL_FOOTFALL_COUNTS 14
+#define IRRL_EVAL_FOOTFALL_NONE 0xFFFFFFFFu
+enum {
+  IRRL_EVAL_FOOTFALL_FRAMES = 0, IRRL_EVAL_FOOTFALL_RAW_STANCE, IRRL_EVAL_FOOTFALL_RAW_TOUCHDOWNS, IRRL_EVAL_FOOTFALL_STANCE,
+  IRRL_EVAL_FOOTFALL_TOUCHDOWNS, IRRL_EVAL_FOOTFALL_LIFTOFFS, IRRL_EVAL_FOOTFALL_FIRST_TD, IRRL_EVAL_FOOTFALL_LAST_TD,
+  IRRL_EVAL_FOOTFALL_STANCE_PHASES, IRRL_EVAL_FOOTFALL_STANCE_SUM, IRRL_EVAL_FOOTFALL_STANCE_MAX,
+  IRRL_EVAL_FOOTFALL_SWING_PHASES, IRRL_EVAL_FOOTFALL_SWING_SUM, IRRL_EVAL_FOOTFALL_SWING_MAX
+};
+typedef struct irrl_eval_footfall_spec {
+  int reach, hold, phase_bins;
+} irrl_eval_footfall_spec;
+int irrl_eval_footfall(const float *rec_gait, const uint8_t *rec_done, int rows, int num_envs, int frame_first, int frame_every, int frames,
+                       const irrl_eval_footfall_spec *spec, uint32_t *counts, uint32_t *support, uint32_t *phase, uint8_t *pattern, void *hip_stream);
+
+#define IRRL_EVAL_MOTOR_MAX_FRAMES 16384
+#define IRRL_EVAL_MOTOR_MAX_BINS 64
+#define IRRL_EVAL_MOTOR_MAX_PERIOD 1024
+#define IRRL_EVAL_MOTOR_COUNTS 6
+enum {
+  IRRL_EVAL_MOTOR_SAMPLES = 0, IRRL_EVAL_MOTOR_SAT_UP, IRRL_EVAL_MOTOR_SAT_LOW, IRRL_EVAL_MOTOR_OUTSIDE, IRRL_EVAL_MOTOR_MOTORING, IRRL_EVAL_MOTOR_BRAKING
+};
+typedef struct irrl_eval_motor_spec {
+  double tau_max, w_crit, w_max, knee_ratio, sat, t_lo, t_hi, w_lo, w_hi;
+  int t_bins, w_bins, period;
+} irrl_eval_motor_spec;
+int irrl_eval_motor_plane(const float *rec_gait, const uint8_t *rec_done, int rows, int num_envs, int conditions, int robots, int frame_first,
+                          int frame_every, int frames, const irrl_eval_motor_spec *spec, uint32_t *counts, uint32_t *hist, double *fold,
+                          void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,9 @@ reference's own (run_bp_v5.py:8-13), resolved by the compat packages at the repo
     python scripts/run_bp_v5.py --test --sweep --model data/..._final.pkl --sweep_cmd 5 --recurrence [--recurrence_frames 800 --recurrence_radius 10] \
         --out sweep.json                                                                   # + recurrence rate, determinism, longest line and stride
                                                                                            # period per condition; the matrices of the first 8 to --out
+    python scripts/run_bp_v5.py --test --sweep --model data/..._final.pkl --sweep_cmd 2,5 --footfall [--motor] --out sweep.json
+                                                                                           # + debounced stride frequency, duty, the gait's name
+                                                                                           # [+ motor saturation]; gait diagrams and maps to --out
     python scripts/run_bp_v5.py --test --sweep --step --gait --model data/..._final.pkl --persistent on   # cost of transport, duty factors and
                                                                                            # touchdown rate per (friction, command level)
 
@@ -115,6 +118,12 @@ def parse_args(argv):
     p.add_argument("--recurrence", dest="flag_recurrence", action="store_true", default=False,
                    help="--sweep: the reference's recurrence plot in numbers, per robot on the device (evaluate.RECURRENCE_SPEC_REFERENCE): the table gains "
                         "RR, DET, LMAX and period_s (--perturb: their medians over the survivors); --out also gets the level matrices of the first 8 conditions")
+    p.add_argument("--footfall", dest="flag_footfall", action="store_true", default=False,
+                   help="--sweep: the reference's debounced contact flags per robot on the device (evaluate.FOOTFALL_SPEC_REFERENCE): the table gains "
+                        "stride_hz_db, duty_db and gait; --out also gets the gait diagrams (`pattern`) of the first 8 conditions")
+    p.add_argument("--motor", dest="flag_motor", action="store_true", default=False,
+                   help="--footfall: the motor's torque-speed plane per condition and joint on the device (evaluate.motor_spec of the config): the table "
+                        "gains sat_max; --out also gets the folded loops and the 2-D maps (`hist`) of the first 8 conditions")
     p.add_argument("--recurrence_frames", type=int, default=None, help="--recurrence: the last so many frames of the run are analysed (default: min(steps, 800))")
     p.add_argument("--recurrence_radius", type=int, default=None, help="--recurrence: the recurrence radius in levels of 0.001 (default 10)")
     return p.parse_args(argv)
@@ -129,6 +138,23 @@ def recurrence_keywords(args):
     if args.recurrence_radius is not None:
         spec["radius"] = args.recurrence_radius
     return dict(recurrence=spec, recurrence_frames=args.recurrence_frames)
+
+
+def footfall_keywords(args, env_cfg):
+    """--footfall [--motor] -> the keywords of robustness_sweep"""
+    from high_speed_quadrupedal_locomotion_by_irrl_amd.evaluate import FOOTFALL_SPEC_REFERENCE, motor_spec
+    if args.flag_motor and not args.flag_footfall:
+        raise SystemExit("--motor goes with --footfall")
+    if not args.flag_footfall:
+        return {}
+    return dict(footfall=dict(FOOTFALL_SPEC_REFERENCE), motor=motor_spec(env_cfg) if args.flag_motor else None)
+
+
+def plain(v):
+    """a row's value for json: arrays as nested lists, dicts of them too"""
+    if isinstance(v, dict):
+        return {k: plain(x) for k, x in v.items()}
+    return v.tolist() if hasattr(v, "tolist") else v
 
 
 def run_test(args, cfg):
@@ -216,11 +242,12 @@ def run_sweep(args, cfg):
                             cmd_hz=args.cmd_filter_freq, vel_hz=none_if_off(args.vel_filter_freq), act_hz=none_if_off(args.act_filter_freq),
                             persistent=PERSISTENT_DEFAULT if args.persistent is None else args.persistent,
                             levels=4 if args.flag_step else None, level_steps=args.step_steps if args.flag_step else None,
-                            heading=heading_hold(n) if args.flag_dir_fd else None, **gait, **recurrence_keywords(args))
-    print(sweep_table(rows, gait=args.flag_gait, recurrence=args.flag_recurrence))
+                            heading=heading_hold(n) if args.flag_dir_fd else None, **gait, **recurrence_keywords(args),
+                            **footfall_keywords(args, cfg["environment"]))
+    print(sweep_table(rows, gait=args.flag_gait, recurrence=args.flag_recurrence, footfall=args.flag_footfall))
     if args.out:
         with open(args.out, "w") as f:                                 # (--recurrence: the level matrices of the first 8 conditions as nested lists)
-            json.dump([{k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in r.items()} for r in rows], f, indent=1)
+            json.dump([{k: plain(v) for k, v in r.items()} for r in rows], f, indent=1)   # (--footfall / --motor: the patterns and the maps too)
         print("table written to", args.out)
     return rows
 

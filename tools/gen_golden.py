@@ -341,9 +341,42 @@ def gen_recurrence_windows():
     print("wrote raisim_recurrence_windows.npz", np.stack(body).shape, mu, delay, cmd)
 
 
+def gen_motor_plane():
+    """tests/golden/raisim_motor_plane.npz: RaiSim's joint torques and rates of bp5_155 at 5 m/s (Exp_Raw_Data/power-2021-07-07-08-25-45.bin: 1000
+    control frames x 8 sub-steps, stored as [192, 1000] float32; after transposing, columns 12 s + j are the torque of sub-step slot s and
+    96 + 12 s + j the rate, Data_Visualization_Code/Figure5.py:98-126), slot 7 of every control frame as tq, qd float32 [1000, 12], joint side,
+    with the settings of its Param-<date>.txt and, as recorded results, the counts the numpy twin of the motor plane finds at the config's
+    envelope (18 N m, 14.2 rad/s, 40 rad/s, knee ratio 1.55).  Data only."""
+    import yaml
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    from high_speed_quadrupedal_locomotion_by_irrl_amd import evaluate as EV
+    src = os.path.join(os.path.dirname(os.path.dirname(REF)), "Exp_Raw_Data")
+    date = "2021-07-07-08-25-45"
+    cfg = yaml.safe_load(open(os.path.join(src, "Param-%s.txt" % date)))
+    raw = np.fromfile(os.path.join(src, "power-%s.bin" % date), dtype=np.float32)
+    assert int(cfg["seg_len"]) == 1000 and int(cfg["FoE"]) == 1000 and int(cfg["NoE"]) == 1 and int(cfg["Num_Of_Env"]) == 1 and raw.size == 192 * 1000
+    data = raw.reshape(192, 1000).T
+    slot = 7
+    tq, qd = np.ascontiguousarray(data[:, 12 * slot:12 * slot + 12]), np.ascontiguousarray(data[:, 96 + 12 * slot:96 + 12 * slot + 12])
+    spec = EV.motor_spec(None, tau_max=18.0, w_crit=14.2, w_max=40.0, sat=1e-3)
+    rec = np.zeros((1000, 1, 32), np.float32)
+    rec[:, 0, 0:12], rec[:, 0, 12:24] = tq, qd
+    counts = EV.motor_plane_numpy(rec, None, spec)["counts"][0]
+    # the same over all 8000 sub-step rows: nothing outside the envelope by more than sat
+    every = np.zeros((8000, 1, 32), np.float32)
+    every[:, 0, 0:12], every[:, 0, 12:24] = data[:, 0:96].reshape(-1, 12), data[:, 96:192].reshape(-1, 12)
+    counts_all = EV.motor_plane_numpy(every, None, spec)["counts"][0]
+    np.savez_compressed(os.path.join(OUT, "raisim_motor_plane.npz"), tq=tq.astype(np.float32), qd=qd.astype(np.float32), name=np.array(date), slot=np.int64(slot),
+                        policy=np.array(str(cfg["policy_name"])), mu=np.float64(cfg["Mu_Min"]), delay=np.int64(cfg["delay"]), cmd=np.float64(cfg["V_Min"]),
+                        frame_dt=np.float64(0.01), sat=np.float64(1e-3), counts=counts, counts_all_substeps=counts_all)
+    print("wrote raisim_motor_plane.npz", tq.shape, "counts (samples sat_up sat_low outside motoring braking) per joint:\n", counts, "\nall sub-steps:\n", counts_all)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["task", "lstm", "lstm_syn", "ppo", "actor", "ckpt", "recurrence"]
+    which = sys.argv[1:] or ["task", "lstm", "lstm_syn", "ppo", "actor", "ckpt", "recurrence", "motor"]
+    if "motor" in which:
+        gen_motor_plane()
     if "recurrence" in which:
         gen_recurrence_windows()
     if "ckpt" in which:
