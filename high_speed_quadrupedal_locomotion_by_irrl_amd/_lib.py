@@ -120,6 +120,12 @@ SIGNATURES = {
                                 + [fp, fp, C.c_int] + [vp] * 9 + [vp, vp, vp, vp]),
     "irrl_lstm_eval_measured_persistent": (C.c_int, [vp, C.c_int, C.c_longlong] + [C.c_int] * 3 + [vp] * 6 + [C.c_int] + [vp] * 8 + [vp] * 2 + [C.c_float] * 3
                                            + [fp, fp, C.c_int] + [vp] * 9 + [vp, vp, vp, vp]),
+    # the loop with MlpPolicy as the actor, both forms: irrl_lstm_eval_measured's list with the table of 8 where lstm_w is and without lstm_state
+    "irrl_mlp_eval_measured": (C.c_int, [vp, C.c_int, C.c_longlong] + [C.c_int] * 3 + [vp] * 6 + [C.c_int] + [vp] * 7 + [vp] * 2 + [C.c_float] * 3
+                               + [fp, fp, C.c_int] + [vp] * 9 + [vp, vp, vp, vp]),
+    "irrl_mlp_eval_measured_persistent": (C.c_int, [vp, C.c_int, C.c_longlong] + [C.c_int] * 3 + [vp] * 6 + [C.c_int] + [vp] * 7 + [vp] * 2 + [C.c_float] * 3
+                                          + [fp, fp, C.c_int] + [vp] * 9 + [vp, vp, vp, vp]),
+    "irrl_mlp_eval_rollout_supports": (C.c_int, [vp, C.c_int]),
     # one kick row per env on the pool now: device rows [N, 11] / host rows
     "irrl_env_perturb_base": (C.c_int, [vp, vp]),
     "irrl_env_perturb_base_host": (C.c_int, [vp, fp]),

@@ -99,6 +99,8 @@ ENV_FLAGS = ["-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=iterative-i
 ENV_FLAGS_W2 = ["-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"]
 # the persistent evaluation kernel's translation unit (env_kernels.hip: env_eval_kernels.hpp in both solver forms, nothing else), compiled with ENV_FLAGS
 EVAL_UNIT_FLAGS = ["-DIRRL_LANES_PER_ROBOT=16", "-DIRRL_EVAL_UNIT"]
+# ... and the one of its MlpPolicy twin (env_eval_mlp_kernels.hpp in both solver forms, nothing else), compiled with ENV_FLAGS
+EVAL_MLP_UNIT_FLAGS = ["-DIRRL_LANES_PER_ROBOT=16", "-DIRRL_EVAL_MLP_UNIT"]
 
 
 # the translation units that go through the plain compiler driver, in link order behind the env objects: the C-ABI + LSTM kernels and one unit
@@ -156,7 +158,7 @@ def source_hash(extra_flags=(), csrc=None, header=None):
         h.update(b"\0")
     with open(header or HEADER, "rb") as f:
         h.update(b"irrl_env.h\0" + f.read())
-    h.update(("\0".join(COMMON_FLAGS + ["|"] + ENV_FLAGS + ["|"] + ENV_FLAGS_W2 + ["|"] + EVAL_UNIT_FLAGS + ["|"] + list(extra_flags))).encode())
+    h.update(("\0".join(COMMON_FLAGS + ["|"] + ENV_FLAGS + ["|"] + ENV_FLAGS_W2 + ["|"] + EVAL_UNIT_FLAGS + ["|"] + EVAL_MLP_UNIT_FLAGS + ["|"] + list(extra_flags))).encode())
     return h.hexdigest()[:16]
 
 
@@ -188,12 +190,13 @@ def build(force=False, verbose=False, extra_flags=()):
     objdir = os.path.join(_HERE, "csrc", "_obj")
     os.makedirs(objdir, exist_ok=True)
     # the env kernels in both lane layouts (same source, different lane-primitive header; the 4-lane layout once more for two waves per
-    # SIMD; the 16-lane layout once more for the run-time-solver twins of the rollout kernels alone, and once more for the persistent evaluation
-    # kernel alone) through the ISA pass, then the C-ABI +
+    # SIMD; the 16-lane layout once more for the run-time-solver twins of the rollout kernels alone, and once each for the persistent evaluation
+    # kernels of the two policies alone) through the ISA pass, then the C-ABI +
     # LSTM kernels and the analyses of the recorders (PLAIN_UNITS, a translation unit each) through the plain driver
     units = [("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=16"] + ENV_FLAGS, "env_kernels_l16.o"),
              ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=16", "-DIRRL_ROLLOUT_RT_UNIT"] + ENV_FLAGS, "env_kernels_l16rt.o"),
              ("env_kernels.hip", EVAL_UNIT_FLAGS + ENV_FLAGS, "env_kernels_l16ev.o"),
+             ("env_kernels.hip", EVAL_MLP_UNIT_FLAGS + ENV_FLAGS, "env_kernels_l16evm.o"),
              ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=4"] + ENV_FLAGS, "env_kernels_l4.o"),
              ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=4", "-DIRRL_L4_WAVES2"] + ENV_FLAGS_W2, "env_kernels_l4w2.o")]
     units += [(src, ['-DIRRL_SRC_HASH="%s"' % want] if src == "irrl_env_abi.hip" else [], os.path.splitext(src)[0] + ".o") for src in PLAIN_UNITS]

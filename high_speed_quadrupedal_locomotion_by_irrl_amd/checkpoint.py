@@ -144,3 +144,75 @@ class NumpyLstmActor(object):
     def predict(self, obs):
         """CustomerLstmNN.predict (NN:112-135): one observation vector -> one action"""
         return self.act(obs)
+
+
+def mlp_checkpoint_layers(params):
+    """does a checkpoint's tensor list have MlpPolicy's shape?  -> (ob_dim, act_dim, layers) or None.  Decided from the arrays' shapes alone:
+    an MlpPolicy of the sizes the first arrays suggest is built and the list is held against its sb_parameters(), tensor by tensor."""
+    from .policies import MlpPolicy
+    shapes = [tuple(np.shape(p)) for p in params]
+    if len(shapes) < 12 or len(shapes) % 4 != 3 or len(shapes[0]) != 2 or len(shapes[1]) != 1:
+        return None
+    n_layers = (len(shapes) - 7) // 4
+    layers = tuple(shapes[4 * i][1] for i in range(n_layers) if len(shapes[4 * i]) == 2)
+    if len(layers) != n_layers or len(shapes[4 * n_layers + 2]) != 2:
+        return None
+    ob_dim, act_dim = shapes[0][0], shapes[4 * n_layers + 2][1]
+    want = [tuple(p.shape) for p in MlpPolicy(ob_dim=ob_dim, act_dim=act_dim, layers=layers).sb_parameters()]
+    squeeze = lambda sh: tuple(d for d in sh if d != 1)
+    if len(want) != len(shapes) or any(squeeze(a) != squeeze(b) for a, b in zip(want, shapes)):
+        return None
+    return ob_dim, act_dim, layers
+
+
+class NumpyMlpActor(object):
+    """numpy float64 forward of MlpPolicy's actor (two tanh layers and the action head) for one observation [ob_dim] or a batch [..., ob_dim]:
+    the float64 twin of the device loop's policy step, with NumpyLstmActor's interface -- act(ob, done=None), reset(), predict, clip -- so that
+    evaluate.reference_rollout takes either.  The policy has no recurrent state: reset() has nothing to clear and `done` changes nothing."""
+
+    def __init__(self, w, b, pi_w, pi_b, clip=True):
+        f64 = lambda a: np.asarray(a, np.float64)
+        self.w, self.b = [f64(a) for a in w], [f64(a).reshape(-1) for a in b]
+        self.pi_w, self.pi_b, self.clip = f64(pi_w), f64(pi_b).reshape(-1), clip
+
+    @classmethod
+    def from_parameter_list(cls, params, n_layers=2, clip=True):
+        """MlpPolicy.sb_parameters() order: pi_fc<i> w, b | vf_fc<i> w, b per layer; then vf w, b | pi w, b | logstd | q w, b"""
+        base = 4 * n_layers
+        return cls([params[4 * i] for i in range(n_layers)], [params[4 * i + 1] for i in range(n_layers)], params[base + 2], params[base + 3], clip)
+
+    @classmethod
+    def from_npz(cls, path, clip=True):
+        """the actor export of tools/export_actor_fixture.py for an MlpPolicy: pi_w<i>, pi_b<i> (i = 1, 2), pi_w, pi_b"""
+        z = np.load(path)
+        layers = range(1, 1 + sum(k.startswith("pi_w") and k != "pi_w" for k in z.files))
+        return cls([z["pi_w%d" % i] for i in layers], [z["pi_b%d" % i] for i in layers], z["pi_w"], z["pi_b"], clip)
+
+    def reset(self):
+        pass
+
+    def act(self, ob, done=None):
+        """one step on ob [..., ob_dim]; `done` is accepted for NumpyLstmActor's interface and not read.  -> float64 action [..., act_dim]"""
+        x = np.asarray(ob, np.float64)
+        # one vector-matrix product per row, so that a batch IS its rows, bit for bit (see NumpyLstmActor.act)
+        mul = lambda v, w: (v[..., None, :] @ w)[..., 0, :]
+        for w, b in zip(self.w, self.b):
+            x = np.tanh(mul(x, w) + b)
+        a = mul(x, self.pi_w) + self.pi_b
+        return np.clip(a, -1.0, 1.0) if self.clip else a
+
+    def predict(self, obs):
+        return self.act(obs)
+
+
+def numpy_actor(params_or_path, clip=True):
+    """the numpy actor a checkpoint's kind asks for: NumpyMlpActor where the tensor list (or the .npz export) is MlpPolicy's, else NumpyLstmActor"""
+    if isinstance(params_or_path, str):
+        mlp = "pi_w1" in np.load(params_or_path).files
+        return (NumpyMlpActor if mlp else NumpyLstmActor).from_npz(params_or_path, clip)
+    layers = mlp_checkpoint_layers(params_or_path)
+    if layers is not None:
+        return NumpyMlpActor.from_parameter_list(params_or_path, len(layers[2]), clip)
+    a = NumpyLstmActor.from_parameter_list(params_or_path)
+    a.clip = clip
+    return a

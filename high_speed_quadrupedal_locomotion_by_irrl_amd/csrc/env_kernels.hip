@@ -27,12 +27,12 @@
 #if IRRL_LANES_PER_ROBOT == 16
 #include "policy_step.hpp"   // the LSTM policy's rollout step (device code shared with lstm_kernels.hip)
 #endif
-#ifdef IRRL_EVAL_UNIT
+#if defined(IRRL_EVAL_UNIT) || defined(IRRL_EVAL_MLP_UNIT)
 #include "eval_elements.hpp"   // the evaluation loop's per-element arithmetic and its argument block (shared with eval_rollout.hpp)
 #endif
 #include "env_kernels_decl.h"   // every kernel below is declared there: the launcher (irrl_env_abi.hip) sees the same signatures
 
-// This file is compiled five times (build.py): once per lane layout, kernel names suffixed _l16 / _l4, and the 4-lane layout once more for
+// This file is compiled six times (build.py; three of them hold the rollout / evaluation kernels alone, see below): once per lane layout, kernel names suffixed _l16 / _l4, and the 4-lane layout once more for
 // TWO waves per SIMD (_l4w2, -DIRRL_L4_WAVES2: 256 registers per wave, ~130-220 of the step kernels' values in scratch).  Pools of more than
 // 16 384 robots are more 4-lane waves than the chip has SIMDs; two resident waves issue 1.35 x what one does (HISTORY.md Appendix C, 2a), which
 // pays for the spills: 32 768 envs 394 -> 450 M env-steps/s, 131 072 envs 394 -> 482 M, 16 384 envs (one wave per SIMD either way) 393 -> 386 M
@@ -157,6 +157,25 @@ extern "C" {
 #define IRRL_RK(name) name##_rt_l16
 #define IRRL_ROLLOUT_RULE 1
 #include "env_eval_kernels.hpp"
+#undef IRRL_RK
+#undef IRRL_ROLLOUT_RULE
+}  // extern "C"
+#elif defined(IRRL_EVAL_MLP_UNIT)
+// SIXTH COMPILATION (build.py, 16-lane layout): nothing but the persistent evaluation kernel with MlpPolicy as the actor (env_eval_mlp_kernels.hpp)
+// in its two solver forms -- irrl_eval_mlp_persistent_kernel_l16 and irrl_eval_mlp_persistent_kernel_rt_l16.  A unit of its own for the reason
+// above: mlp_policy_wave_body would get a second caller in whichever unit took this kernel in.
+#if IRRL_LANES_PER_ROBOT != 16
+#error "the evaluation kernel exists in the 16-lane layout only"
+#endif
+extern "C" {
+#define IRRL_RK(name) name##_l16
+#define IRRL_ROLLOUT_RULE IRRL_RULE_SHIPPED
+#include "env_eval_mlp_kernels.hpp"
+#undef IRRL_RK
+#undef IRRL_ROLLOUT_RULE
+#define IRRL_RK(name) name##_rt_l16
+#define IRRL_ROLLOUT_RULE 1
+#include "env_eval_mlp_kernels.hpp"
 #undef IRRL_RK
 #undef IRRL_ROLLOUT_RULE
 }  // extern "C"

@@ -51,3 +51,6 @@ IRRL_DECLARE_ROLLOUT_KERNELS(_rt_l16)
 #define IRRL_EVAL_KERNEL_ARGS EnvParams, EnvState, float *, float *, uint8_t *, float *, PolicyStepArgs, EvalArgs
 extern "C" __global__ void irrl_eval_persistent_kernel_l16(IRRL_EVAL_KERNEL_ARGS);
 extern "C" __global__ void irrl_eval_persistent_kernel_rt_l16(IRRL_EVAL_KERNEL_ARGS);
+// the same with MlpPolicy as the actor (csrc/env_eval_mlp_kernels.hpp, a translation unit of its own)
+extern "C" __global__ void irrl_eval_mlp_persistent_kernel_l16(IRRL_EVAL_KERNEL_ARGS);
+extern "C" __global__ void irrl_eval_mlp_persistent_kernel_rt_l16(IRRL_EVAL_KERNEL_ARGS);

@@ -496,7 +496,8 @@ int irrl_lstm_rollout(irrl_env *h, int steps, int hid, int ob_dim, int act_dim, 
 // plain launches back to back on `hip_stream`.  Stateless: everything that survives a call lives in the caller's buffers, so a second call with
 // step0 + steps continues where the first stopped.  Arguments are refused BEFORE any HIP call.
 // (the refusals of both forms of the loop, with the entry point's own name in the texts)
-static int eval_rollout_check(const char *who, irrl_env *h, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *lstm_w, const float *pi_w,
+// (lstm: the table has 12 entries, hid is 32 / 48 / 64 and the recurrent state is mandatory; !lstm: MlpPolicy's table of 8, hid 64, no state)
+static int eval_rollout_check(const char *who, bool lstm, irrl_env *h, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *lstm_w, const float *pi_w,
                               const float *pi_b, const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring, float *cmd, float *vel_his,
                               float *act_his, float *lstm_state, uint8_t *done, float *obs, float *work, const int *delay, const float *cmd_target, float a_cmd,
                               float a_vel, float a_act, const float *cmd_mean, const float *cmd_std) {
@@ -504,14 +505,15 @@ static int eval_rollout_check(const char *who, irrl_env *h, int steps, long long
   if (!h) { g_err = w + "NULL handle"; return 1; }
   if (steps < 0 || step0 < 0) { g_err = w + "steps >= 0, step0 >= 0"; return 1; }
   if (depth < 1) { g_err = w + "the delay line needs a depth D >= 1"; return 1; }
-  if (hid != 32 && hid != 48 && hid != 64) { g_err = w + "hid is 32, 48 or 64"; return 1; }
+  if (lstm && hid != 32 && hid != 48 && hid != 64) { g_err = w + "hid is 32, 48 or 64"; return 1; }
+  if (!lstm && hid != 64) { g_err = w + "hid is 64"; return 1; }
   if (ob_dim != 35 || act_dim != 12) { g_err = w + "ob 35, act 12"; return 1; }
-  if (!(ring && cmd && vel_his && act_his && lstm_state && done && obs && work && delay && cmd_target && cmd_mean && cmd_std)) {
+  if (!(ring && cmd && vel_his && act_his && (lstm_state || !lstm) && done && obs && work && delay && cmd_target && cmd_mean && cmd_std)) {
     g_err = w + "NULL evaluator state / parameter pointer"; return 1;
   }
   if (!(lstm_w && pi_w && pi_b && vf_w && vf_b && logstd)) { g_err = w + "NULL weight pointer"; return 1; }
-  for (int i = 0; i < 12; i++)
-    if (!lstm_w[i]) { g_err = w + "the LSTM weight table has a NULL entry"; return 1; }
+  for (int i = 0; i < (lstm ? 12 : 8); i++)
+    if (!lstm_w[i]) { g_err = w + (lstm ? "the LSTM weight table has a NULL entry" : "the weight table has a NULL entry"); return 1; }
   if (!(a_cmd > 0.0f && a_cmd <= 1.0f && a_vel > 0.0f && a_vel <= 1.0f && a_act > 0.0f && a_act <= 1.0f)) {
     g_err = w + "filter coefficients lie in (0, 1] (1 = off)"; return 1;
   }
@@ -606,9 +608,10 @@ static void eval_gait_args(EvalArgs &a, const irrl_env *h, const irrl_eval_gait 
   h, steps, step0, hid, ob_dim, act_dim, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, depth, ring, cmd, vel_his, act_his, lstm_state, done, obs, work, delay, \
       cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std, clip, rec_obs_cond, rec_act_clipped, rec_act_applied, rec_body, rec_torque, rec_obs_raw,       \
       rec_reward, rec_done, stats
-static int eval_rollout_steps(const char *who, IRRL_EVAL_PARAMS, const irrl_eval_scenario *sc, const irrl_eval_kicks *kk, const irrl_eval_gait *gg,
+// (lstm: the policy step is irrl_lstm_policy_step; else irrl_mlp_policy_step, lstm_w is its table of 8 and lstm_state is not read)
+static int eval_rollout_steps(const char *who, bool lstm, IRRL_EVAL_PARAMS, const irrl_eval_scenario *sc, const irrl_eval_kicks *kk, const irrl_eval_gait *gg,
                               void *hip_stream) {
-  if (eval_rollout_check(who, h, steps, step0, hid, ob_dim, act_dim, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, depth, ring, cmd, vel_his, act_his,
+  if (eval_rollout_check(who, lstm, h, steps, step0, hid, ob_dim, act_dim, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, depth, ring, cmd, vel_his, act_his,
                          lstm_state, done, obs, work, delay, cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std)) return 1;
   if (eval_scenario_check(who, sc)) return 1;
   if (eval_kicks_check(who, kk)) return 1;
@@ -628,10 +631,13 @@ static int eval_rollout_steps(const char *who, IRRL_EVAL_PARAMS, const irrl_eval
     a.row = k;
     a.t = step0 + k;
     hipLaunchKernelGGL(sc ? irrl_eval_condition_kernel<true> : irrl_eval_condition_kernel<false>, eval_grid(n * 35), dim3(256), 0, h->stream, a);
-    if (irrl_lstm_policy_step(hid, ob_dim, act_dim, n, w.obs_cond, done, lstm_state, lstm_state, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, nullptr, 0, 0u, 0, nullptr, 0,
-                              w.action, w.clipped, w.value, w.neglogp, -1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, hip_stream) != 0) {
-      g_err = std::string(who) + ": policy step refused its arguments"; return 1;
-    }
+    // the policy step: deterministic (noise NULL, rng off), no rollout rows; MlpPolicy's (lstm_w is then its table of 8) has no recurrent state
+    const int prc = lstm ? irrl_lstm_policy_step(hid, ob_dim, act_dim, n, w.obs_cond, done, lstm_state, lstm_state, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, nullptr, 0, 0u,
+                                                 0, nullptr, 0, w.action, w.clipped, w.value, w.neglogp, -1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                 hip_stream)
+                         : irrl_mlp_policy_step(hid, ob_dim, act_dim, n, w.obs_cond, done, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, nullptr, 0, 0u, 0, nullptr, 0, w.action,
+                                                w.clipped, w.value, w.neglogp, -1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, hip_stream);
+    if (prc != 0) { g_err = std::string(who) + ": policy step refused its arguments"; return 1; }
     hipLaunchKernelGGL(irrl_eval_action_kernel, eval_grid(n * 12), dim3(256), 0, h->stream, a);
     if (kk) {     // a step whose row fires: the kick, on the state the previous step (or the reset) left
       const int r = irrl_eval_kick_row(a, a.t);
@@ -646,16 +652,16 @@ static int eval_rollout_steps(const char *who, IRRL_EVAL_PARAMS, const irrl_eval
   return 0;
 }
 int irrl_lstm_eval_rollout(IRRL_EVAL_PARAMS, void *hip_stream) {
-  return eval_rollout_steps("irrl_lstm_eval_rollout", IRRL_EVAL_FORWARD, nullptr, nullptr, nullptr, hip_stream);
+  return eval_rollout_steps("irrl_lstm_eval_rollout", true, IRRL_EVAL_FORWARD, nullptr, nullptr, nullptr, hip_stream);
 }
 int irrl_lstm_eval_scenario(IRRL_EVAL_PARAMS, const irrl_eval_scenario *scenario, void *hip_stream) {
-  return eval_rollout_steps("irrl_lstm_eval_scenario", IRRL_EVAL_FORWARD, scenario, nullptr, nullptr, hip_stream);
+  return eval_rollout_steps("irrl_lstm_eval_scenario", true, IRRL_EVAL_FORWARD, scenario, nullptr, nullptr, hip_stream);
 }
 int irrl_lstm_eval_perturbed(IRRL_EVAL_PARAMS, const irrl_eval_scenario *scenario, const irrl_eval_kicks *kicks, void *hip_stream) {
-  return eval_rollout_steps("irrl_lstm_eval_perturbed", IRRL_EVAL_FORWARD, scenario, kicks, nullptr, hip_stream);
+  return eval_rollout_steps("irrl_lstm_eval_perturbed", true, IRRL_EVAL_FORWARD, scenario, kicks, nullptr, hip_stream);
 }
 int irrl_lstm_eval_measured(IRRL_EVAL_PARAMS, const irrl_eval_scenario *scenario, const irrl_eval_kicks *kicks, const irrl_eval_gait *gait, void *hip_stream) {
-  return eval_rollout_steps("irrl_lstm_eval_measured", IRRL_EVAL_FORWARD, scenario, kicks, gait, hip_stream);
+  return eval_rollout_steps("irrl_lstm_eval_measured", true, IRRL_EVAL_FORWARD, scenario, kicks, gait, hip_stream);
 }
 // one kick row per env on the pool now (the same kernel), stream-ordered on the pool's stream
 int irrl_env_perturb_base(irrl_env *h, const float *rows) {
@@ -692,7 +698,7 @@ int irrl_lstm_eval_rollout_supports(irrl_env *h, int hid) {
 }
 static int eval_rollout_one_launch(const char *who, IRRL_EVAL_PARAMS, const irrl_eval_scenario *sc, const irrl_eval_kicks *kk, const irrl_eval_gait *gg,
                               void *hip_stream) {
-  if (eval_rollout_check(who, h, steps, step0, hid, ob_dim, act_dim, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, depth, ring, cmd, vel_his, act_his, lstm_state, done,
+  if (eval_rollout_check(who, true, h, steps, step0, hid, ob_dim, act_dim, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, depth, ring, cmd, vel_his, act_his, lstm_state, done,
                          obs, work, delay, cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std)) return 1;
   if (eval_scenario_check(who, sc)) return 1;
   if (eval_kicks_check(who, kk)) return 1;
@@ -738,6 +744,61 @@ int irrl_lstm_eval_perturbed_persistent(IRRL_EVAL_PARAMS, const irrl_eval_scenar
 int irrl_lstm_eval_measured_persistent(IRRL_EVAL_PARAMS, const irrl_eval_scenario *scenario, const irrl_eval_kicks *kicks, const irrl_eval_gait *gait,
                                        void *hip_stream) {
   return eval_rollout_one_launch("irrl_lstm_eval_measured_persistent", IRRL_EVAL_FORWARD, scenario, kicks, gait, hip_stream);
+}
+
+// THE EVALUATION LOOP WITH MlpPolicy AS THE ACTOR (include/irrl_env.h): the per-step form is eval_rollout_steps with irrl_mlp_policy_step in the
+// policy step's place; the persistent form is ONE launch of irrl_eval_mlp_persistent_kernel (csrc/env_eval_mlp_kernels.hpp), which exists where the
+// persistent MlpPolicy rollout kernel does -- irrl_mlp_rollout_supports(h, 64, 2) -- and is refused elsewhere; there is no fallback inside the call.
+static const eval_kernel_t kEvalMlpKernels[2] = {irrl_eval_mlp_persistent_kernel_l16, irrl_eval_mlp_persistent_kernel_rt_l16};   // the order of kRolloutKernels
+#define IRRL_EVAL_MLP_PARAMS                                                                                                                          \
+  irrl_env *h, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *mlp_w, const float *pi_w, const float *pi_b,         \
+      const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring, float *cmd, float *vel_his, float *act_his,                  \
+      uint8_t *done, float *obs, float *work, const int *delay, const float *cmd_target, float a_cmd, float a_vel, float a_act, const float *cmd_mean,  \
+      const float *cmd_std, int clip, float *rec_obs_cond, float *rec_act_clipped, float *rec_act_applied, float *rec_body, float *rec_torque,         \
+      float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats
+int irrl_mlp_eval_rollout_supports(irrl_env *h, int hid) {
+  if (!h) { g_err = "irrl_mlp_eval_rollout_supports: NULL handle"; return -1; }
+  return (rollout_kernels(h) && hid == 64) ? 1 : 0;
+}
+int irrl_mlp_eval_measured(IRRL_EVAL_MLP_PARAMS, const irrl_eval_scenario *scenario, const irrl_eval_kicks *kicks, const irrl_eval_gait *gait, void *hip_stream) {
+  float *const lstm_state = nullptr;
+  const float *const *lstm_w = mlp_w;
+  return eval_rollout_steps("irrl_mlp_eval_measured", false, IRRL_EVAL_FORWARD, scenario, kicks, gait, hip_stream);
+}
+int irrl_mlp_eval_measured_persistent(IRRL_EVAL_MLP_PARAMS, const irrl_eval_scenario *sc, const irrl_eval_kicks *kk, const irrl_eval_gait *gg, void *hip_stream) {
+  const char *who = "irrl_mlp_eval_measured_persistent";
+  if (eval_rollout_check(who, false, h, steps, step0, hid, ob_dim, act_dim, mlp_w, pi_w, pi_b, vf_w, vf_b, logstd, depth, ring, cmd, vel_his, act_his, nullptr, done,
+                         obs, work, delay, cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std)) return 1;
+  if (eval_scenario_check(who, sc)) return 1;
+  if (eval_kicks_check(who, kk)) return 1;
+  if (eval_gait_check(who, gg)) return 1;
+  if (need_init(h)) return 1;
+  // which condition keeps the kernel from this pool (settings only: nothing is launched)
+  if (h->lanes != 16) { g_err = std::string(who) + ": the persistent kernel exists in the 16-lane layout only (this pool runs 4 lanes per robot)"; return 1; }
+  const RolloutKernels *rk = rollout_kernel_set(h);
+  if (!rk) {
+    g_err = std::string(who) + ": the persistent kernel exists for the kernel variants shipped_flat / shipped / md only (this pool runs '" +
+            kVariantNames[step_variant(h)] + "': Crutial pools and ContactSolver without the published rule keep irrl_mlp_eval_measured)";
+    return 1;
+  }
+  if (steps == 0) return 0;
+  HIP_TRY(hipSetDevice(h->device));
+  h->stream = (hipStream_t)hip_stream;
+  const int n = h->P.n_envs;
+  const EvalWork w = eval_work(work, (size_t)n);
+  EvalArgs a = eval_args(h, w, depth, ring, cmd, vel_his, act_his, done, obs, delay, cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std, clip, rec_obs_cond,
+                         rec_act_clipped, rec_act_applied, rec_body, rec_torque, rec_obs_raw, rec_reward, rec_done, stats);
+  eval_scenario_args(a, sc, step0);
+  eval_kicks_args(a, kk);
+  eval_gait_args(a, h, gg);
+  a.slot = (int)(step0 % depth);
+  a.steps = steps;
+  // both networks, deterministic, no rollout rows: action | clipped | value | neglogp are written as irrl_mlp_policy_step writes them
+  const PolicyStepArgs pa = policy_step_args(n, ob_dim, act_dim, obs, done, nullptr, nullptr, mlp_w, 8, pi_w, pi_b, vf_w, vf_b, logstd, nullptr, 0, 0u, 0, nullptr, 0,
+                                             w.action, w.clipped, w.value, w.neglogp, -1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  hipLaunchKernelGGL(kEvalMlpKernels[rk == &kRolloutKernels[0] ? 0 : 1], dim3((n + 15) / 16), dim3(256), 0, h->stream, h->P, h->S, obs, w.reward, done, w.extra, pa, a);
+  HIP_TRY(hipGetLastError());
+  return 0;
 }
 
 // irrl_mlp_rollout_supports: which `fuse` modes exist for this pool (the twin of irrl_lstm_rollout_supports; fuse 2 falls back inside the call)

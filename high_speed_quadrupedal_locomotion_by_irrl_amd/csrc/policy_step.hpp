@@ -255,7 +255,8 @@ LSTM_DEV void policy_heads_wave(const PolicyStepArgs &a, float *ws, const float 
   }
 }
 
-template <int H, bool LDSW, bool XLDS = false>
+// RAW_ACT: policy_heads_wave's switch (the unclipped action in the scratch: the persistent MlpPolicy evaluation kernel)
+template <int H, bool LDSW, bool XLDS = false, bool RAW_ACT = false>
 LSTM_DEV void mlp_policy_wave_body(const PolicyStepArgs &a, const int e4, float *ws, const float *wl, const float *head_w, const int l) {
   static_assert(H == 64, "one lane per hidden unit");
   constexpr int LD = MlpWaveLds<H>::LD;
@@ -319,7 +320,7 @@ LSTM_DEV void mlp_policy_wave_body(const PolicyStepArgs &a, const int e4, float 
 #pragma unroll
   for (int r = 0; r < 4; r++) { h2[r * LD + l] = fast_tanh(ap[r]); h2[4 * LD + r * LD + l] = fast_tanh(av[r]); }
   PS_WAVE_SYNC();
-  policy_heads_wave<H, XLDS, MlpWaveLds<H>>(a, ws, h2, h2 + 4 * LD, LD, LDSW ? head_w : a.pi_w, LDSW ? head_w + H * a.act_dim : a.vf_w, terms, e4, l, t, gstep);
+  policy_heads_wave<H, XLDS, MlpWaveLds<H>, false, RAW_ACT>(a, ws, h2, h2 + 4 * LD, LD, LDSW ? head_w : a.pi_w, LDSW ? head_w + H * a.act_dim : a.vf_w, terms, e4, l, t, gstep);
 }
 #ifdef IRRL_PROFILE_POLICY   /* diagnostic build (tools/policy_phases.py): 100 MHz time stamps of the phases of one workgroup */
 #define IRRL_PS_STAMP() do { __builtin_amdgcn_sched_barrier(0); ts_[tsn_++] = wall_clock64(); __builtin_amdgcn_sched_barrier(0); } while (0)

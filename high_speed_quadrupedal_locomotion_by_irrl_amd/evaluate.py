@@ -3,7 +3,8 @@ rate / action low-passes, command ramp) without a host round trip per control st
 
   PolicyEvaluator     the evaluation loop on the GPU (C-ABI irrl_lstm_eval_rollout, kernels csrc/eval_rollout.hpp: five launches per control
                       step; irrl_lstm_eval_rollout_persistent, csrc/env_eval_kernels.hpp: the whole run as one persistent launch, bit-identical):
-                      per-env delay and command, recorders, per-env f64 statistics
+                      per-env delay and command, recorders, per-env f64 statistics.  The actor is a CustomLSTMPolicy or an MlpPolicy (64, 64)
+                      (irrl_mlp_eval_measured[_persistent], csrc/env_eval_mlp_kernels.hpp: the same two forms)
   condition           numpy float64 twin of the loop's observation conditioning (command low-pass, delay line, rate low-pass, command overwrite)
   reference_rollout   numpy float64 twin of the whole loop around any env adapter with reset / step / get_state / set_contact_coeff: THE host-driven
                       evaluation loop (the test harnesses and tools translate their cases into one call of it)
@@ -54,6 +55,13 @@ WORK_DIM = 80            # IRRL_EVAL_WORK_DIM
 # launch where it exists -- measured faster at both pool sizes, 36.5 against 58.5 us per control step at 4096 envs and 36.0 against 55.1 us at 90
 # 
 PERSISTENT_DEFAULT = "auto"
+
+
+def mlp_auto_persistent(n):
+    """does persistent="auto" take the persistent launch for an MlpPolicy on a pool of n robots?  Only at the pool sizes where its median time per
+    control step measured below the per-step form's: it did at both sizes measured, 30.1 against 49.0 us at 4096 robots and 30.2 against 45.7 us
+    at 90 (MI355X, profiles/eval_mlp_mi355x.log), so every size takes it."""
+    return True
 RECORDERS = {"obs_cond": 35, "act_clipped": 12, "act_applied": 12, "body": 13, "torque": 12, "obs_raw": 35, "reward": 0, "done": 0}   # C argument order
 
 
@@ -1521,7 +1529,9 @@ def resolve_persistent(persistent, supported):
 class PolicyEvaluator(object):
     """PolicyEvaluator(env_impl, policy, delay, cmd, cmd_hz=1.0, vel_hz=None, act_hz=None, clip=True)
 
-    env_impl: an initialised FlexibleGymEnv (Manual mode: the evaluator owns obs[0:3]); policy: a CustomLSTMPolicy on the pool's device;
+    env_impl: an initialised FlexibleGymEnv (Manual mode: the evaluator owns obs[0:3]); policy: a CustomLSTMPolicy or an MlpPolicy with
+    layers (64, 64) on the pool's device (the latter has no recurrent state: `lstm_state` is None, and the loop runs through the C-ABI's
+    irrl_mlp_eval_measured[_persistent], the one pair of entry points that exists for it);
     delay [N] control steps and cmd [N] (v_x) or [N, 3] per env; depth: length of the delay line (default max(delay) + 1).
     Friction goes through env_impl.SetContactCoefficient between `run` calls (a warm-up on another material = two calls)."""
 
@@ -1530,9 +1540,21 @@ class PolicyEvaluator(object):
         self.env, self.policy = env_impl, policy
         self.n = n = env_impl.getNumOfEnvs()
         self.dev = dev = torch.device("cuda", env_impl.device_index)
-        self.hid = int(policy.n_lstm[0])
-        if len(policy.n_lstm) != 2 or policy.n_lstm[0] != policy.n_lstm[1] or self.hid not in (32, 48, 64) or policy.act_dim != 12:
-            raise ValueError("PolicyEvaluator runs CustomLSTMPolicy with two equal LSTM layers of 32, 48 or 64 units and 12 actions")
+        from .policies import CustomLSTMPolicy, MlpPolicy
+        self.is_mlp = isinstance(policy, MlpPolicy)
+        if self.is_mlp:
+            layers = tuple(int(l.w.shape[1]) for l in policy.pi_fc)
+            if (layers != (64, 64) or tuple(int(l.w.shape[1]) for l in policy.vf_fc) != layers or int(policy.pi_fc[0].w.shape[0]) != 35
+                    or policy.act_dim != 12):
+                raise ValueError("PolicyEvaluator runs MlpPolicy with layers (64, 64), 35 observations and 12 actions")
+            self.hid = 64
+        elif isinstance(policy, CustomLSTMPolicy):
+            self.hid = int(policy.n_lstm[0])
+            if len(policy.n_lstm) != 2 or policy.n_lstm[0] != policy.n_lstm[1] or self.hid not in (32, 48, 64) or policy.act_dim != 12:
+                raise ValueError("PolicyEvaluator runs CustomLSTMPolicy with two equal LSTM layers of 32, 48 or 64 units and 12 actions")
+        else:
+            raise ValueError("PolicyEvaluator runs CustomLSTMPolicy (two equal LSTM layers of 32, 48 or 64 units) or MlpPolicy (layers (64, 64)), "
+                             "not %s" % type(policy).__name__)
         delay, self.depth = _delay_rows(delay, n, depth)
         cfg = {k: env_impl.cfg_value(k) for k in ("abad", "Vx", "Vy", "Omega", "control_dt")}
         mean, std, _, _ = obs_normalisation(cfg)
@@ -1547,7 +1569,7 @@ class PolicyEvaluator(object):
         self.cmd = torch.zeros(n, 3, **f32)
         self.vel_his = torch.zeros(n, 35, **f32)
         self.act_his = torch.zeros(n, 12, **f32)
-        self.lstm_state = torch.zeros(n, 8 * self.hid, **f32)
+        self.lstm_state = None if self.is_mlp else torch.zeros(n, 8 * self.hid, **f32)     # MlpPolicy has no recurrent state
         self.done = torch.zeros(n, dtype=torch.bool, device=dev)
         self.obs = torch.zeros(n, 35, **f32)
         self.work = torch.zeros(n, WORK_DIM, **f32)
@@ -1561,7 +1583,7 @@ class PolicyEvaluator(object):
         # which C entry points `run` calls: "auto" = the narrowest list that takes what is installed (irrl_lstm_eval_rollout / _scenario /
         # _perturbed / _measured); "perturbed" = always the kick table's, "measured" = always the gait measurements', with NULL for what is not
         # installed -- the same code path by construction (the narrower entry points are calls of the wider ones with NULL), which is what the
-        # tests hold them to
+        # tests hold them to.  MlpPolicy has the widest pair only (irrl_mlp_eval_measured[_persistent]): "auto" and "measured" are that pair
         self.entry_points = "auto"
         self.t = 0
         self.reset()
@@ -1573,7 +1595,8 @@ class PolicyEvaluator(object):
         self.env.reset(self.obs)
         self.ring.copy_(self.obs.unsqueeze(0).expand_as(self.ring))
         for b in (self.cmd, self.vel_his, self.act_his, self.lstm_state, self.heading_int):
-            b.zero_()
+            if b is not None:
+                b.zero_()
         self.done.zero_()
         self.prev_contact.zero_()
         self.t = 0
@@ -1638,13 +1661,22 @@ class PolicyEvaluator(object):
 
     @property
     def persistent_supported(self):
-        """does the persistent single-launch kernel exist for this pool and policy (16-lane layout, 48 units, kernel variant shipped_flat /
-        shipped / md)?"""
+        """does the persistent single-launch kernel exist for this pool and policy (16-lane layout, kernel variant shipped_flat / shipped / md;
+        CustomLSTMPolicy of 48 units or MlpPolicy)?"""
         from . import _lib
-        rc = _lib.load().irrl_lstm_eval_rollout_supports(self.env._h, self.hid)
+        lib = _lib.load()
+        rc = (lib.irrl_mlp_eval_rollout_supports if self.is_mlp else lib.irrl_lstm_eval_rollout_supports)(self.env._h, self.hid)
         if rc < 0:
             raise RuntimeError(_lib.last_error())
         return rc == 1
+
+    @property
+    def auto_persistent(self):
+        """what persistent="auto" resolves to: the persistent launch where it exists and is the measured-faster form.  For CustomLSTMPolicy that
+        is wherever it exists; for MlpPolicy see mlp_auto_persistent."""
+        if not self.persistent_supported:
+            return False
+        return mlp_auto_persistent(self.n) if self.is_mlp else True
 
     def run(self, steps, record=(), accumulate=True, persistent=False):
         """`steps` control steps from ONE C call (stream-ordered on torch's current stream, no synchronisation).  record: names out of
@@ -1652,11 +1684,13 @@ class PolicyEvaluator(object):
         persistent: False = five launches per control step (every pool and policy; also steps the critic's half of lstm_state); True = the
         whole call as one persistent launch (raises with the library's text where the kernel does not exist); "auto" = the persistent launch
         where `persistent_supported`, else five launches per step.  The two forms leave bit-identical buffers -- except the critic's half of
-        lstm_state and the `value` column of the work array, which the persistent form does not touch -- and may follow each other."""
+        lstm_state and the `value` column of the work array, which the persistent form does not touch -- and may follow each other.
+        With an MlpPolicy both forms run both networks and every buffer is bit-identical, the whole work array included; "auto" is
+        resolved by `auto_persistent`."""
         import torch
         from . import _lib
         from ._lib import ptr
-        from .lstm_fused import _head_ptrs, _lstm_weight_table
+        from .lstm_fused import _head_ptrs, _lstm_weight_table, _mlp_weight_table
         steps = int(steps)
         unknown = [k for k in record if k not in RECORDERS and k != "gait"]
         if unknown:
@@ -1666,10 +1700,15 @@ class PolicyEvaluator(object):
             shape = (steps, self.n) + ((GAIT_REC_DIM,) if k == "gait" else (RECORDERS[k],) if RECORDERS[k] else ())
             out[k] = torch.empty(shape, device=self.dev, dtype=torch.bool if k == "done" else torch.float32)
         with torch.cuda.device(self.dev):
-            self.policy.prepare()                              # the kernels' permuted weight copies follow the parameters (a learner may have stepped)
-            warr = _lstm_weight_table(self.policy, self.dev)
+            if self.is_mlp:
+                warr = _mlp_weight_table(self.policy)
+            else:
+                self.policy.prepare()                          # the kernels' permuted weight copies follow the parameters (a learner may have stepped)
+                warr = _lstm_weight_table(self.policy, self.dev)
             lib = _lib.load()
-            one_launch = resolve_persistent(persistent, lambda: self.persistent_supported)
+            one_launch = resolve_persistent(persistent, lambda: self.auto_persistent)
+            if self.is_mlp and self.entry_points not in ("auto", "measured"):
+                raise ValueError("entry_points is 'auto' or 'measured' for an MlpPolicy (only the widest pair of entry points exists for it)")
             if self.entry_points not in ("auto", "perturbed", "measured"):
                 raise ValueError("entry_points is 'auto', 'perturbed' or 'measured'")
             has_kicks = self.scenario is not None and self.scenario["kicks"] is not None
@@ -1683,7 +1722,10 @@ class PolicyEvaluator(object):
                 gstruct = _lib.EvalGait(gait=ptr(self.gait).value if (self.gait is not None and accumulate) else None,
                                         prev_contact=ptr(self.prev_contact).value if self.gait is not None else None,
                                         rec_gait=ptr(out["gait"]).value if "gait" in out else None)
-            if gstruct is not None or self.entry_points == "measured":
+            if self.is_mlp:
+                fn = lib.irrl_mlp_eval_measured_persistent if one_launch else lib.irrl_mlp_eval_measured
+                scenario = (raw(struct), raw(kstruct), raw(gstruct))
+            elif gstruct is not None or self.entry_points == "measured":
                 fn = lib.irrl_lstm_eval_measured_persistent if one_launch else lib.irrl_lstm_eval_measured
                 scenario = (raw(struct), raw(kstruct), raw(gstruct))
             elif has_kicks or self.entry_points == "perturbed":  # the kick table's struct behind the scenario's
@@ -1694,7 +1736,7 @@ class PolicyEvaluator(object):
                 fn, scenario = (lib.irrl_lstm_eval_rollout_persistent if one_launch else lib.irrl_lstm_eval_rollout), ()
             _lib.check(fn(
                 self.env._h, steps, self.t, self.hid, 35, 12, warr, *_head_ptrs(self.policy), self.depth, ptr(self.ring), ptr(self.cmd), ptr(self.vel_his),
-                ptr(self.act_his), ptr(self.lstm_state), ptr(self.done), ptr(self.obs), ptr(self.work), ptr(self.delay), ptr(self.cmd_target),
+                ptr(self.act_his), *(() if self.is_mlp else (ptr(self.lstm_state),)), ptr(self.done), ptr(self.obs), ptr(self.work), ptr(self.delay), ptr(self.cmd_target),
                 self.a_cmd, self.a_vel, self.a_act, self.cmd_mean, self.cmd_std, int(self.clip), *[ptr(out.get(k)) for k in RECORDERS],
                 ptr(self.stats) if accumulate else None, *scenario, _lib.stream_ptr(self.dev)))
         self.t += steps
@@ -1748,31 +1790,45 @@ class PolicyEvaluator(object):
 
 
 def load_policy(model_or_policy, device):
-    """a CustomLSTMPolicy on `device` from: the policy itself, a model that has `.policy` (PPO2), the path of a checkpoint (this build's or a
-    stable-baselines pickle of the reference), or the path of an actor export `actor_*.npz` (tools/export_actor_fixture.py: two LSTM layers and
-    the action head; the critic, which the evaluation does not read, keeps the initialisation of torch.manual_seed(3))"""
+    """a CustomLSTMPolicy or an MlpPolicy on `device` from: the policy itself, a model that has `.policy` (PPO2), the path of a checkpoint (this
+    build's or a stable-baselines pickle of the reference; which of the two policies it holds is decided from the shapes of its tensor list,
+    through MlpPolicy.sb_parameters()), or the path of an actor export `actor_*.npz` (tools/export_actor_fixture.py: two LSTM layers and the action
+    head, keys wx0 ...; or MlpPolicy's actor, keys pi_w1, pi_b1, pi_w2, pi_b2, pi_w, pi_b; the critic, which the evaluation's records do not
+    depend on, keeps the initialisation of torch.manual_seed(3))"""
     import torch
-    from .policies import CustomLSTMPolicy
+    from .policies import CustomLSTMPolicy, MlpPolicy
     pol = getattr(model_or_policy, "policy", model_or_policy)
     if isinstance(pol, str):
         if pol.endswith(".npz"):
             z = np.load(pol)
             torch.manual_seed(3)
-            pol = CustomLSTMPolicy(ob_dim=z["wx0"].shape[0], act_dim=z["pi_w"].shape[1], n_lstm=(z["wh0"].shape[0], z["wh1"].shape[0]))
-            ps = [p for l in pol.lstm_pi for p in (l.wx, l.wh, l.b)] + [pol.pi.w, pol.pi.b]
-            params = [z[k] for k in ("wx0", "wh0", "b0", "wx1", "wh1", "b1", "pi_w", "pi_b")]
+            if "pi_w1" in z.files:
+                pol = MlpPolicy(ob_dim=z["pi_w1"].shape[0], act_dim=z["pi_w"].shape[1], layers=(z["pi_w1"].shape[1], z["pi_w2"].shape[1]))
+                ps = [p for l in pol.pi_fc for p in (l.w, l.b)] + [pol.pi.w, pol.pi.b]
+                params = [z[k] for k in ("pi_w1", "pi_b1", "pi_w2", "pi_b2", "pi_w", "pi_b")]
+            else:
+                pol = CustomLSTMPolicy(ob_dim=z["wx0"].shape[0], act_dim=z["pi_w"].shape[1], n_lstm=(z["wh0"].shape[0], z["wh1"].shape[0]))
+                ps = [p for l in pol.lstm_pi for p in (l.wx, l.wh, l.b)] + [pol.pi.w, pol.pi.b]
+                params = [z[k] for k in ("wx0", "wh0", "b0", "wx1", "wh1", "b1", "pi_w", "pi_b")]
         else:
-            from .checkpoint import read_checkpoint
+            from .checkpoint import mlp_checkpoint_layers, read_checkpoint
             _, params = read_checkpoint(pol)
-            pol = CustomLSTMPolicy(ob_dim=params[0].shape[0], act_dim=params[14].shape[1], n_lstm=(params[1].shape[0], params[4].shape[0]))
-            ps = pol.sb_parameters()
-            if len(ps) != len(params):
-                raise ValueError("checkpoint holds %d tensors, CustomLSTMPolicy has %d" % (len(params), len(ps)))
+            layers = mlp_checkpoint_layers(params)
+            if layers is not None:
+                ob_dim, act_dim, layers = layers
+                pol = MlpPolicy(ob_dim=ob_dim, act_dim=act_dim, layers=layers)
+                ps = pol.sb_parameters()
+            else:
+                pol = CustomLSTMPolicy(ob_dim=params[0].shape[0], act_dim=params[14].shape[1], n_lstm=(params[1].shape[0], params[4].shape[0]))
+                ps = pol.sb_parameters()
+                if len(ps) != len(params):
+                    raise ValueError("checkpoint holds %d tensors, CustomLSTMPolicy has %d" % (len(params), len(ps)))
         with torch.no_grad():
             for p, a in zip(ps, params):
                 p.copy_(torch.as_tensor(np.asarray(a), dtype=p.dtype).reshape(p.shape))
     pol = pol.to(device)
-    pol.prepare()
+    if hasattr(pol, "prepare"):
+        pol.prepare()
     return pol
 
 

@@ -606,6 +606,42 @@ int irrl_lstm_eval_measured_persistent(irrl_env *env, int steps, long long step0
                                        float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats, const irrl_eval_scenario *scenario,
                                        const irrl_eval_kicks *kicks, const irrl_eval_gait *gait, void *hip_stream);
 
+/* THE EVALUATION LOOP WITH MlpPolicy AS THE ACTOR (policies.py MlpPolicy: separate pi / vf nets of two tanh layers of 64 units): the loop above,
+ * steps 1-13, with irrl_mlp_policy_step in step 7's place.  ONE widest pair of entry points: the argument list is irrl_lstm_eval_measured's with
+ * mlp_w (HOST array of 8 device pointers, as irrl_mlp_policy_step takes it) where lstm_w is, and WITHOUT lstm_state -- the policy has no recurrent
+ * state; `done` still drives cmd = 0 (step 13) and the heading integrator.  hid must be 64, ob_dim 35, act_dim 12.  scenario, kicks and gait may
+ * each be NULL = none, exactly as the irrl_lstm_eval_* entry points treat them; evaluator state, parameters, recorders, stats and the three
+ * structs are theirs, unchanged.  The policy runs deterministically: no noise, rng off, no rollout rows.
+ *   irrl_mlp_eval_measured              `steps` control steps as plain launches back to back (five per step, a sixth at a kick step); every pool
+ *                                       kind, kernel variant and lane layout.
+ *   irrl_mlp_eval_measured_persistent   the same call as ONE persistent launch (kernel csrc/env_eval_mlp_kernels.hpp): a wave keeps its four robots
+ *                                       -- lane context in registers; weights, filter histories, command, statistics and gait accumulators in LDS
+ *                                       -- for all `steps` control steps.
+ * WHAT BOTH FORMS WRITE, BIT-IDENTICALLY: every recorder (rec_gait included), stats, gait, prev_contact, heading_int, ring, cmd, vel_his, act_his,
+ * done, obs, the pool, and EVERY column of the work array the per-step form writes: obs_cond | action | clipped | applied | value | neglogp | reward |
+ * extra.  The persistent kernel runs both networks (the per-wave body of irrl_mlp_policy_step's kernel), so -- unlike the LSTM pair -- `value` and
+ * `neglogp` are written by both forms; no column stays untouched.  Calls of either form may follow each other on the same buffers.
+ * irrl_mlp_eval_rollout_supports: 1 = the persistent kernel exists for this pool and a network of `hid` units -- exactly where
+ * irrl_mlp_rollout_supports(env, 64, 2) is 1: 16 lanes per robot, kernel variant shipped_flat / shipped / md, hid 64 --, 0 = it does not,
+ * -1 = NULL handle (irrl_last_error() set).
+ * Errors (non-zero, irrl_last_error() set with the entry point's own name, checked before any HIP call): the refusals of irrl_lstm_eval_measured
+ * with "hid is 64" for any other hid and an 8-entry weight table; irrl_mlp_eval_measured_persistent also refuses a pool without the kernel with a
+ * text that names the failed condition: there is NO fallback inside the call.  steps == 0 returns 0 and launches nothing. */
+int irrl_mlp_eval_rollout_supports(irrl_env *env, int hid);
+int irrl_mlp_eval_measured(irrl_env *env, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *mlp_w, const float *pi_w,
+                           const float *pi_b, const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring, float *cmd, float *vel_his,
+                           float *act_his, uint8_t *done, float *obs, float *work, const int *delay, const float *cmd_target, float a_cmd, float a_vel,
+                           float a_act, const float *cmd_mean, const float *cmd_std, int clip, float *rec_obs_cond, float *rec_act_clipped,
+                           float *rec_act_applied, float *rec_body, float *rec_torque, float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats,
+                           const irrl_eval_scenario *scenario, const irrl_eval_kicks *kicks, const irrl_eval_gait *gait, void *hip_stream);
+int irrl_mlp_eval_measured_persistent(irrl_env *env, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *mlp_w,
+                                      const float *pi_w, const float *pi_b, const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring,
+                                      float *cmd, float *vel_his, float *act_his, uint8_t *done, float *obs, float *work, const int *delay,
+                                      const float *cmd_target, float a_cmd, float a_vel, float a_act, const float *cmd_mean, const float *cmd_std, int clip,
+                                      float *rec_obs_cond, float *rec_act_clipped, float *rec_act_applied, float *rec_body, float *rec_torque,
+                                      float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats, const irrl_eval_scenario *scenario,
+                                      const irrl_eval_kicks *kicks, const irrl_eval_gait *gait, void *hip_stream);
+
 /* ENSEMBLE ANALYSIS OF A BODY RECORDER: state-space entropy, cell counts, per-feature histograms and moments per (condition, frame) -- what the
  * reference's figure scripts do with a perturbation exploration (Data_Visualization_Code/Figure3.py:145-151 and Figure4.py:160-166 `entropy`,
  * Figure3.py:213-230 the time x value densities).  rec_body is the recorder of the evaluation loop, device f32 [rows, num_envs, 13] (base x y z,

@@ -159,10 +159,11 @@ def plain(v):
 
 def run_test(args, cfg):
     """Headless evaluation loop (run_bp_v5.py:300-470 without gamepad, window and plots).  One Manual-mode env on the
-    numpy boundary (testStep-style single env), the trained actor as a numpy LSTM (CustomerLstmNN twin)."""
+    numpy boundary (testStep-style single env), the trained actor as a numpy LSTM (CustomerLstmNN twin) or, for an MlpPolicy checkpoint, its
+    numpy MLP twin -- picked by the checkpoint's kind."""
     import numpy as np
     from flex_gym.env.RaisimGymVecEnv import RaisimGymVecEnv
-    from high_speed_quadrupedal_locomotion_by_irrl_amd.checkpoint import NumpyLstmActor, read_checkpoint
+    from high_speed_quadrupedal_locomotion_by_irrl_amd.checkpoint import numpy_actor, read_checkpoint
     from high_speed_quadrupedal_locomotion_by_irrl_amd.evaluate import (condition, condition_state, contact_material, heading_hold, heading_parameters,
                                                                         lowpass_alpha, staircase_schedule, yaw_from_quaternion)
     from high_speed_quadrupedal_locomotion_by_irrl_amd.helper import obs_normalisation
@@ -175,7 +176,7 @@ def run_test(args, cfg):
         ecfg["Manual"] = True
     env = RaisimGymVecEnv(FlexibleGymEnv(__RSCDIR__, yaml.safe_dump(ecfg)))
     _, params = read_checkpoint(args.trained_model)
-    ctrl = NumpyLstmActor.from_parameter_list(params, n_layers=len(N_LSTM))
+    ctrl = numpy_actor(params)
     obs_mean, obs_std, action_mean, action_std = obs_normalisation(ecfg)
     dt = float(ecfg["control_dt"])
     # the default 1e6 Hz of --vel_filter_freq / --act_filter_freq goes THROUGH the filters here (alpha ~ 0.99992) as in the reference's loop,

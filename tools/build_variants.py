@@ -29,7 +29,7 @@ for spec in sys.argv[1:]:
     common = list(B.COMMON_FLAGS) + flags
     for src, fl, obj in (("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=16"] + B_ENV, "l16"),
                          ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=16", "-DIRRL_ROLLOUT_RT_UNIT"] + B_ENV, "l16rt"),
-                         ("env_kernels.hip", list(B.EVAL_UNIT_FLAGS) + B_ENV, "l16ev"), ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=4"] + B_ENV, "l4"),
+                         ("env_kernels.hip", list(B.EVAL_UNIT_FLAGS) + B_ENV, "l16ev"), ("env_kernels.hip", list(B.EVAL_MLP_UNIT_FLAGS) + B_ENV, "l16evm"), ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=4"] + B_ENV, "l4"),
                          ("env_kernels.hip", ["-DIRRL_LANES_PER_ROBOT=4", "-DIRRL_L4_WAVES2"] + (B_ENV if swapped else list(B.ENV_FLAGS_W2)), "l4w2"),
                          ) + tuple((u, [], os.path.splitext(u)[0]) for u in B.PLAIN_UNITS):      # (the plain-driver units of build.build())
         o = os.path.join(out, f"{name}_{obj}.o")

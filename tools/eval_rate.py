@@ -19,6 +19,12 @@ kicks, so only roughly comparable with it.
 
 --gait (with --ab): every leg measures joint power, torque and ground-force sums and the footfall pattern too (PolicyEvaluator.measure_gait) through
 irrl_lstm_eval_measured[_persistent]; the same trajectory as the run without, so the difference is the measurements' cost.
+
+--policy mlp: the actor is an MlpPolicy (layers (64, 64); torch.manual_seed(0) initialisation, no trained fixture is needed for a time per step)
+through irrl_mlp_eval_measured[_persistent].  With --events the time per control step comes from events on the stream around `--steps` steps
+behind a `--warmup`-step warm-up of the same form, the two forms alternating, `--runs` runs each, medians:
+
+    python tools/eval_rate.py --events --policy mlp [--envs 4096 | --envs 90] [--steps 2000] [--warmup 200] [--runs 5]
 """
 import argparse
 import json
@@ -75,8 +81,37 @@ def ab(args, env, pol, delays, cmds, out):
     print(json.dumps(out))
 
 
+def events(args, env, pol, delays, cmds, out):
+    """per-step form, persistent form, per-step form ... on one pool, `runs` runs each: a fresh evaluator (reset), `warmup` steps of the run's own
+    form, then `steps` steps between two events on the stream.  Statistics on, no recorders.  Medians."""
+    times = {False: [], True: []}
+    for _ in range(args.runs):
+        for persistent in (False, True):
+            ev = EV.PolicyEvaluator(env, pol, delays, cmds, cmd_hz=1.0, vel_hz=50.0, act_hz=30.0)
+            ev.run(args.warmup, persistent=persistent)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            ev.run(args.steps, persistent=persistent)
+            e1.record()
+            e1.synchronize()
+            us = 1e3 * e0.elapsed_time(e1) / args.steps
+            times[persistent].append(us)
+            print("%-10s: %d envs x %d steps, %.2f us per control step, falls %d"
+                  % ("persistent" if persistent else "per-step", args.envs, args.steps, us, int(ev.statistics()["falls"].sum())), flush=True)
+    a, b = float(np.median(times[False])), float(np.median(times[True]))
+    out.update(policy=args.policy, steps=args.steps, warmup=args.warmup, per_step_us=times[False], persistent_us=times[True], per_step_median_us=a,
+               persistent_median_us=b, persistent_over_per_step=b / a)
+    print("%s policy, %d envs: per-step form %.2f us, persistent form %.2f us per control step (medians of %d), ratio %.3f"
+          % (args.policy, args.envs, a, b, args.runs, b / a))
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--policy", choices=("lstm", "mlp"), default="lstm", help="the actor: the LSTM fixture, or an MlpPolicy (64, 64) as initialised under seed 0")
+    ap.add_argument("--events", action="store_true", help="per-step form against persistent form, alternating, timed by stream events; medians of --runs")
+    ap.add_argument("--warmup", type=int, default=200, help="--events: control steps of each run's own form in front of the timed ones")
+    ap.add_argument("--runs", type=int, default=5, help="--events: runs per form")
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--host-steps", type=int, default=200)
@@ -90,11 +125,18 @@ def main():
     cfg = yaml.safe_load(open(os.path.join(pkg.__BLACKPANTHER_V55_RESOURCE_DIRECTORY__, "bp5_manual_eval.yaml")))["environment"]
     cfg["num_envs"] = n
     delays, cmds, mus = np.arange(n) % 6, np.linspace(0.5, 5.0, n), np.linspace(0.05, 0.8, n)
-    pol = EV.load_policy(os.path.join(ROOT, "tests", "golden", "actor_bp5_155.npz"), torch.device("cuda"))
+    if args.policy == "mlp":
+        from high_speed_quadrupedal_locomotion_by_irrl_amd.policies import MlpPolicy
+        torch.manual_seed(0)
+        pol = EV.load_policy(MlpPolicy(), torch.device("cuda"))
+    else:
+        pol = EV.load_policy(os.path.join(ROOT, "tests", "golden", "actor_bp5_155.npz"), torch.device("cuda"))
     env = FlexibleGymEnv(pkg.__BLACKPANTHER_V55_RESOURCE_DIRECTORY__, yaml.safe_dump(cfg, default_flow_style=False, width=float("inf")))
     env.init()
     env.SetContactCoefficient(EV.contact_material(mus))
     out = {"envs": n, "scenario": bool(args.scenario), "kicks": int(args.kicks), "gait": bool(args.gait)}
+    if args.events:
+        return events(args, env, pol, delays, cmds, out)
     if args.ab:
         return ab(args, env, pol, delays, cmds, out)
     for name, record in (("statistics only", ()), ("all recorders", tuple(EV.RECORDERS))):
