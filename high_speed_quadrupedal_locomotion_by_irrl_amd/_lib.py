@@ -141,6 +141,16 @@ SIGNATURES = {
     # the motor plane of a gait recorder: rec_gait, rec_done | rows, num_envs, conditions, robots, frame_first, frame_every, frames |
     # `const irrl_eval_motor_spec *` (EvalMotorSpec below) | counts, hist, fold | stream
     "irrl_eval_motor_plane": (C.c_int, [vp, vp] + [C.c_int] * 7 + [vp] + [vp] * 3 + [vp]),
+    # the five-launch loop with trace recorders: the measured calls' lists with `const irrl_eval_trace *` (EvalTrace below; None = NULL = the
+    # measured call) behind the gait measurements
+    "irrl_lstm_eval_traced": (C.c_int, [vp, C.c_int, C.c_longlong] + [C.c_int] * 3 + [vp] * 6 + [C.c_int] + [vp] * 8 + [vp] * 2 + [C.c_float] * 3
+                              + [fp, fp, C.c_int] + [vp] * 9 + [vp, vp, vp, vp, vp]),
+    "irrl_mlp_eval_traced": (C.c_int, [vp, C.c_int, C.c_longlong] + [C.c_int] * 3 + [vp] * 6 + [C.c_int] + [vp] * 7 + [vp] * 2 + [C.c_float] * 3
+                             + [fp, fp, C.c_int] + [vp] * 9 + [vp, vp, vp, vp, vp]),
+    # the correlation moments of two recorder windows: x, y, rec_done | rows, num_envs, conditions, robots, frame_first, frame_every, frames |
+    # `const irrl_eval_corr_spec *` (EvalCorrSpec below) | count, sx, sy, sxy, range_x, range_y, work | stream
+    "irrl_eval_correlation": (C.c_int, [vp, vp, vp] + [C.c_int] * 7 + [vp] + [vp] * 7 + [vp]),
+    "irrl_eval_correlation_work": (C.c_size_t, [C.c_int, vp]),
 }
 
 
@@ -186,6 +196,17 @@ class EvalMotorSpec(C.Structure):
     histogram's ranges and bins, the fold's period in frames)"""
     _fields_ = [(k, C.c_double) for k in ("tau_max", "w_crit", "w_max", "knee_ratio", "sat", "t_lo", "t_hi", "w_lo", "w_hi")] + \
                [(k, C.c_int) for k in ("t_bins", "w_bins", "period")]
+
+
+class EvalTrace(C.Structure):
+    """struct irrl_eval_trace of include/irrl_env.h (a HOST struct of device pointers: rec_lstm f32 [steps, N, 4 hid], the actor's half of the
+    recurrent state after each policy step; rec_value f32 [steps, N], the critic's value); C.byref(...) or None"""
+    _fields_ = [("rec_lstm", vp), ("rec_value", vp)]
+
+
+class EvalCorrSpec(C.Structure):
+    """struct irrl_eval_corr_spec of include/irrl_env.h (a HOST struct: row width, first column and column count of the x and of the y window)"""
+    _fields_ = [(k, C.c_int) for k in ("x_dim", "x_first", "x_count", "y_dim", "y_first", "y_count")]
 
 
 def load():

@@ -513,3 +513,29 @@ static inline const char *irrl_eval_motor_spec_error(const irrl_eval_motor_spec 
   }
   return NULL;
 }
+
+// ---- the correlation moments of two recorder windows (irrl_eval_correlation, include/irrl_env.h) ----
+// THE accumulation: s + (double)a * (double)b.  The product of two f32 values has at most 48 significant bits and is exact in f64, so the fused
+// form (one rounding of s + a b) and the separate form (an exact product, one rounding of the sum) are the same number: host compiler, device
+// compiler and numpy agree bit for bit as long as every accumulator takes its samples in the one stated order.  sum x is b = 1, sum x^2 is b = a.
+static inline IRRL_EVAL_FN double irrl_eval_corr_add(double s, float a, float b) { return s + (double)a * (double)b; }
+// the running minimum / maximum: m unless v is smaller / larger -- a NaN never enters a range
+static inline IRRL_EVAL_FN float irrl_eval_corr_min(float m, float v) { return v < m ? v : m; }
+static inline IRRL_EVAL_FN float irrl_eval_corr_max(float m, float v) { return v > m ? v : m; }
+// the f64 accumulators of one robot: sxy [cx, cy] | sx [cx, 2] | sy [cy, 2]
+static inline IRRL_EVAL_FN size_t irrl_eval_corr_sums(const irrl_eval_corr_spec &s) {
+  return (size_t)s.x_count * (size_t)s.y_count + 2 * (size_t)s.x_count + 2 * (size_t)s.y_count;
+}
+// the doubles of `work` per robot: the sums, T_e as an int64, the two ranges as f32 pairs
+static inline IRRL_EVAL_FN size_t irrl_eval_corr_work_per_env(const irrl_eval_corr_spec &s) {
+  return irrl_eval_corr_sums(s) + 1 + (size_t)s.x_count + (size_t)s.y_count;
+}
+// what is wrong with a spec, or NULL
+static inline const char *irrl_eval_corr_spec_error(const irrl_eval_corr_spec &s) {
+  if (s.x_dim < 1 || s.y_dim < 1) return "x_dim >= 1, y_dim >= 1";
+  if (s.x_count < 1 || s.x_count > IRRL_EVAL_CORR_MAX_X) return "x_count lies in 1 .. 64";
+  if (s.y_count < 1 || s.y_count > IRRL_EVAL_CORR_MAX_Y) return "y_count lies in 1 .. 1024";
+  if (s.x_first < 0 || (long long)s.x_first + (long long)s.x_count > (long long)s.x_dim) return "the x window x_first .. x_first + x_count lies outside the row width x_dim";
+  if (s.y_first < 0 || (long long)s.y_first + (long long)s.y_count > (long long)s.y_dim) return "the y window y_first .. y_first + y_count lies outside the row width y_dim";
+  return NULL;
+}

@@ -111,4 +111,17 @@ __global__ void __launch_bounds__(256) irrl_eval_perturb_kernel(int N, const flo
   gv[0] = v0; gv[1] = v1; gv[2] = v2; gv[3] = o0; gv[4] = o1; gv[5] = o2;
 }
 
+// the trace recorders' row of one step (irrl_eval_trace, include/irrl_env.h; the extra launch of irrl_lstm_eval_traced / irrl_mlp_eval_traced between
+// the policy step and the action filter): a lane per (env, column < hid4) copies the actor's half of the recurrent state, lstm_state[e, 0 : hid4]
+// of [N, 2 hid4], and the lanes e < N the critic's value -- reads and writes both run along the lanes.  Either row pointer may be NULL.
+__global__ void __launch_bounds__(256) irrl_eval_trace_kernel(int N, int hid4, const float *lstm_state, const float *value, float *rec_lstm_row,
+                                                              float *rec_value_row) {
+  const size_t i = (size_t)blockIdx.x * 256u + (size_t)threadIdx.x;
+  if (rec_lstm_row && i < (size_t)N * (size_t)hid4) {
+    const size_t e = i / (size_t)hid4, j = i - e * (size_t)hid4;
+    rec_lstm_row[i] = lstm_state[e * 2 * (size_t)hid4 + j];
+  }
+  if (rec_value_row && i < (size_t)N) rec_value_row[i] = value[i];
+}
+
 static inline dim3 eval_grid(int n_elems) { return dim3((unsigned)((n_elems + 255) / 256)); }

@@ -24,6 +24,7 @@
 #include "eval_ensemble.hpp"  // the ensemble analysis: argument block and launcher of csrc/eval_ensemble.hip (irrl_eval_ensemble below)
 #include "eval_recurrence.hpp"  // the recurrence analysis: argument block and launcher of csrc/eval_recurrence.hip (irrl_eval_recurrence below)
 #include "eval_footfall.hpp"    // the gait recorder's analyses: argument blocks and launchers of csrc/eval_footfall.hip
+#include "eval_correlation.hpp"  // the correlation moments: argument block and launcher of csrc/eval_correlation.hip (irrl_eval_correlation below)
 
 #include <cmath>
 #include <string>
@@ -597,7 +598,15 @@ static void eval_gait_args(EvalArgs &a, const irrl_env *h, const irrl_eval_gait 
   a.gait = gg->gait; a.prev_contact = gg->prev_contact; a.rec_gait = gg->rec_gait;
   a.in_contact = h->S.in_contact; a.lam_w = h->S.lam_w; a.inv_control_dt = h->P.inv_control_dt;
 }
-// the argument list the eight evaluation entry points share, and its forwarding
+// the trace recorders of irrl_lstm_eval_traced / irrl_mlp_eval_traced (include/irrl_env.h): refused before any HIP call; NULL = none
+static int eval_trace_check(const char *who, bool lstm, const irrl_eval_trace *tr) {
+  if (!tr) return 0;
+  const std::string w = std::string(who) + ": trace: ";
+  if (!tr->rec_lstm && !tr->rec_value) { g_err = w + "rec_lstm and rec_value are both NULL (pass a NULL struct for no trace)"; return 1; }
+  if (!lstm && tr->rec_lstm) { g_err = w + "rec_lstm must be NULL: MlpPolicy has no recurrent state"; return 1; }
+  return 0;
+}
+// the argument list the evaluation entry points share, and its forwarding
 #define IRRL_EVAL_PARAMS                                                                                                                              \
   irrl_env *h, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *lstm_w, const float *pi_w, const float *pi_b,        \
       const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring, float *cmd, float *vel_his, float *act_his, float *lstm_state, \
@@ -609,8 +618,10 @@ static void eval_gait_args(EvalArgs &a, const irrl_env *h, const irrl_eval_gait 
       cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std, clip, rec_obs_cond, rec_act_clipped, rec_act_applied, rec_body, rec_torque, rec_obs_raw,       \
       rec_reward, rec_done, stats
 // (lstm: the policy step is irrl_lstm_policy_step; else irrl_mlp_policy_step, lstm_w is its table of 8 and lstm_state is not read)
+// (tr: the trace recorders, NULL = none and then the loop issues the launches it issues without them)
 static int eval_rollout_steps(const char *who, bool lstm, IRRL_EVAL_PARAMS, const irrl_eval_scenario *sc, const irrl_eval_kicks *kk, const irrl_eval_gait *gg,
-                              void *hip_stream) {
+                              const irrl_eval_trace *tr, void *hip_stream) {
+  if (eval_trace_check(who, lstm, tr)) return 1;
   if (eval_rollout_check(who, lstm, h, steps, step0, hid, ob_dim, act_dim, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, depth, ring, cmd, vel_his, act_his,
                          lstm_state, done, obs, work, delay, cmd_target, a_cmd, a_vel, a_act, cmd_mean, cmd_std)) return 1;
   if (eval_scenario_check(who, sc)) return 1;
@@ -638,6 +649,12 @@ static int eval_rollout_steps(const char *who, bool lstm, IRRL_EVAL_PARAMS, cons
                          : irrl_mlp_policy_step(hid, ob_dim, act_dim, n, w.obs_cond, done, lstm_w, pi_w, pi_b, vf_w, vf_b, logstd, nullptr, 0, 0u, 0, nullptr, 0, w.action,
                                                 w.clipped, w.value, w.neglogp, -1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, hip_stream);
     if (prc != 0) { g_err = std::string(who) + ": policy step refused its arguments"; return 1; }
+    if (tr) {     // the state that has consumed this step's observation, and this step's value
+      const size_t hid4 = 4 * (size_t)hid, lanes = tr->rec_lstm ? (size_t)n * hid4 : (size_t)n;
+      hipLaunchKernelGGL(irrl_eval_trace_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, h->stream, n, (int)hid4, (const float *)lstm_state,
+                         (const float *)w.value, tr->rec_lstm ? tr->rec_lstm + (size_t)k * (size_t)n * hid4 : nullptr,
+                         tr->rec_value ? tr->rec_value + (size_t)k * (size_t)n : nullptr);
+    }
     hipLaunchKernelGGL(irrl_eval_action_kernel, eval_grid(n * 12), dim3(256), 0, h->stream, a);
     if (kk) {     // a step whose row fires: the kick, on the state the previous step (or the reset) left
       const int r = irrl_eval_kick_row(a, a.t);
@@ -652,16 +669,20 @@ static int eval_rollout_steps(const char *who, bool lstm, IRRL_EVAL_PARAMS, cons
   return 0;
 }
 int irrl_lstm_eval_rollout(IRRL_EVAL_PARAMS, void *hip_stream) {
-  return eval_rollout_steps("irrl_lstm_eval_rollout", true, IRRL_EVAL_FORWARD, nullptr, nullptr, nullptr, hip_stream);
+  return eval_rollout_steps("irrl_lstm_eval_rollout", true, IRRL_EVAL_FORWARD, nullptr, nullptr, nullptr, nullptr, hip_stream);
 }
 int irrl_lstm_eval_scenario(IRRL_EVAL_PARAMS, const irrl_eval_scenario *scenario, void *hip_stream) {
-  return eval_rollout_steps("irrl_lstm_eval_scenario", true, IRRL_EVAL_FORWARD, scenario, nullptr, nullptr, hip_stream);
+  return eval_rollout_steps("irrl_lstm_eval_scenario", true, IRRL_EVAL_FORWARD, scenario, nullptr, nullptr, nullptr, hip_stream);
 }
 int irrl_lstm_eval_perturbed(IRRL_EVAL_PARAMS, const irrl_eval_scenario *scenario, const irrl_eval_kicks *kicks, void *hip_stream) {
-  return eval_rollout_steps("irrl_lstm_eval_perturbed", true, IRRL_EVAL_FORWARD, scenario, kicks, nullptr, hip_stream);
+  return eval_rollout_steps("irrl_lstm_eval_perturbed", true, IRRL_EVAL_FORWARD, scenario, kicks, nullptr, nullptr, hip_stream);
 }
 int irrl_lstm_eval_measured(IRRL_EVAL_PARAMS, const irrl_eval_scenario *scenario, const irrl_eval_kicks *kicks, const irrl_eval_gait *gait, void *hip_stream) {
-  return eval_rollout_steps("irrl_lstm_eval_measured", true, IRRL_EVAL_FORWARD, scenario, kicks, gait, hip_stream);
+  return eval_rollout_steps("irrl_lstm_eval_measured", true, IRRL_EVAL_FORWARD, scenario, kicks, gait, nullptr, hip_stream);
+}
+int irrl_lstm_eval_traced(IRRL_EVAL_PARAMS, const irrl_eval_scenario *scenario, const irrl_eval_kicks *kicks, const irrl_eval_gait *gait,
+                          const irrl_eval_trace *trace, void *hip_stream) {
+  return eval_rollout_steps("irrl_lstm_eval_traced", true, IRRL_EVAL_FORWARD, scenario, kicks, gait, trace, hip_stream);
 }
 // one kick row per env on the pool now (the same kernel), stream-ordered on the pool's stream
 int irrl_env_perturb_base(irrl_env *h, const float *rows) {
@@ -763,7 +784,13 @@ int irrl_mlp_eval_rollout_supports(irrl_env *h, int hid) {
 int irrl_mlp_eval_measured(IRRL_EVAL_MLP_PARAMS, const irrl_eval_scenario *scenario, const irrl_eval_kicks *kicks, const irrl_eval_gait *gait, void *hip_stream) {
   float *const lstm_state = nullptr;
   const float *const *lstm_w = mlp_w;
-  return eval_rollout_steps("irrl_mlp_eval_measured", false, IRRL_EVAL_FORWARD, scenario, kicks, gait, hip_stream);
+  return eval_rollout_steps("irrl_mlp_eval_measured", false, IRRL_EVAL_FORWARD, scenario, kicks, gait, nullptr, hip_stream);
+}
+int irrl_mlp_eval_traced(IRRL_EVAL_MLP_PARAMS, const irrl_eval_scenario *scenario, const irrl_eval_kicks *kicks, const irrl_eval_gait *gait,
+                         const irrl_eval_trace *trace, void *hip_stream) {
+  float *const lstm_state = nullptr;
+  const float *const *lstm_w = mlp_w;
+  return eval_rollout_steps("irrl_mlp_eval_traced", false, IRRL_EVAL_FORWARD, scenario, kicks, gait, trace, hip_stream);
 }
 int irrl_mlp_eval_measured_persistent(IRRL_EVAL_MLP_PARAMS, const irrl_eval_scenario *sc, const irrl_eval_kicks *kk, const irrl_eval_gait *gg, void *hip_stream) {
   const char *who = "irrl_mlp_eval_measured_persistent";
@@ -1487,6 +1514,39 @@ int irrl_eval_motor_plane(const float *rec_gait, const uint8_t *rec_done, int ro
   a.frame_every = frame_every; a.spec = *spec; a.counts = counts;
   a.hist = spec->t_bins > 0 && spec->w_bins > 0 ? hist : nullptr; a.fold = spec->period > 0 ? fold : nullptr;
   HIP_TRY(irrl_eval_motor_plane_launch(a, (hipStream_t)hip_stream));
+  return 0;
+}
+
+// ---- correlation moments of two recorder windows (kernels and launcher: csrc/eval_correlation.hip; the accumulation: csrc/eval_elements.hpp) ----
+size_t irrl_eval_correlation_work(int num_envs, const irrl_eval_corr_spec *spec) {
+  if (!spec || num_envs < 1 || irrl_eval_corr_spec_error(*spec)) return 0;
+  return (size_t)num_envs * irrl_eval_corr_work_per_env(*spec);
+}
+
+int irrl_eval_correlation(const float *x, const float *y, const uint8_t *rec_done, int rows, int num_envs, int conditions, int robots,
+                          int frame_first, int frame_every, int frames, const irrl_eval_corr_spec *spec, int64_t *count, double *sx, double *sy,
+                          double *sxy, float *range_x, float *range_y, double *work, void *hip_stream) {
+  const std::string w = "irrl_eval_correlation: ";
+  if (!x || !y || !spec || !count || !sx || !sy || !sxy) { g_err = w + "NULL x, y, spec, count, sx, sy or sxy"; return 1; }
+  if (const char *bad = irrl_eval_corr_spec_error(*spec)) { g_err = w + "spec: " + bad; return 1; }
+  if (frames < 1) { g_err = w + "frames lies in 1 .. 16384"; return 1; }
+  if (const char *bad = gait_window_error(rows, num_envs, frame_first, frame_every, frames, IRRL_EVAL_CORR_MAX_FRAMES)) { g_err = w + bad; return 1; }
+  if (conditions < 1 || robots < 1 || (long long)conditions * (long long)robots != (long long)num_envs) {
+    g_err = w + "conditions >= 1, robots >= 1, conditions * robots == num_envs"; return 1;
+  }
+  if (robots > 1 && !work) { g_err = w + "robots > 1 needs work (irrl_eval_correlation_work doubles)"; return 1; }
+  CorrelationArgs a = CorrelationArgs();
+  a.x = x; a.y = y; a.rec_done = rec_done; a.N = num_envs; a.C = conditions; a.R = robots; a.T = frames; a.frame_first = frame_first;
+  a.frame_every = frame_every; a.spec = *spec; a.zero = 0.0;
+  const bool ranges = range_x && range_y;      // (one of the two alone: off, like both NULL)
+  if (robots == 1) {
+    a.p_sxy = sxy; a.p_sx = sx; a.p_sy = sy; a.p_count = count; a.p_rx = ranges ? range_x : nullptr; a.p_ry = ranges ? range_y : nullptr;
+  } else {
+    irrl_eval_corr_work_regions(a, work);
+    if (!ranges) { a.p_rx = nullptr; a.p_ry = nullptr; }
+    a.sxy = sxy; a.sx = sx; a.sy = sy; a.count = count; a.range_x = ranges ? range_x : nullptr; a.range_y = ranges ? range_y : nullptr;
+  }
+  HIP_TRY(irrl_eval_correlation_launch(a, (hipStream_t)hip_stream));
   return 0;
 }
 

@@ -1513,6 +1513,239 @@ def motor_plane_row(counts):
     return dict(saturated=(c[:, 1] + c[:, 2]) / n, outside=c[:, 3] / n, motoring=c[:, 4] / n, braking=c[:, 5] / n, samples=np.asarray(counts)[:, 0].astype(np.int64))
 
 
+# ---- correlation moments of two recorder windows (irrl_eval_correlation) ----
+CORR_MAX_FRAMES = 16384          # IRRL_EVAL_CORR_MAX_FRAMES
+CORR_MAX_X = 64                  # IRRL_EVAL_CORR_MAX_X
+CORR_MAX_Y = 1024                # IRRL_EVAL_CORR_MAX_Y
+CORR_MATRICES = 8                # robustness_sweep: the rows of the first 8 conditions carry the [cx, cy] matrix
+TRACE_RECORDERS = ("lstm", "value")     # PolicyEvaluator.run: what only the five-launch form records (include/irrl_env.h irrl_eval_trace)
+# name -> (recorder of PolicyEvaluator.run, first column, count); lstm's count is the policy's 4 * hid (c0 | h0 | c1 | h1), value's recorder is
+# [steps, N], a single column
+CORR_SOURCES = {"contact": ("gait", 24, 4), "torque": ("gait", 0, 12), "joint_rate": ("gait", 12, 12), "body": ("body", 0, 13),
+                "obs": ("obs_cond", 0, 35), "action": ("act_applied", 0, 12), "lstm": ("lstm", 0, None), "value": ("value", 0, 1)}
+_CORR_KEYS = ("x_dim", "x_first", "x_count", "y_dim", "y_first", "y_count")
+
+
+def correlation_source(name, hid=None):
+    """a name out of CORR_SOURCES -> (recorder, row width, first column, count); hid: the policy's LSTM units, needed for "lstm\""""
+    if name not in CORR_SOURCES:
+        raise KeyError("unknown correlation source %r: choose from %s" % (name, sorted(CORR_SOURCES)))
+    rec, first, count = CORR_SOURCES[name]
+    if rec == "lstm":
+        if hid is None:
+            raise ValueError("the correlation source 'lstm' needs the policy's number of LSTM units")
+        return rec, 4 * int(hid), first, 4 * int(hid)
+    width = GAIT_REC_DIM if rec == "gait" else 1 if rec == "value" else RECORDERS[rec]
+    return rec, width, first, count
+
+
+def correlation_spec(x_dim, x_first, x_count, y_dim, y_first, y_count):
+    """The spec of irrl_eval_correlation: of rows x_dim (y_dim) floats wide the columns x_first .. x_first + x_count (y_first ..) are analysed.
+    -> dict, refused like the C call refuses its struct"""
+    s = dict(zip(_CORR_KEYS, (int(v) for v in (x_dim, x_first, x_count, y_dim, y_first, y_count))))
+    if s["x_dim"] < 1 or s["y_dim"] < 1:
+        raise ValueError("correlation spec: x_dim >= 1, y_dim >= 1")
+    if not 1 <= s["x_count"] <= CORR_MAX_X:
+        raise ValueError("correlation spec: x_count lies in 1 .. %d" % CORR_MAX_X)
+    if not 1 <= s["y_count"] <= CORR_MAX_Y:
+        raise ValueError("correlation spec: y_count lies in 1 .. %d" % CORR_MAX_Y)
+    for k in "xy":
+        if s[k + "_first"] < 0 or s[k + "_first"] + s[k + "_count"] > s[k + "_dim"]:
+            raise ValueError("correlation spec: the %s window lies outside the row width" % k)
+    return s
+
+
+def _corr_frames(rows, frame_first, frame_every, frames):
+    frame_first, frame_every, T = _gait_frames(rows, frame_first, frame_every, frames, CORR_MAX_FRAMES)
+    if T < 1:
+        raise ValueError("frames lies in 1 .. %d" % CORR_MAX_FRAMES)
+    return frame_first, frame_every, T
+
+
+def correlation_numpy(x, y, rec_done, spec, conditions=None, frame_first=0, frame_every=1, frames=None):
+    """The twin of irrl_eval_correlation (include/irrl_env.h): x [rows, N, x_dim] and y [rows, N, y_dim] float32 ([rows, N] with a row width of 1),
+    rec_done [rows, N] or None, env = condition * robots + robot (conditions None: N, one robot each) -> dict(count int64 [G], sx float64
+    [G, cx, 2] (sum x, sum x^2), sy float64 [G, cy, 2], sxy float64 [G, cx, cy], range_x float32 [G, cx, 2] and range_y float32 [G, cy, 2] (min,
+    max; +inf, -inf without a sample)) over the frames i < T_e of each condition's robots.  An explicit loop over the frames, every robot and
+    pair at once, as s = s + (double)a * (double)b from +0.0, then an explicit loop over a condition's robots from +0.0: the one order of the f64
+    additions the kernel and the host program follow, so equal means equal bits.  A NaN sample never enters a range and poisons the sums of
+    its own column (pairs) only."""
+    s = correlation_spec(**spec)
+    cx, cy = s["x_count"], s["y_count"]
+
+    def rows3(a, dim, what):
+        a = np.asarray(a)
+        a = a[:, :, None] if a.ndim == 2 and dim == 1 else a
+        if a.ndim != 3 or a.shape[2] != dim or a.dtype != np.float32:
+            raise ValueError("%s: float32 [rows, N, %d]" % (what, dim))
+        return a
+    x, y = rows3(x, s["x_dim"], "x"), rows3(y, s["y_dim"], "y")
+    if x.shape[:2] != y.shape[:2]:
+        raise ValueError("x and y have the same rows and N")
+    rows, N = x.shape[:2]
+    Cn, R = _motor_shape(N, N if conditions is None else conditions)
+    frame_first, frame_every, T = _corr_frames(rows, frame_first, frame_every, frames)
+    sel = frame_first + frame_every * np.arange(T)
+    te = np.full(N, T, np.int64)
+    if rec_done is not None:
+        done = np.asarray(rec_done)
+        if done.shape != (rows, N):
+            raise ValueError("rec_done [rows, N]")
+        dn = done[sel] != 0
+        te = np.where(dn.any(0), dn.argmax(0), T).astype(np.int64)
+    xw, yw = x[sel][:, :, s["x_first"]:s["x_first"] + cx], y[sel][:, :, s["y_first"]:s["y_first"] + cy]     # float32 [T, N, c]
+    sxy, sx, sy = np.zeros((N, cx, cy)), np.zeros((N, cx, 2)), np.zeros((N, cy, 2))
+    inf = np.float32(np.inf)
+    rx, ry = np.empty((N, cx, 2), np.float32), np.empty((N, cy, 2), np.float32)
+    rx[..., 0] = ry[..., 0] = inf
+    rx[..., 1] = ry[..., 1] = -inf
+    with np.errstate(invalid="ignore", over="ignore"):
+        for i in range(int(te.max()) if N else 0):             # frames in ascending order
+            on = i < te
+            a32, b32 = xw[i], yw[i]
+            a, b = a32.astype(np.float64), b32.astype(np.float64)
+            sxy = np.where(on[:, None, None], sxy + a[:, :, None] * b[:, None, :], sxy)
+            for acc, v, v32, rng in ((sx, a, a32, rx), (sy, b, b32, ry)):
+                m = on[:, None]
+                acc[..., 0] = np.where(m, acc[..., 0] + v, acc[..., 0])
+                acc[..., 1] = np.where(m, acc[..., 1] + v * v, acc[..., 1])
+                rng[..., 0] = np.where(m & (v32 < rng[..., 0]), v32, rng[..., 0])
+                rng[..., 1] = np.where(m & (v32 > rng[..., 1]), v32, rng[..., 1])
+        out = dict(count=te.reshape(Cn, R).sum(1).astype(np.int64))
+        for k, part in (("sx", sx), ("sy", sy), ("sxy", sxy)):
+            part = part.reshape((Cn, R) + part.shape[1:])
+            tot = np.zeros((Cn,) + part.shape[2:])
+            for r in range(R):                                 # robots in ascending order
+                tot = tot + part[:, r]
+            out[k] = tot
+        for k, part in (("range_x", rx), ("range_y", ry)):
+            part = part.reshape((Cn, R) + part.shape[1:])
+            tot = part[:, 0].copy()
+            for r in range(1, R):
+                tot[..., 0] = np.where(part[:, r, :, 0] < tot[..., 0], part[:, r, :, 0], tot[..., 0])
+                tot[..., 1] = np.where(part[:, r, :, 1] > tot[..., 1], part[:, r, :, 1], tot[..., 1])
+            out[k] = tot
+    return out
+
+
+def correlation_struct(spec):
+    from . import _lib
+    return _lib.EvalCorrSpec(**correlation_spec(**spec))
+
+
+def correlation_work(num_envs, spec):
+    """the doubles of `work` for a pool of num_envs: irrl_eval_correlation_work = num_envs * (cx cy + 3 cx + 3 cy + 1)"""
+    s = correlation_spec(**spec)
+    return int(num_envs) * (s["x_count"] * s["y_count"] + 3 * s["x_count"] + 3 * s["y_count"] + 1)
+
+
+def correlation_device(x, y, rec_done, spec, conditions=None, frame_first=0, frame_every=1, frames=None, ranges=True, work="auto"):
+    """correlation_numpy on the device: ONE call of irrl_eval_correlation on torch's current stream (one workgroup per robot and, with more than
+    one robot per condition, a second launch that adds the robots' partials in order), no synchronisation.  x, y: float32 device tensors [rows,
+    N, dim] ([rows, N] with a row width of 1; the same tensor for an auto-covariance), rec_done a bool / uint8 device tensor [rows, N] or None.
+    work: "auto" = allocated here where robots > 1, None = NULL (one robot per condition only), or a float64 device tensor of correlation_work
+    doubles.  -> dict of device tensors count int64 [G], sx, sy, sxy float64, range_x, range_y float32 (None with ranges=False)"""
+    import torch
+    from . import _lib
+    from ._lib import ptr
+    s = correlation_spec(**spec)
+    cx, cy = s["x_count"], s["y_count"]
+
+    def rows3(a, dim, what):
+        a = a.unsqueeze(2) if a.dim() == 2 and dim == 1 else a
+        if a.dim() != 3 or a.shape[2] != dim or a.dtype != torch.float32 or not a.is_cuda:
+            raise ValueError("%s: a float32 device tensor [rows, N, %d]" % (what, dim))
+        return _lib.contig(a)
+    x, y = rows3(x, s["x_dim"], "x"), rows3(y, s["y_dim"], "y")
+    if x.shape[:2] != y.shape[:2] or x.device != y.device:
+        raise ValueError("x and y have the same rows and N and live on one device")
+    rows, n = int(x.shape[0]), int(x.shape[1])
+    if rec_done is not None:
+        if tuple(rec_done.shape) != (rows, n) or rec_done.device != x.device or rec_done.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("rec_done: a bool / uint8 device tensor [rows, N]")
+        rec_done = _lib.contig(rec_done).view(torch.uint8)
+    Cn, R = _motor_shape(n, n if conditions is None else conditions)
+    frame_first, frame_every, T = _corr_frames(rows, frame_first, frame_every, frames)
+    dev = x.device
+    if isinstance(work, str) and work == "auto":
+        work = torch.empty(correlation_work(n, s), device=dev, dtype=torch.float64) if R > 1 else None
+    elif work is not None and (work.dtype != torch.float64 or work.numel() < correlation_work(n, s) or work.device != dev or not work.is_contiguous()):
+        raise ValueError("work: a contiguous float64 device tensor of at least %d elements" % correlation_work(n, s))
+    st = correlation_struct(s)
+    f64 = dict(device=dev, dtype=torch.float64)
+    out = dict(count=torch.zeros(Cn, device=dev, dtype=torch.int64), sx=torch.zeros(Cn, cx, 2, **f64), sy=torch.zeros(Cn, cy, 2, **f64),
+               sxy=torch.zeros(Cn, cx, cy, **f64),
+               range_x=torch.zeros(Cn, cx, 2, device=dev, dtype=torch.float32) if ranges else None,
+               range_y=torch.zeros(Cn, cy, 2, device=dev, dtype=torch.float32) if ranges else None)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().irrl_eval_correlation(ptr(x), ptr(y), ptr(rec_done), rows, n, Cn, R, frame_first, frame_every, T,
+                                                     C.cast(C.pointer(st), C.c_void_p), ptr(out["count"]), ptr(out["sx"]), ptr(out["sy"]), ptr(out["sxy"]),
+                                                     ptr(out["range_x"]), ptr(out["range_y"]), ptr(work), _lib.stream_ptr(dev)))
+    return out
+
+
+def correlation_to_numpy(res):
+    """a result of correlation_device -> the twin's dict of numpy arrays (synchronises)"""
+    return {k: None if v is None else v.cpu().numpy() for k, v in res.items()}
+
+
+def correlation_from_moments(m):
+    """The moments of correlation_numpy / correlation_to_numpy -> dict(r [G, cx, cy] the Pearson correlation, cov [G, cx, cy] the sample
+    covariance (n - 1 in the denominator, like pandas), mean_x [G, cx], mean_y [G, cy], std_x, std_y (n - 1), count [G]).  r is NaN where the
+    condition has fewer than 2 samples or either column is constant -- decided EXACTLY from the ranges, min == max, where they are given (a foot
+    that never touches down: pandas gives NaN there too), from a variance that is not positive otherwise; cov and the standard deviations are NaN
+    below 2 samples, the means below 1.  The one function behind both the device path and the twin; the differences n sxy - sx sy are taken
+    in extended precision."""
+    ld = np.longdouble
+    n = np.asarray(m["count"]).astype(ld)
+    sx1, sx2 = np.asarray(m["sx"])[..., 0].astype(ld), np.asarray(m["sx"])[..., 1].astype(ld)
+    sy1, sy2 = np.asarray(m["sy"])[..., 0].astype(ld), np.asarray(m["sy"])[..., 1].astype(ld)
+    sxy = np.asarray(m["sxy"]).astype(ld)
+    n1, n2, n3 = n[:, None], n[:, None, None], (n * (n - 1))[:, None, None]
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        cxy = n2 * sxy - sx1[:, :, None] * sy1[:, None, :]
+        vx, vy = n1 * sx2 - sx1 * sx1, n1 * sy2 - sy1 * sy1
+        r = cxy / np.sqrt(vx[:, :, None] * vy[:, None, :])
+        cov = cxy / n3
+        few1, few2 = (n < 1), (n < 2)
+        if m.get("range_x") is not None and m.get("range_y") is not None:
+            flat_x = ~(np.asarray(m["range_x"])[..., 0] < np.asarray(m["range_x"])[..., 1])
+            flat_y = ~(np.asarray(m["range_y"])[..., 0] < np.asarray(m["range_y"])[..., 1])
+        else:
+            flat_x, flat_y = ~(vx > 0), ~(vy > 0)
+        bad = few2[:, None, None] | flat_x[:, :, None] | flat_y[:, None, :]
+        r = np.where(bad, np.nan, np.clip(r, -1.0, 1.0)).astype(np.float64)
+        cov = np.where(few2[:, None, None], np.nan, cov).astype(np.float64)
+        mean_x, mean_y = np.where(few1[:, None], np.nan, sx1 / n1).astype(np.float64), np.where(few1[:, None], np.nan, sy1 / n1).astype(np.float64)
+        d = (n * (n - 1))[:, None]
+        std_x = np.where(few2[:, None], np.nan, np.sqrt(np.maximum(vx, 0) / d)).astype(np.float64)
+        std_y = np.where(few2[:, None], np.nan, np.sqrt(np.maximum(vy, 0) / d)).astype(np.float64)
+    return dict(r=r, cov=cov, mean_x=mean_x, mean_y=mean_y, std_x=std_x, std_y=std_y, count=np.asarray(m["count"]).astype(np.int64))
+
+
+def correlation_unit(y_name, j, cy):
+    """column j of a y window of cy columns -> for "lstm" (layer 1 or 2, "c" or "h", index) in the recorder's order c0 | h0 | c1 | h1
+    (the reference's layer1_c | layer1_h | layer2_c | layer2_h), else (y_name, j)"""
+    if y_name != "lstm":
+        return (y_name, int(j))
+    hid = cy // 4
+    block = int(j) // hid
+    return (block // 2 + 1, "ch"[block % 2], int(j) % hid)
+
+
+def correlation_row(m, names, g=0):
+    """one condition of the moments -> dict(corr_max: the largest |r| over the [cx, cy] pairs (NaN if no pair has an r), corr_r: that r with its
+    sign, corr_leg: the x column's label -- the leg's name out of FOOTFALL_LEGS for the source "contact", else (x name, column) --, corr_unit:
+    correlation_unit of the y column).  names: the (x, y) source names out of CORR_SOURCES"""
+    x_name, y_name = names
+    r = correlation_from_moments({k: None if v is None else np.asarray(v)[g:g + 1] for k, v in m.items()})["r"][0]
+    if not np.any(np.isfinite(r)):
+        return dict(corr_max=float("nan"), corr_r=float("nan"), corr_leg=None, corr_unit=None)
+    i, j = np.unravel_index(int(np.nanargmax(np.abs(r))), r.shape)
+    leg = FOOTFALL_LEGS[i] if x_name == "contact" else (x_name, int(i))
+    return dict(corr_max=float(abs(r[i, j])), corr_r=float(r[i, j]), corr_leg=leg, corr_unit=correlation_unit(y_name, j, r.shape[1]))
+
+
 # ---- the device loop ----
 def resolve_persistent(persistent, supported):
     """the `persistent` keyword of PolicyEvaluator.run / robustness_sweep (False, True, "auto"; the command line's "off" / "on" too) -> bool;
@@ -1681,6 +1914,10 @@ class PolicyEvaluator(object):
     def run(self, steps, record=(), accumulate=True, persistent=False):
         """`steps` control steps from ONE C call (stream-ordered on torch's current stream, no synchronisation).  record: names out of
         RECORDERS, and "gait" (rec_gait [steps, N, 32]: tq | qd | in_contact | lam_w_z / control_dt) -> dict of device tensors [steps, N, .]; accumulate: add these steps' frames to the per-env statistics.
+        The trace recorders "lstm" ([steps, N, 4 hid]: the actor's half of the recurrent state, c0 | h0 | c1 | h1, AFTER each step's policy step;
+        steps x N x 4 hid x 4 B) and "value" ([steps, N]: the critic's value of each step) exist in the five-launch form only (include/irrl_env.h
+        irrl_eval_trace: one extra launch per step, every other buffer bit-identical): with one of them persistent=True raises ValueError and
+        "auto" is the five-launch form; "lstm" with an MlpPolicy raises ValueError, the policy has no recurrent state.
         persistent: False = five launches per control step (every pool and policy; also steps the critic's half of lstm_state); True = the
         whole call as one persistent launch (raises with the library's text where the kernel does not exist); "auto" = the persistent launch
         where `persistent_supported`, else five launches per step.  The two forms leave bit-identical buffers -- except the critic's half of
@@ -1692,12 +1929,19 @@ class PolicyEvaluator(object):
         from ._lib import ptr
         from .lstm_fused import _head_ptrs, _lstm_weight_table, _mlp_weight_table
         steps = int(steps)
-        unknown = [k for k in record if k not in RECORDERS and k != "gait"]
+        unknown = [k for k in record if k not in RECORDERS and k != "gait" and k not in TRACE_RECORDERS]
         if unknown:
-            raise KeyError("unknown recorder(s) %s: choose from %s" % (unknown, sorted(RECORDERS) + ["gait"]))
+            raise KeyError("unknown recorder(s) %s: choose from %s" % (unknown, sorted(RECORDERS) + ["gait"] + list(TRACE_RECORDERS)))
+        trace = [k for k in TRACE_RECORDERS if k in record]
+        if "lstm" in trace and self.is_mlp:
+            raise ValueError("the recorder 'lstm' needs a recurrent policy: MlpPolicy has no recurrent state")
+        if trace and persistent in (True, "on"):
+            raise ValueError("the trace recorder(s) %s exist in the five-launch form only: the persistent kernel keeps the recurrent state in an LDS "
+                             "allocation that is full (163 264 of 163 840 B) and does not run the critic -- use persistent=False or 'auto'" % trace)
         out = {}
         for k in record:
-            shape = (steps, self.n) + ((GAIT_REC_DIM,) if k == "gait" else (RECORDERS[k],) if RECORDERS[k] else ())
+            shape = (steps, self.n) + ((4 * self.hid,) if k == "lstm" else () if k == "value" else (GAIT_REC_DIM,) if k == "gait"
+                                       else (RECORDERS[k],) if RECORDERS[k] else ())
             out[k] = torch.empty(shape, device=self.dev, dtype=torch.bool if k == "done" else torch.float32)
         with torch.cuda.device(self.dev):
             if self.is_mlp:
@@ -1706,7 +1950,7 @@ class PolicyEvaluator(object):
                 self.policy.prepare()                          # the kernels' permuted weight copies follow the parameters (a learner may have stepped)
                 warr = _lstm_weight_table(self.policy, self.dev)
             lib = _lib.load()
-            one_launch = resolve_persistent(persistent, lambda: self.auto_persistent)
+            one_launch = resolve_persistent(persistent, lambda: self.auto_persistent) and not trace
             if self.is_mlp and self.entry_points not in ("auto", "measured"):
                 raise ValueError("entry_points is 'auto' or 'measured' for an MlpPolicy (only the widest pair of entry points exists for it)")
             if self.entry_points not in ("auto", "perturbed", "measured"):
@@ -1722,7 +1966,12 @@ class PolicyEvaluator(object):
                 gstruct = _lib.EvalGait(gait=ptr(self.gait).value if (self.gait is not None and accumulate) else None,
                                         prev_contact=ptr(self.prev_contact).value if self.gait is not None else None,
                                         rec_gait=ptr(out["gait"]).value if "gait" in out else None)
-            if self.is_mlp:
+            if trace:                                          # the widest list with the trace struct behind the gait measurements'
+                tstruct = _lib.EvalTrace(rec_lstm=ptr(out["lstm"]).value if "lstm" in out else None,
+                                         rec_value=ptr(out["value"]).value if "value" in out else None)
+                fn = lib.irrl_mlp_eval_traced if self.is_mlp else lib.irrl_lstm_eval_traced
+                scenario = (raw(struct), raw(kstruct), raw(gstruct), raw(tstruct))
+            elif self.is_mlp:
                 fn = lib.irrl_mlp_eval_measured_persistent if one_launch else lib.irrl_mlp_eval_measured
                 scenario = (raw(struct), raw(kstruct), raw(gstruct))
             elif gstruct is not None or self.entry_points == "measured":
@@ -1834,7 +2083,8 @@ def load_policy(model_or_policy, device):
 
 def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=1000, steps=2000, cmd_hz=1.0, vel_hz=None, act_hz=None, clip=True,
                      mu_warm=0.8, device=None, persistent=PERSISTENT_DEFAULT, levels=None, level_steps=None, heading=None, gait=False,
-                     mass=None, g=9.81, recurrence=None, recurrence_frames=None, record_body=False, footfall=None, motor=None, record_gait=False):
+                     mass=None, g=9.81, recurrence=None, recurrence_frames=None, record_body=False, footfall=None, motor=None, record_gait=False,
+                     correlation=None, record_correlation=False):
     """The reference's robustness grid in one pool: len(mus) x len(delays) x len(cmds) Manual-mode envs (condition index = (i_mu * len(delays) +
     i_delay) * len(cmds) + i_cmd), `warm_steps` control steps on friction mu_warm, then `steps` on the condition's own friction over which the
     statistics are taken.  env_cfg: the `environment:` mapping of a config.  persistent: PolicyEvaluator.run's keyword (same statistics bit for bit
@@ -1858,7 +2108,16 @@ def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=100
     saturated, outside, motoring and braking fractions per joint; plus `counts` [12, 6], `fold` [period, 3]) over the frames the row's statistics
     cover (staircase: the second half of the level); the rows of the first 8 conditions also carry `pattern` uint8 [frames] (the gait diagram)
     and `hist` uint32 [12, t_bins, w_bins].  record_gait: every row carries `rec_gait` [frames, 32] and `rec_done` [frames], the words the two
-    analyses saw.  Without these keywords the rows are what they were, key for key."""
+    analyses saw.
+    correlation: dict(x="contact", y="lstm"), two names out of CORR_SOURCES -- the reference's `--corr`: the recorders of the two sources (and
+    `done`) are kept on the device for the MEASURED steps only (the warm-up records nothing; the LSTM state's recorder is steps x N x 4 hid x 4 B,
+    1000 steps x 4096 robots x 192 units = 3.1 GB) in the five-launch form of the loop (`persistent` must not be True), irrl_eval_correlation runs
+    per robot over the frames the row's statistics cover, and every row gains `corr_max` (the largest |r| of a pair, NaN if no pair has an r),
+    `corr_r` (that r), `corr_leg` (its x column: the leg's name for "contact") and `corr_unit` (its y column: (layer, "c" or "h", index) for
+    "lstm") -- correlation_row; the rows of the first 8 conditions also carry `corr` float64 [cx, cy], the matrix r, and `corr_moments`, the
+    condition's sums.  record_correlation: every row carries `corr_x` [frames, cx], `corr_y` [frames, cy] and `rec_done` [frames], the words
+    the analysis saw.  With an MlpPolicy the source "lstm" is refused: the policy has no recurrent state.
+    Without these keywords the rows are what they were, key for key."""
     import torch
     import yaml
     from . import __BLACKPANTHER_V55_RESOURCE_DIRECTORY__ as rsc
@@ -1907,12 +2166,25 @@ def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=100
         footfall = footfall_spec(footfall)
     if motor is not None:
         motor = motor_spec_check(motor)
-    if recurrence is None and not record_body and not want_gait:
+    corr = None
+    if correlation is not None:
+        names = (correlation.get("x", "contact"), correlation.get("y", "lstm"))
+        if ev.is_mlp and "lstm" in names:
+            raise ValueError("correlation with the source 'lstm': the policy is an MlpPolicy and has no recurrent state (choose another source, e.g. "
+                             "'action' or 'value')")
+        srcs = [correlation_source(k, None if ev.is_mlp else ev.hid) for k in names]
+        corr = dict(names=names, recs=[s[0] for s in srcs],
+                    spec=correlation_spec(srcs[0][1], srcs[0][2], srcs[0][3], srcs[1][1], srcs[1][2], srcs[1][3]))
+    elif record_correlation:
+        raise ValueError("record_correlation needs correlation=dict(x=..., y=...)")
+    if recurrence is None and not record_body and not want_gait and corr is None:
         ev.run(steps, persistent=persistent)
         extra = lambda i, l: {}
     else:
-        rec = ev.run(steps, record=(("body",) if recurrence is not None or record_body else ()) + (("gait", "done") if want_gait else ()),
-                     persistent=persistent)
+        wanted = (("body",) if recurrence is not None or record_body else ()) + (("gait", "done") if want_gait else ())
+        if corr is not None:
+            wanted += tuple(corr["recs"]) + ("done",)
+        rec = ev.run(steps, record=tuple(dict.fromkeys(wanted)), persistent=persistent)              # (each recorder once, in the order asked for)
         span = steps if levels is None else level_steps               # a row's frames: the run, or its level
         parts = []
         fparts, mparts, grec = [], [], None
@@ -1927,6 +2199,17 @@ def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=100
                 mparts.append(motor_plane_to_numpy(motor_plane_device(rec["gait"], rec["done"], motor, frame_first=first(l), frames=count)))
         if record_gait:
             grec = (rec["gait"].cpu().numpy(), rec["done"].cpu().numpy())
+        cparts, crec = [], None
+        if corr is not None:
+            if count > CORR_MAX_FRAMES:
+                raise ValueError("correlation: a row covers %d frames, more than %d" % (count, CORR_MAX_FRAMES))
+            xr, yr = rec[corr["recs"][0]], rec[corr["recs"][1]]
+            for l in range(1 if levels is None else levels):
+                cparts.append(correlation_to_numpy(correlation_device(xr, yr, rec["done"], corr["spec"], frame_first=first(l), frames=count)))
+            if record_correlation:
+                sp = corr["spec"]
+                win = lambda t, a, n: (t if t.dim() == 3 else t.unsqueeze(2))[:, :, a:a + n].cpu().numpy()
+                crec = (win(xr, sp["x_first"], sp["x_count"]), win(yr, sp["y_first"], sp["y_count"]), rec["done"].cpu().numpy())
         if recurrence is not None:
             shown = list(range(min(len(grid), RECURRENCE_MAX_MATRICES)))
             for l in range(1 if levels is None else levels):
@@ -1948,6 +2231,14 @@ def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=100
                 out["motor"] = dict(motor_plane_row(m["counts"][i]), counts=m["counts"][i], fold=None if m["fold"] is None else m["fold"][i])
                 if i < FOOTFALL_PATTERNS and m["hist"] is not None:
                     out["hist"] = m["hist"][i]
+            if cparts:
+                out.update(correlation_row(cparts[l], corr["names"], g=i))
+                if i < CORR_MATRICES:
+                    one = {k: None if v is None else v[i:i + 1] for k, v in cparts[l].items()}
+                    out["corr"], out["corr_moments"] = correlation_from_moments(one)["r"][0], {k: v[0] for k, v in one.items()}
+            if crec is not None:
+                lo = first(l)
+                out["corr_x"], out["corr_y"], out["rec_done"] = crec[0][lo:lo + count, i], crec[1][lo:lo + count, i], crec[2][lo:lo + count, i]
             if grec is not None:
                 out["rec_gait"], out["rec_done"] = grec[0][first(l):first(l) + count, i], grec[1][first(l):first(l) + count, i]
             if parts:
@@ -2129,13 +2420,17 @@ RECURRENCE_TABLE_KEYS = ("RR", "DET", "LMAX", "period_s")
 FOOTFALL_TABLE_KEYS = ("stride_hz_db", "duty_db", "gait", "sat_max")
 
 
-def sweep_table(rows, gait=False, recurrence=False, footfall=False):
+CORRELATION_TABLE_KEYS = ("corr_max", "corr_leg", "corr_unit")
+
+
+def sweep_table(rows, gait=False, recurrence=False, footfall=False, correlation=False):
     """one line per row of a robustness_sweep; gait (rows of a sweep with gait=True): the cost of transport, the mean mechanical power, the four
     duty factors, `stride_hz` (mean over the legs of gait_from_sums' stride_hz<l>: the RAW contact flags' touchdown rate, several times the
     stride frequency because the flag chatters while a foot is down -- the debounced one is stride_hz_db) and the flight fraction too; footfall
     (rows of a sweep with a footfall spec): stride_hz_db and duty_db, the debounced stride frequency and duty factor (footfall_row, mean over
     the legs), the gait's name and, with a motor spec too, sat_max, the largest saturated fraction of a joint; recurrence (rows of a sweep with a recurrence spec): the
-    recurrence rate, the determinism, the longest diagonal line and the stride period too"""
+    recurrence rate, the determinism, the longest diagonal line and the stride period too; correlation (rows of a sweep with correlation=...):
+    corr_max, the largest |r| of a pair, with corr_leg and corr_unit, the x and the y column it belongs to"""
     keys = ("vx_body_mean", "vx_body_std", "z_mean", "z_std", "roll_std", "pitch_mean", "pitch_std", "yaw_rate_mean")
     staircase = bool(rows) and "level" in rows[0]              # one row per (condition, level): the level and its commanded v_x as well
     lead = ("mu", "delay", "cmd") + (("level", "cmd_level") if staircase else ()) + ("falls",)
@@ -2147,6 +2442,8 @@ def sweep_table(rows, gait=False, recurrence=False, footfall=False):
         out[0] += " " + " ".join("%-12s" % k for k in RECURRENCE_TABLE_KEYS)
     if footfall:
         out[0] += " " + " ".join("%-12s" % k for k in FOOTFALL_TABLE_KEYS)
+    if correlation:
+        out[0] += " " + " ".join("%-12s" % k for k in CORRELATION_TABLE_KEYS)
     for r in rows:
         lvl = "%-5d %-9g " % (r["level"], r["cmd_level"]) if staircase else ""
         out.append("%-6g %-5d %-5g %s%-5d " % (r["mu"], r["delay"], r["cmd"], lvl, r["falls"]) + " ".join("%+12.4f" % r[k] for k in keys))
@@ -2158,4 +2455,7 @@ def sweep_table(rows, gait=False, recurrence=False, footfall=False):
         if footfall:
             sat = float(np.nanmax(r["motor"]["saturated"])) if "motor" in r and not np.all(np.isnan(r["motor"]["saturated"])) else float("nan")
             out[-1] += " %+12.4f %+12.4f %-12s %+12.4f" % (r["footfall"]["stride_hz"], r["footfall"]["duty"], r["footfall"]["gait"], sat)
+        if correlation:
+            label = lambda v: "-" if v is None else v if isinstance(v, str) else ":".join(str(p) for p in v)
+            out[-1] += " %+12.4f %-12s %-12s" % (r["corr_max"], label(r["corr_leg"]), label(r["corr_unit"]))
     return "\n".join(out)

@@ -806,6 +806,72 @@ int irrl_eval_motor_plane(const float *rec_gait, const uint8_t *rec_done, int ro
                           int frame_every, int frames, const irrl_eval_motor_spec *spec, uint32_t *counts, uint32_t *hist, double *fold,
                           void *hip_stream);
 
+/* TRACE RECORDERS OF THE FIVE-LAUNCH EVALUATION LOOP: what the policy holds inside, per control step (the reference's `--corr` path records
+ * CustomerLstmNN.get_hidden_state after every predict, run_bp_v5.py:458-460; its `--val` path the critic's value).  irrl_eval_trace is a HOST
+ * struct of device pointers, each may be NULL (but not both):
+ *   rec_lstm  f32 [steps, N, 4 * hid]  the ACTOR's half of lstm_state, c0 | h0 | c1 | h1 (lstm_state[:, 0 : 4 hid]), AFTER step k's policy step:
+ *                                      row k holds the state that has consumed step k's observation, reset included where `done` was set
+ *   rec_value f32 [steps, N]           the critic's value of step k (the `value` column of the work array)
+ * irrl_lstm_eval_traced is irrl_lstm_eval_measured with the struct behind `gait`; irrl_mlp_eval_traced is irrl_mlp_eval_measured with it, and
+ * refuses rec_lstm: MlpPolicy has no recurrent state.  With a trace the loop makes ONE extra launch per step between the policy step and the action
+ * filter (irrl_eval_trace_kernel, csrc/eval_rollout.hpp: a lane per (env, column), both copies coalesced); trace == NULL is the measured call,
+ * launch for launch.  Every other buffer is bit-identical to the call without the trace.  There is NO persistent form: the persistent kernel
+ * keeps the state in LDS that is full, and does not run the critic at all.
+ * Errors (non-zero, irrl_last_error() set with the entry point's own name, checked before any HIP call): the refusals of the measured calls;
+ * a trace whose two pointers are both NULL; rec_lstm with irrl_mlp_eval_traced. */
+typedef struct irrl_eval_trace {
+  float *rec_lstm;
+  float *rec_value;
+} irrl_eval_trace;
+int irrl_lstm_eval_traced(irrl_env *env, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *lstm_w, const float *pi_w,
+                          const float *pi_b, const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring, float *cmd, float *vel_his,
+                          float *act_his, float *lstm_state, uint8_t *done, float *obs, float *work, const int *delay, const float *cmd_target, float a_cmd,
+                          float a_vel, float a_act, const float *cmd_mean, const float *cmd_std, int clip, float *rec_obs_cond, float *rec_act_clipped,
+                          float *rec_act_applied, float *rec_body, float *rec_torque, float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats,
+                          const irrl_eval_scenario *scenario, const irrl_eval_kicks *kicks, const irrl_eval_gait *gait, const irrl_eval_trace *trace,
+                          void *hip_stream);
+int irrl_mlp_eval_traced(irrl_env *env, int steps, long long step0, int hid, int ob_dim, int act_dim, const float *const *mlp_w, const float *pi_w,
+                         const float *pi_b, const float *vf_w, const float *vf_b, const float *logstd, int depth, float *ring, float *cmd, float *vel_his,
+                         float *act_his, uint8_t *done, float *obs, float *work, const int *delay, const float *cmd_target, float a_cmd, float a_vel,
+                         float a_act, const float *cmd_mean, const float *cmd_std, int clip, float *rec_obs_cond, float *rec_act_clipped,
+                         float *rec_act_applied, float *rec_body, float *rec_torque, float *rec_obs_raw, float *rec_reward, uint8_t *rec_done, double *stats,
+                         const irrl_eval_scenario *scenario, const irrl_eval_kicks *kicks, const irrl_eval_gait *gait, const irrl_eval_trace *trace,
+                         void *hip_stream);
+
+/* CORRELATION MOMENTS OF TWO RECORDER WINDOWS: the sums a Pearson correlation (or a covariance, or a PCA) of recorder columns needs -- the
+ * reference's `--corr` figure, contact flags x LSTM units (run_bp_v5.py:1032-1088), and its full df.corr().  x is device f32 [rows, num_envs,
+ * x_dim], of which the columns x_first .. x_first + x_count are analysed; y the same with its own three numbers; x and y may be the same buffer
+ * and window.  Frames and T_e are irrl_eval_motor_plane's: analysed frame i is recorder row irrl_eval_recurrence_row(frame_first, frame_every, i),
+ * T_e = the first analysed frame whose rec_done word is non-zero (rec_done NULL: T_e = frames); env index = condition * robots + robot, per-robot
+ * matrices are conditions = num_envs, robots = 1.  Outputs per condition g over the samples i < T_e of its robots:
+ *   count[g] i64            sum of T_e
+ *   sx[g, cx, 2] f64        sum x, sum x^2          sy[g, cy, 2] f64   the same of y
+ *   sxy[g, cx, cy] f64      sum x y
+ *   range_x[g, cx, 2] f32, range_y[g, cy, 2] f32 (NULL: off)   min, max over the pooled samples, (+inf, -inf) when there are none: what tells a
+ *                           constant column EXACTLY (n sum x^2 - (sum x)^2 is not to be trusted to be 0)
+ * THE ONE ORDER (csrc/eval_elements.hpp irrl_eval_corr_add): per robot every accumulator starts at +0.0 and takes its frames in ascending order
+ * as s = s + (double)a * (double)b (sum x: b = 1); the condition's total starts at +0.0 and takes its robots' partials in ascending robot order.
+ * The product of two f32 is exact in f64, so a fused multiply-add and a multiply and an add give the same bits: device, host and numpy agree bit
+ * for bit.  No atomics; nothing depends on the order in which waves arrive.  min / max keep m unless v < m (v > m): a NaN sample never enters a
+ * range.  A non-finite sample poisons the accumulators of its own column (pairs) and no other.
+ * work: device f64 [irrl_eval_correlation_work(num_envs, spec)] = num_envs * (cx cy + 3 cx + 3 cy + 1) doubles, the robots' partials; needed with
+ * robots > 1, may be NULL with robots == 1 (the first kernel then writes the outputs itself).  irrl_eval_correlation_work needs no GPU; 0 for a
+ * NULL or refused spec or num_envs < 1.
+ * Refused before any HIP call with "irrl_eval_correlation: " in front of the text: NULL x, y, spec, count, sx, sy or sxy; x_dim or y_dim < 1, a
+ * window outside its row width; x_count outside 1 .. IRRL_EVAL_CORR_MAX_X; y_count outside 1 .. IRRL_EVAL_CORR_MAX_Y; num_envs < 1, conditions or
+ * robots < 1, conditions * robots != num_envs; frames outside 1 .. IRRL_EVAL_CORR_MAX_FRAMES; frame_first < 0, frame_every < 1, frame_first +
+ * (frames - 1) * frame_every >= rows; robots > 1 with work NULL. */
+#define IRRL_EVAL_CORR_MAX_FRAMES 16384
+#define IRRL_EVAL_CORR_MAX_X 64
+#define IRRL_EVAL_CORR_MAX_Y 1024
+typedef struct irrl_eval_corr_spec {
+  int x_dim, x_first, x_count, y_dim, y_first, y_count;
+} irrl_eval_corr_spec;
+size_t irrl_eval_correlation_work(int num_envs, const irrl_eval_corr_spec *spec);
+int irrl_eval_correlation(const float *x, const float *y, const uint8_t *rec_done, int rows, int num_envs, int conditions, int robots,
+                          int frame_first, int frame_every, int frames, const irrl_eval_corr_spec *spec, int64_t *count, double *sx, double *sy,
+                          double *sxy, float *range_x, float *range_y, double *work, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,9 @@ reference's own (run_bp_v5.py:8-13), resolved by the compat packages at the repo
     python scripts/run_bp_v5.py --test --sweep --model data/..._final.pkl --sweep_cmd 2,5 --footfall [--motor] --out sweep.json
                                                                                            # + debounced stride frequency, duty, the gait's name
                                                                                            # [+ motor saturation]; gait diagrams and maps to --out
+    python scripts/run_bp_v5.py --test --sweep --model data/..._final.pkl --sweep_cmd 2,5 --corr [--corr_x contact --corr_y lstm] --out sweep.json
+                                                                                           # + the largest correlation of a foot-contact flag with
+                                                                                           # an LSTM unit, its leg and unit; the matrices to --out
     python scripts/run_bp_v5.py --test --sweep --step --gait --model data/..._final.pkl --persistent on   # cost of transport, duty factors and
                                                                                            # touchdown rate per (friction, command level)
 
@@ -124,6 +127,13 @@ def parse_args(argv):
     p.add_argument("--motor", dest="flag_motor", action="store_true", default=False,
                    help="--footfall: the motor's torque-speed plane per condition and joint on the device (evaluate.motor_spec of the config): the table "
                         "gains sat_max; --out also gets the folded loops and the 2-D maps (`hist`) of the first 8 conditions")
+    p.add_argument("--corr", dest="flag_corr", action="store_true", default=False,
+                   help="--sweep: the reference's --corr -- the Pearson correlation of two recorded quantities per robot on the device over the measured "
+                        "steps (evaluate.CORR_SOURCES; by default the four foot-contact flags against every LSTM cell and hidden unit, recorded after "
+                        "each policy step): the table gains corr_max, corr_leg and corr_unit; --out also gets the matrices of the first 8 conditions. "
+                        "The measured steps run in the five-launch form (the LSTM state's recorder is steps x robots x 4 hid x 4 B)")
+    p.add_argument("--corr_x", type=str, default="contact", help="--corr: the x source, one of contact, torque, joint_rate, body, obs, action, lstm, value")
+    p.add_argument("--corr_y", type=str, default="lstm", help="--corr: the y source (an MlpPolicy checkpoint has no recurrent state: choose another than lstm)")
     p.add_argument("--recurrence_frames", type=int, default=None, help="--recurrence: the last so many frames of the run are analysed (default: min(steps, 800))")
     p.add_argument("--recurrence_radius", type=int, default=None, help="--recurrence: the recurrence radius in levels of 0.001 (default 10)")
     return p.parse_args(argv)
@@ -148,6 +158,19 @@ def footfall_keywords(args, env_cfg):
     if not args.flag_footfall:
         return {}
     return dict(footfall=dict(FOOTFALL_SPEC_REFERENCE), motor=motor_spec(env_cfg) if args.flag_motor else None)
+
+
+def correlation_keywords(args):
+    """--corr [--corr_x NAME --corr_y NAME] -> the keywords of robustness_sweep"""
+    from high_speed_quadrupedal_locomotion_by_irrl_amd.evaluate import CORR_SOURCES
+    if not args.flag_corr:
+        return {}
+    for k in (args.corr_x, args.corr_y):
+        if k not in CORR_SOURCES:
+            raise SystemExit("--corr_x / --corr_y: %r is none of %s" % (k, ", ".join(sorted(CORR_SOURCES))))
+    if args.persistent == "on":
+        raise SystemExit("--corr records inside the policy, which only the five-launch form of the loop can: --persistent auto or off")
+    return dict(correlation=dict(x=args.corr_x, y=args.corr_y))
 
 
 def plain(v):
@@ -239,13 +262,18 @@ def run_sweep(args, cfg):
     # --step: four levels of --step_steps steps in place of --steps, one row per condition and level; --dir_fd: the heading hold on every env.
     # Still one pool and one call per run: with --persistent on, one launch (two with a warm-up).
     gait = dict(gait=True, mass=args.gait_mass, g=args.gait_g) if args.flag_gait else {}
-    rows = robustness_sweep(args.trained_model, cfg["environment"], args.sweep_mu, args.sweep_delay, args.sweep_cmd, warm_steps=args.warm, steps=args.steps,
-                            cmd_hz=args.cmd_filter_freq, vel_hz=none_if_off(args.vel_filter_freq), act_hz=none_if_off(args.act_filter_freq),
-                            persistent=PERSISTENT_DEFAULT if args.persistent is None else args.persistent,
-                            levels=4 if args.flag_step else None, level_steps=args.step_steps if args.flag_step else None,
-                            heading=heading_hold(n) if args.flag_dir_fd else None, **gait, **recurrence_keywords(args),
-                            **footfall_keywords(args, cfg["environment"]))
-    print(sweep_table(rows, gait=args.flag_gait, recurrence=args.flag_recurrence, footfall=args.flag_footfall))
+    keywords = dict(warm_steps=args.warm, steps=args.steps, cmd_hz=args.cmd_filter_freq, vel_hz=none_if_off(args.vel_filter_freq),
+                    act_hz=none_if_off(args.act_filter_freq), persistent=PERSISTENT_DEFAULT if args.persistent is None else args.persistent,
+                    levels=4 if args.flag_step else None, level_steps=args.step_steps if args.flag_step else None,
+                    heading=heading_hold(n) if args.flag_dir_fd else None, **gait, **recurrence_keywords(args),
+                    **footfall_keywords(args, cfg["environment"]), **correlation_keywords(args))
+    try:
+        rows = robustness_sweep(args.trained_model, cfg["environment"], args.sweep_mu, args.sweep_delay, args.sweep_cmd, **keywords)
+    except ValueError as e:
+        if args.flag_corr and "no recurrent state" in str(e):      # an MlpPolicy checkpoint with --corr_y lstm (or --corr_x lstm)
+            raise SystemExit("--corr: %s" % e)
+        raise
+    print(sweep_table(rows, gait=args.flag_gait, recurrence=args.flag_recurrence, footfall=args.flag_footfall, correlation=args.flag_corr))
     if args.out:
         with open(args.out, "w") as f:                                 # (--recurrence: the level matrices of the first 8 conditions as nested lists)
             json.dump([{k: plain(v) for k, v in r.items()} for r in rows], f, indent=1)   # (--footfall / --motor: the patterns and the maps too)
