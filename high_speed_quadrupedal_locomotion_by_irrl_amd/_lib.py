@@ -151,6 +151,12 @@ SIGNATURES = {
     # `const irrl_eval_corr_spec *` (EvalCorrSpec below) | count, sx, sy, sxy, range_x, range_y, work | stream
     "irrl_eval_correlation": (C.c_int, [vp, vp, vp] + [C.c_int] * 7 + [vp] + [vp] * 7 + [vp]),
     "irrl_eval_correlation_work": (C.c_size_t, [C.c_int, vp]),
+    # the spectrogram and Welch spectrum of recorder columns: x, rec_done | rows, num_envs, conditions, robots, frame_first, frame_every, frames |
+    # `const irrl_eval_spectrum_spec *` (EvalSpectrumSpec below) | window, tw | segments, psd_sum, sxx, work | stream
+    "irrl_eval_spectrum": (C.c_int, [vp, vp] + [C.c_int] * 7 + [vp] + [vp] * 2 + [vp] * 4 + [vp]),
+    "irrl_eval_spectrum_work": (C.c_size_t, [C.c_int, vp]),
+    # HOST tables for it: nperseg, window_kind (0 boxcar, 1 Hann, 2 Tukey), alpha | window [nperseg], tw [nperseg, 2]
+    "irrl_eval_spectrum_tables": (C.c_int, [C.c_int, C.c_int, C.c_double, dp, dp]),
 }
 
 
@@ -207,6 +213,13 @@ class EvalTrace(C.Structure):
 class EvalCorrSpec(C.Structure):
     """struct irrl_eval_corr_spec of include/irrl_env.h (a HOST struct: row width, first column and column count of the x and of the y window)"""
     _fields_ = [(k, C.c_int) for k in ("x_dim", "x_first", "x_count", "y_dim", "y_first", "y_count")]
+
+
+class EvalSpectrumSpec(C.Structure):
+    """struct irrl_eval_spectrum_spec of include/irrl_env.h (a HOST struct: row width, first column and column count of the window, the segment
+    length and hop in frames, the detrend switch, the robots whose spectrograms are wanted, the sampling rate, the scale per analysed column)"""
+    _fields_ = [(k, C.c_int) for k in ("x_dim", "x_first", "x_count", "nperseg", "hop", "detrend", "matrix_count")] + \
+               [("matrix_env", C.c_int * 8), ("fs", C.c_double), ("scale", C.c_double * 64)]
 
 
 def load():

@@ -105,7 +105,7 @@ EVAL_MLP_UNIT_FLAGS = ["-DIRRL_LANES_PER_ROBOT=16", "-DIRRL_EVAL_MLP_UNIT"]
 
 # the translation units that go through the plain compiler driver, in link order behind the env objects: the C-ABI + LSTM kernels and one unit
 # per analysis of a recorder.  build() and tools/build_variants.py both take them from here (the C-ABI unit references every launcher).
-PLAIN_UNITS = ["irrl_env_abi.hip", "eval_ensemble.hip", "eval_recurrence.hip", "eval_footfall.hip", "eval_correlation.hip"]
+PLAIN_UNITS = ["irrl_env_abi.hip", "eval_ensemble.hip", "eval_recurrence.hip", "eval_footfall.hip", "eval_spectrum.hip", "eval_correlation.hip"]
 
 
 def llvm_bin():

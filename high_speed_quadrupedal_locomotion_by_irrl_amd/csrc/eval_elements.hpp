@@ -539,3 +539,101 @@ static inline const char *irrl_eval_corr_spec_error(const irrl_eval_corr_spec &s
   if (s.y_first < 0 || (long long)s.y_first + (long long)s.y_count > (long long)s.y_dim) return "the y window y_first .. y_first + y_count lies outside the row width y_dim";
   return NULL;
 }
+
+// ---- the spectrogram and the Welch spectrum of recorder columns (irrl_eval_spectrum, include/irrl_env.h) ----
+// scipy.signal.spectrogram(mode='psd', scaling='density', return_onesided=True, nfft=nperseg) as a direct DFT, every step in f64.  The steps that
+// are a product next to a sum are statements of their own, so that no compiler fuses them (the library is built with -ffp-contract=on) -- all
+// but THE accumulation, irrl_eval_spectrum_add, which is written as one expression: the device fuses it, a host without a fused multiply-add
+// does not, and the tests' bound (n 2^-53 sum |a_n| per dot product, in any order, fused or not) covers both.
+static inline IRRL_EVAL_FN int irrl_eval_spectrum_bins(int nperseg) { return nperseg / 2 + 1; }
+// S_e: the segments s * hop .. s * hop + nperseg - 1 that lie wholly inside the frames i < T_e
+static inline IRRL_EVAL_FN int irrl_eval_spectrum_segments(int te, int nperseg, int hop) { return te >= nperseg ? (te - nperseg) / hop + 1 : 0; }
+// v_n = (double)x_n * scale[c]
+static inline IRRL_EVAL_FN double irrl_eval_spectrum_sample(float x, double scale) { return (double)x * scale; }
+// m = (((zero + v_0) + v_1) + ...) / nperseg over the words v[0], v[stride], ...; zero is +0.0 (why it is an argument: eval_correlation.hip)
+static inline IRRL_EVAL_FN double irrl_eval_spectrum_mean(const double *v, size_t stride, int nperseg, double zero) {
+  double t = zero;
+  for (int n = 0; n < nperseg; n++) t = t + v[(size_t)n * stride];
+  return t / (double)nperseg;
+}
+// a_n = (v_n - m) * window[n]; without a detrend nothing is subtracted (not even 0.0: -0.0 stays what it is)
+static inline IRRL_EVAL_FN double irrl_eval_spectrum_windowed(double v, double m, int detrend, double w) {
+  const double d = detrend ? v - m : v;
+  return d * w;
+}
+// THE accumulation of Re_k (t = cos) and of -Im_k (t = sin): s + a * t, n ascending
+static inline IRRL_EVAL_FN double irrl_eval_spectrum_add(double s, double a, double t) { return s + a * t; }
+// the next (k n) mod nperseg out of the last, 0 <= k < nperseg
+static inline IRRL_EVAL_FN int irrl_eval_spectrum_step(int j, int k, int nperseg) {
+  const int next = j + k;
+  return next >= nperseg ? next - nperseg : next;
+}
+// g_k: 2, except g_0 = 1 and, with an even nperseg, g_{K-1} = 1 (the bins without a mirror image)
+static inline IRRL_EVAL_FN double irrl_eval_spectrum_gain(int k, int nperseg) { return (k == 0 || 2 * k == nperseg) ? 1.0 : 2.0; }
+// P_k = g_k * density * (Re_k^2 + Im_k^2) with Im_k = -sim, the negated sum of the sines
+static inline IRRL_EVAL_FN double irrl_eval_spectrum_power(double re, double sim, double gain, double density) {
+  const double im = -sim;
+  const double re2 = re * re;
+  const double im2 = im * im;
+  const double mag2 = re2 + im2;
+  const double f = gain * density;
+  return f * mag2;
+}
+// density = 1 / (fs * sum_n window[n]^2), the squares added in ascending order from zero = +0.0 (a square is never -0.0: the argument is there
+// for the rule's sake); once per workgroup on the device, the window is the caller's device table
+static inline IRRL_EVAL_FN double irrl_eval_spectrum_density(const double *window, int nperseg, double fs, double zero) {
+  double t = zero;
+  for (int n = 0; n < nperseg; n++) {
+    const double sq = window[n] * window[n];
+    t = t + sq;
+  }
+  const double d = fs * t;
+  return 1.0 / d;
+}
+// the doubles of `work` per robot: the partials [cx, K] and S_e as an int64
+static inline IRRL_EVAL_FN size_t irrl_eval_spectrum_work_per_env(const irrl_eval_spectrum_spec &s) {
+  return (size_t)s.x_count * (size_t)irrl_eval_spectrum_bins(s.nperseg) + 1;
+}
+// what is wrong with a spec, or NULL (the matrix_env range needs num_envs: the call checks it)
+static inline const char *irrl_eval_spectrum_spec_error(const irrl_eval_spectrum_spec &s) {
+  if (s.x_dim < 1) return "x_dim >= 1";
+  if (s.x_count < 1 || s.x_count > IRRL_EVAL_SPECTRUM_MAX_X) return "x_count lies in 1 .. 64";
+  if (s.x_first < 0 || (long long)s.x_first + (long long)s.x_count > (long long)s.x_dim) return "the x window x_first .. x_first + x_count lies outside the row width x_dim";
+  if (s.nperseg < 8 || s.nperseg > IRRL_EVAL_SPECTRUM_MAX_NPERSEG) return "nperseg lies in 8 .. 1024";
+  if (s.hop < 1 || s.hop > s.nperseg) return "hop lies in 1 .. nperseg";
+  if (s.detrend < 0 || s.detrend > 1) return "detrend lies in 0 .. 1";
+  if (!irrl_eval_ensemble_finite(s.fs) || !(s.fs > 0.0)) return "fs > 0, finite";
+  for (int c = 0; c < s.x_count; c++)
+    if (!irrl_eval_ensemble_finite(s.scale[c]) || !(s.scale[c] > 0.0)) return "scale_c > 0, finite, for every analysed column";
+  if (s.matrix_count < 0 || s.matrix_count > IRRL_EVAL_SPECTRUM_MAX_MATRICES) return "matrix_count lies in 0 .. 8";
+  return NULL;
+}
+// what is wrong with the arguments of irrl_eval_spectrum_tables, or NULL
+static inline const char *irrl_eval_spectrum_tables_error(int nperseg, int window_kind, double alpha, const double *window, const double *tw) {
+  if (!window || !tw) return "NULL window or tw";
+  if (nperseg < 8 || nperseg > IRRL_EVAL_SPECTRUM_MAX_NPERSEG) return "nperseg lies in 8 .. 1024";
+  if (window_kind < 0 || window_kind > 2) return "window_kind lies in 0 .. 2 (boxcar, Hann, Tukey)";
+  if (!irrl_eval_ensemble_finite(alpha)) return "alpha is finite";
+  return NULL;
+}
+// The tables of irrl_eval_spectrum_tables (include/irrl_env.h states the formulas against scipy's): window [nperseg], tw [nperseg, 2].  Host code.
+static inline void irrl_eval_spectrum_tables_fill(int nperseg, int window_kind, double alpha, double *window, double *tw) {
+  const double pi = 3.14159265358979323846;
+  if (window_kind == 2 && alpha <= 0.0) window_kind = 0;
+  if (window_kind == 2 && alpha >= 1.0) window_kind = 1;
+  const int M = nperseg + 1;                                   // the periodic window: the symmetric one of M samples without its last
+  const int width = window_kind == 2 ? (int)floor(alpha * (double)(M - 1) / 2.0) : 0;
+  for (int n = 0; n < nperseg; n++) {
+    double w = 1.0;
+    if (window_kind == 1) {
+      w = 0.5 - 0.5 * cos(2.0 * pi * (double)n / (double)nperseg);
+    } else if (window_kind == 2) {
+      if (n <= width) w = 0.5 * (1.0 + cos(pi * (-1.0 + 2.0 * (double)n / alpha / (double)(M - 1))));
+      else if (n >= M - width - 1) w = 0.5 * (1.0 + cos(pi * (-2.0 / alpha + 1.0 + 2.0 * (double)n / alpha / (double)(M - 1))));
+    }
+    window[n] = w;
+    const double phi = 2.0 * pi * (double)n / (double)nperseg;
+    tw[2 * n] = cos(phi);
+    tw[2 * n + 1] = sin(phi);
+  }
+}

@@ -25,6 +25,7 @@
 #include "eval_recurrence.hpp"  // the recurrence analysis: argument block and launcher of csrc/eval_recurrence.hip (irrl_eval_recurrence below)
 #include "eval_footfall.hpp"    // the gait recorder's analyses: argument blocks and launchers of csrc/eval_footfall.hip
 #include "eval_correlation.hpp"  // the correlation moments: argument block and launcher of csrc/eval_correlation.hip (irrl_eval_correlation below)
+#include "eval_spectrum.hpp"     // the spectrogram: argument block and launcher of csrc/eval_spectrum.hip (irrl_eval_spectrum below)
 
 #include <cmath>
 #include <string>
@@ -1547,6 +1548,66 @@ int irrl_eval_correlation(const float *x, const float *y, const uint8_t *rec_don
     a.sxy = sxy; a.sx = sx; a.sy = sy; a.count = count; a.range_x = ranges ? range_x : nullptr; a.range_y = ranges ? range_y : nullptr;
   }
   HIP_TRY(irrl_eval_correlation_launch(a, (hipStream_t)hip_stream));
+  return 0;
+}
+
+// ---- spectrogram and Welch spectrum of recorder columns (kernels and launcher: csrc/eval_spectrum.hip; every step: csrc/eval_elements.hpp) ----
+int irrl_eval_spectrum_tables(int nperseg, int window_kind, double alpha, double *window, double *tw) {
+  if (const char *bad = irrl_eval_spectrum_tables_error(nperseg, window_kind, alpha, window, tw)) {
+    g_err = std::string("irrl_eval_spectrum_tables: ") + bad; return 1;
+  }
+  irrl_eval_spectrum_tables_fill(nperseg, window_kind, alpha, window, tw);
+  return 0;
+}
+
+size_t irrl_eval_spectrum_work(int num_envs, const irrl_eval_spectrum_spec *spec) {
+  if (!spec || num_envs < 1 || irrl_eval_spectrum_spec_error(*spec)) return 0;
+  return (size_t)num_envs * irrl_eval_spectrum_work_per_env(*spec);
+}
+
+// zero `bytes` at p on the stream; memory that HIP does not know as a device's (or as managed) is the host's own and is written here
+static hipError_t spectrum_zero(void *p, size_t bytes, hipStream_t stream) {
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, p) == hipSuccess && (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged))
+    return hipMemsetAsync(p, 0, bytes, stream);
+  (void)hipGetLastError();
+  memset(p, 0, bytes);
+  return hipSuccess;
+}
+
+int irrl_eval_spectrum(const float *x, const uint8_t *rec_done, int rows, int num_envs, int conditions, int robots, int frame_first,
+                       int frame_every, int frames, const irrl_eval_spectrum_spec *spec, const double *window, const double *tw,
+                       int64_t *segments, double *psd_sum, double *sxx, double *work, void *hip_stream) {
+  const std::string w = "irrl_eval_spectrum: ";
+  if (!x || !spec || !window || !tw || !segments || !psd_sum) { g_err = w + "NULL x, spec, window, tw, segments or psd_sum"; return 1; }
+  if (const char *bad = irrl_eval_spectrum_spec_error(*spec)) { g_err = w + "spec: " + bad; return 1; }
+  if (frames < 1) { g_err = w + "frames lies in 1 .. 16384"; return 1; }
+  if (const char *bad = gait_window_error(rows, num_envs, frame_first, frame_every, frames, IRRL_EVAL_SPECTRUM_MAX_FRAMES)) { g_err = w + bad; return 1; }
+  if (conditions < 1 || robots < 1 || (long long)conditions * (long long)robots != (long long)num_envs) {
+    g_err = w + "conditions >= 1, robots >= 1, conditions * robots == num_envs"; return 1;
+  }
+  if (spec->matrix_count > 0 && !sxx) { g_err = w + "matrix_count > 0 with a NULL sxx"; return 1; }
+  for (int m = 0; m < spec->matrix_count; m++)
+    if (spec->matrix_env[m] < 0 || spec->matrix_env[m] >= num_envs) { g_err = w + "a matrix_env lies outside 0 .. num_envs - 1"; return 1; }
+  if (robots > 1 && !work) { g_err = w + "robots > 1 needs work (irrl_eval_spectrum_work doubles)"; return 1; }
+  const int K = irrl_eval_spectrum_bins(spec->nperseg);
+  if (frames < spec->nperseg) {                // no segment anywhere: nothing to launch (and no tables to read)
+    HIP_TRY(spectrum_zero(segments, (size_t)conditions * sizeof(int64_t), (hipStream_t)hip_stream));
+    HIP_TRY(spectrum_zero(psd_sum, (size_t)conditions * (size_t)spec->x_count * (size_t)K * sizeof(double), (hipStream_t)hip_stream));
+    return 0;
+  }
+  SpectrumArgs a = SpectrumArgs();
+  a.x = x; a.rec_done = rec_done; a.window = window; a.tw = tw; a.N = num_envs; a.C = conditions; a.R = robots; a.T = frames;
+  a.frame_first = frame_first; a.frame_every = frame_every; a.K = K; a.S_max = irrl_eval_spectrum_segments(frames, spec->nperseg, spec->hop);
+  a.spec = *spec; a.zero = 0.0;
+  a.sxx = spec->matrix_count > 0 ? sxx : nullptr;
+  if (robots == 1) {
+    a.p_psd = psd_sum; a.p_seg = segments;
+  } else {
+    irrl_eval_spectrum_work_regions(a, work);
+    a.psd_sum = psd_sum; a.segments = segments;
+  }
+  HIP_TRY(irrl_eval_spectrum_launch(a, (hipStream_t)hip_stream));
   return 0;
 }
 

@@ -1746,6 +1746,262 @@ def correlation_row(m, names, g=0):
     return dict(corr_max=float(abs(r[i, j])), corr_r=float(r[i, j]), corr_leg=leg, corr_unit=correlation_unit(y_name, j, r.shape[1]))
 
 
+# ---- spectrogram and Welch spectrum of recorder columns (irrl_eval_spectrum) ----
+SPECTRUM_MAX_FRAMES = 16384      # IRRL_EVAL_SPECTRUM_MAX_FRAMES
+SPECTRUM_MAX_X = 64              # IRRL_EVAL_SPECTRUM_MAX_X
+SPECTRUM_MAX_NPERSEG = 1024      # IRRL_EVAL_SPECTRUM_MAX_NPERSEG
+SPECTRUM_MAX_MATRICES = 8        # IRRL_EVAL_SPECTRUM_MAX_MATRICES; robustness_sweep: the rows of the first 8 conditions carry the spectrogram
+SPECTRUM_WINDOWS = {"boxcar": 0, "hann": 1, "tukey": 2}      # the window_kind of irrl_eval_spectrum_tables
+# name -> (recorder of PolicyEvaluator.run, first column, count): what the reference's --virba plots (run_bp_v5.py:1090-1117)
+SPECTRUM_SOURCES = {"joint": ("obs_cond", 5, 12), "joint_rate": ("obs_cond", 17, 12), "action": ("act_applied", 0, 12)}
+# the reference's bare scipy.signal.spectrogram(column, fs): Tukey(0.25), 256 frames per segment, 32 of them shared, a constant detrend; and the
+# 50 Hz of its set_ylim([0, 50]) as the band above which power counts as vibration
+SPECTRUM_REFERENCE = dict(nperseg=256, hop=224, window="tukey", alpha=0.25, detrend=1, band_hz=50.0)
+
+
+def spectrum_spec(x_dim, x_first, x_count, nperseg, hop, fs, scale=None, detrend=1, matrix_env=()):
+    """The spec of irrl_eval_spectrum: of rows x_dim floats wide the columns x_first .. x_first + x_count are analysed in segments of nperseg
+    frames, hop frames apart, sampled at fs Hz; scale: one factor per analysed column (None: 1.0), detrend: 1 subtracts each segment's mean,
+    matrix_env: up to 8 robots whose spectrograms are wanted.  -> dict, refused like the C call refuses its struct"""
+    s = dict(x_dim=int(x_dim), x_first=int(x_first), x_count=int(x_count), nperseg=int(nperseg), hop=int(hop), fs=float(fs), detrend=int(detrend),
+             matrix_env=tuple(int(e) for e in matrix_env))
+    if s["x_dim"] < 1:
+        raise ValueError("spectrum spec: x_dim >= 1")
+    if not 1 <= s["x_count"] <= SPECTRUM_MAX_X:
+        raise ValueError("spectrum spec: x_count lies in 1 .. %d" % SPECTRUM_MAX_X)
+    if s["x_first"] < 0 or s["x_first"] + s["x_count"] > s["x_dim"]:
+        raise ValueError("spectrum spec: the x window lies outside the row width")
+    if not 8 <= s["nperseg"] <= SPECTRUM_MAX_NPERSEG:
+        raise ValueError("spectrum spec: nperseg lies in 8 .. %d" % SPECTRUM_MAX_NPERSEG)
+    if not 1 <= s["hop"] <= s["nperseg"]:
+        raise ValueError("spectrum spec: hop lies in 1 .. nperseg")
+    if s["detrend"] not in (0, 1):
+        raise ValueError("spectrum spec: detrend lies in 0 .. 1")
+    if not (math.isfinite(s["fs"]) and s["fs"] > 0):
+        raise ValueError("spectrum spec: fs > 0, finite")
+    sc = np.ones(s["x_count"]) if scale is None else np.asarray(scale, np.float64).reshape(-1)
+    if sc.shape != (s["x_count"],) or not np.all(np.isfinite(sc) & (sc > 0)):
+        raise ValueError("spectrum spec: scale holds x_count factors > 0, finite")
+    s["scale"] = tuple(float(v) for v in sc)
+    if len(s["matrix_env"]) > SPECTRUM_MAX_MATRICES:
+        raise ValueError("spectrum spec: matrix_env lists at most %d robots" % SPECTRUM_MAX_MATRICES)
+    return s
+
+
+def spectrum_bins(nperseg):
+    return int(nperseg) // 2 + 1
+
+
+def spectrum_frequencies(nperseg, fs):
+    """the frequency of every bin, k fs / nperseg (scipy's rfftfreq)"""
+    return np.arange(spectrum_bins(nperseg)) * (float(fs) / int(nperseg))
+
+
+def spectrum_tables(nperseg, window="tukey", alpha=0.25):
+    """-> (window float64 [nperseg], tw float64 [nperseg, 2] = cos, sin of 2 pi j / nperseg), filled by the library's host helper
+    irrl_eval_spectrum_tables (no GPU): the device call, the twin, the host program and the tests all read THESE bits, so the tables' rounding
+    drops out of every comparison.  window: a name out of SPECTRUM_WINDOWS; alpha: Tukey's taper fraction"""
+    from . import _lib
+    if window not in SPECTRUM_WINDOWS:
+        raise KeyError("unknown window %r: choose from %s" % (window, sorted(SPECTRUM_WINDOWS)))
+    nperseg = int(nperseg)
+    if not 8 <= nperseg <= SPECTRUM_MAX_NPERSEG:
+        raise ValueError("nperseg lies in 8 .. %d" % SPECTRUM_MAX_NPERSEG)
+    win, tw = np.zeros(nperseg), np.zeros((nperseg, 2))
+    _lib.check(_lib.load().irrl_eval_spectrum_tables(nperseg, SPECTRUM_WINDOWS[window], float(alpha), win.ctypes.data_as(_lib.dp), tw.ctypes.data_as(_lib.dp)))
+    return win, tw
+
+
+def _spectrum_frames(rows, frame_first, frame_every, frames):
+    frame_first, frame_every, T = _gait_frames(rows, frame_first, frame_every, frames, SPECTRUM_MAX_FRAMES)
+    if T < 1:
+        raise ValueError("frames lies in 1 .. %d" % SPECTRUM_MAX_FRAMES)
+    return frame_first, frame_every, T
+
+
+def _spectrum_tables_check(window, tw, nperseg):
+    window, tw = np.asarray(window), np.asarray(tw)
+    if window.shape != (nperseg,) or tw.shape != (nperseg, 2) or window.dtype != np.float64 or tw.dtype != np.float64:
+        raise ValueError("window: float64 [nperseg], tw: float64 [nperseg, 2] (spectrum_tables)")
+    return window, tw
+
+
+def spectrum_numpy(x, rec_done, spec, window, tw, conditions=None, frame_first=0, frame_every=1, frames=None, windowed=False):
+    """The twin of irrl_eval_spectrum (include/irrl_env.h): x float32 [rows, N, x_dim], rec_done [rows, N] or None, window / tw the tables of
+    spectrum_tables, env = condition * robots + robot (conditions None: N, one robot each) -> dict(segments int64 [G], psd_sum float64 [G, cx, K],
+    sxx float64 [M, cx, S_max, K] for the robots spec["matrix_env"] (None without any)).  Written in the stated order: per segment an explicit
+    loop over n for the detrend's sum and for the DFT's two sums (every robot, column and bin at once, each as s = s + a * t from +0.0 with the
+    twiddle at (k n) mod nperseg), then the power as (g_k density) (Re^2 + Im^2); the segments in ascending order from +0.0, then a condition's
+    robots in ascending order from +0.0.  windowed=True: the result also carries `a` float64 [N, S_max, cx, nperseg], the detrended and windowed
+    segments (0 where a robot has none), from which a test computes its bound."""
+    s = spectrum_spec(**spec)
+    cx, P, hop, K = s["x_count"], s["nperseg"], s["hop"], spectrum_bins(s["nperseg"])
+    window, tw = _spectrum_tables_check(window, tw, P)
+    x = np.asarray(x)
+    if x.ndim != 3 or x.shape[2] != s["x_dim"] or x.dtype != np.float32:
+        raise ValueError("x: float32 [rows, N, %d]" % s["x_dim"])
+    rows, N = x.shape[:2]
+    Cn, R = _motor_shape(N, N if conditions is None else conditions)
+    frame_first, frame_every, T = _spectrum_frames(rows, frame_first, frame_every, frames)
+    if any(e < 0 or e >= N for e in s["matrix_env"]):
+        raise ValueError("a matrix_env lies outside 0 .. N - 1")
+    sel = frame_first + frame_every * np.arange(T)
+    te = np.full(N, T, np.int64)
+    if rec_done is not None:
+        done = np.asarray(rec_done)
+        if done.shape != (rows, N):
+            raise ValueError("rec_done [rows, N]")
+        dn = done[sel] != 0
+        te = np.where(dn.any(0), dn.argmax(0), T).astype(np.int64)
+    S = np.where(te >= P, (te - P) // hop + 1, 0).astype(np.int64)
+    S_max = (T - P) // hop + 1 if T >= P else 0
+    xw = x[sel][:, :, s["x_first"]:s["x_first"] + cx]                 # float32 [T, N, cx]
+    scale = np.asarray(s["scale"], np.float64)
+    t = 0.0
+    for n in range(P):
+        t = t + window[n] * window[n]
+    density = 1.0 / (s["fs"] * t)
+    k = np.arange(K)
+    gain = np.where((k == 0) | (2 * k == P), 1.0, 2.0)
+    factor = gain * density
+    part = np.zeros((N, cx, K))
+    M = len(s["matrix_env"])
+    sxx = np.zeros((M, cx, S_max, K)) if M else None
+    a_all = np.zeros((N, S_max, cx, P)) if windowed else None
+    with np.errstate(invalid="ignore", over="ignore"):
+        for seg in range(int(S.max()) if N else 0):                # segments in ascending order
+            on = seg < S
+            v = xw[seg * hop:seg * hop + P].astype(np.float64) * scale          # [P, N, cx]
+            if s["detrend"]:
+                m = np.zeros((N, cx))
+                for n in range(P):
+                    m = m + v[n]
+                m = m / float(P)
+                v = v - m
+            a = v * window[:, None, None]
+            re, si = np.zeros((N, cx, K)), np.zeros((N, cx, K))
+            j = np.zeros(K, np.int64)
+            for n in range(P):                                     # samples in ascending order
+                re = re + a[n][:, :, None] * tw[j, 0]
+                si = si + a[n][:, :, None] * tw[j, 1]
+                j = (j + k) % P
+            im = -si
+            p = factor * (re * re + im * im)
+            part = np.where(on[:, None, None], part + p, part)
+            for mi, e in enumerate(s["matrix_env"]):
+                if on[e]:
+                    sxx[mi, :, seg, :] = p[e]
+            if windowed:
+                a_all[on, seg] = np.transpose(a, (1, 2, 0))[on]
+        part = part.reshape(Cn, R, cx, K)
+        tot = np.zeros((Cn, cx, K))
+        for r in range(R):                                         # robots in ascending order
+            tot = tot + part[:, r]
+    out = dict(segments=S.reshape(Cn, R).sum(1).astype(np.int64), psd_sum=tot, sxx=sxx)
+    if windowed:
+        out["a"] = a_all
+    return out
+
+
+def spectrum_struct(spec):
+    from . import _lib
+    s = spectrum_spec(**spec)
+    st = _lib.EvalSpectrumSpec(**{k: s[k] for k in ("x_dim", "x_first", "x_count", "nperseg", "hop", "detrend")}, matrix_count=len(s["matrix_env"]), fs=s["fs"])
+    for i, e in enumerate(s["matrix_env"]):
+        st.matrix_env[i] = e
+    for i, v in enumerate(s["scale"]):
+        st.scale[i] = v
+    return st
+
+
+def spectrum_work(num_envs, spec):
+    """the doubles of `work` for a pool of num_envs: irrl_eval_spectrum_work = num_envs * (cx K + 1)"""
+    s = spectrum_spec(**spec)
+    return int(num_envs) * (s["x_count"] * spectrum_bins(s["nperseg"]) + 1)
+
+
+def spectrum_device(x, rec_done, spec, window, tw, conditions=None, frame_first=0, frame_every=1, frames=None, sxx=True, work="auto"):
+    """spectrum_numpy on the device: ONE call of irrl_eval_spectrum on torch's current stream (one workgroup per robot and block of four columns
+    and, with more than one robot per condition, a second launch that adds the robots' partials in order), no synchronisation.  x: a float32
+    device tensor [rows, N, x_dim], rec_done a bool / uint8 device tensor [rows, N] or None; window, tw: the tables of spectrum_tables as numpy
+    arrays (uploaded here) or float64 device tensors.  sxx=False: no spectrograms although the spec lists robots.  work: "auto" = allocated here
+    where robots > 1, None = NULL (one robot per condition only), or a float64 device tensor of spectrum_work doubles.
+    -> dict of device tensors segments int64 [G], psd_sum float64 [G, cx, K], sxx float64 [M, cx, S_max, K] or None"""
+    import torch
+    from . import _lib
+    from ._lib import ptr
+    s = spectrum_spec(**spec)
+    if not sxx:
+        s = dict(s, matrix_env=())
+    cx, P, K = s["x_count"], s["nperseg"], spectrum_bins(s["nperseg"])
+    if x.dim() != 3 or x.shape[2] != s["x_dim"] or x.dtype != torch.float32 or not x.is_cuda:
+        raise ValueError("x: a float32 device tensor [rows, N, %d]" % s["x_dim"])
+    x = _lib.contig(x)
+    rows, n = int(x.shape[0]), int(x.shape[1])
+    dev = x.device
+    if rec_done is not None:
+        if tuple(rec_done.shape) != (rows, n) or rec_done.device != dev or rec_done.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("rec_done: a bool / uint8 device tensor [rows, N]")
+        rec_done = _lib.contig(rec_done).view(torch.uint8)
+
+    def table(t, shape, what):
+        if not torch.is_tensor(t):
+            t = torch.from_numpy(np.array(t)).to(dev)                  # (a copy: the caller's table may be read-only)
+        if tuple(t.shape) != shape or t.dtype != torch.float64 or t.device != dev:
+            raise ValueError("%s: float64 %s on the device of x (spectrum_tables)" % (what, list(shape)))
+        return _lib.contig(t)
+    window, tw = table(window, (P,), "window"), table(tw, (P, 2), "tw")
+    Cn, R = _motor_shape(n, n if conditions is None else conditions)
+    frame_first, frame_every, T = _spectrum_frames(rows, frame_first, frame_every, frames)
+    S_max = (T - P) // s["hop"] + 1 if T >= P else 0
+    if isinstance(work, str) and work == "auto":
+        work = torch.empty(spectrum_work(n, s), device=dev, dtype=torch.float64) if R > 1 else None
+    elif work is not None and (work.dtype != torch.float64 or work.numel() < spectrum_work(n, s) or work.device != dev or not work.is_contiguous()):
+        raise ValueError("work: a contiguous float64 device tensor of at least %d elements" % spectrum_work(n, s))
+    M = len(s["matrix_env"])
+    st = spectrum_struct(s if S_max > 0 else dict(s, matrix_env=()))      # (no segment anywhere: `sxx` is empty, and an empty tensor has no address)
+    out = dict(segments=torch.zeros(Cn, device=dev, dtype=torch.int64), psd_sum=torch.zeros(Cn, cx, K, device=dev, dtype=torch.float64),
+               sxx=torch.zeros(M, cx, S_max, K, device=dev, dtype=torch.float64) if M else None)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().irrl_eval_spectrum(ptr(x), ptr(rec_done), rows, n, Cn, R, frame_first, frame_every, T, C.cast(C.pointer(st), C.c_void_p),
+                                                  ptr(window), ptr(tw), ptr(out["segments"]), ptr(out["psd_sum"]), ptr(out["sxx"]), ptr(work),
+                                                  _lib.stream_ptr(dev)))
+    return out
+
+
+def spectrum_to_numpy(res):
+    """a result of spectrum_device -> the twin's dict of numpy arrays (synchronises)"""
+    return {k: None if v is None else v.cpu().numpy() for k, v in res.items()}
+
+
+def spectrum_row(psd_sum, segments, fs, names, band_hz, nperseg=None):
+    """One condition's Welch spectra -> per signal group `name` of names the keys vib_peak_hz_<name>, the frequency of the largest bin of the
+    group's spectrum without bin 0, and vib_frac_<name>, the fraction of the group's power in the bins above band_hz (of the power in the bins
+    k >= 1; the bins are equally wide, so the sums are the integrals).  psd_sum: name -> float64 [cx, K] (the call's sums of one condition),
+    segments: name -> int, or one int for all; the group's spectrum is the sum over its columns of psd_sum / segments.  nperseg: the segment
+    length behind the K bins (None: the even one, 2 (K - 1); an odd one has to be named).  NaN for both keys where the group has no segment or
+    its power is not a positive finite number."""
+    out = {}
+    for name in names:
+        p = np.asarray(psd_sum[name], np.float64)
+        n = int(segments[name] if isinstance(segments, dict) else segments)
+        K = p.shape[-1]
+        P = 2 * (K - 1) if nperseg is None else int(nperseg)
+        if spectrum_bins(P) != K:
+            raise ValueError("spectrum_row: nperseg = %d does not have %d bins" % (P, K))
+        peak = frac = float("nan")
+        if n > 0:
+            with np.errstate(invalid="ignore", over="ignore"):
+                w = p.reshape(-1, K).sum(0) / n
+                total = float(w[1:].sum())
+            if math.isfinite(total) and total > 0:
+                f = spectrum_frequencies(P, fs)
+                peak = float(f[1 + int(np.argmax(w[1:]))])
+                frac = float(w[1:][f[1:] > float(band_hz)].sum() / total)
+        out["vib_peak_hz_" + name], out["vib_frac_" + name] = peak, frac
+    return out
+
+
 # ---- the device loop ----
 def resolve_persistent(persistent, supported):
     """the `persistent` keyword of PolicyEvaluator.run / robustness_sweep (False, True, "auto"; the command line's "off" / "on" too) -> bool;
@@ -2084,7 +2340,7 @@ def load_policy(model_or_policy, device):
 def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=1000, steps=2000, cmd_hz=1.0, vel_hz=None, act_hz=None, clip=True,
                      mu_warm=0.8, device=None, persistent=PERSISTENT_DEFAULT, levels=None, level_steps=None, heading=None, gait=False,
                      mass=None, g=9.81, recurrence=None, recurrence_frames=None, record_body=False, footfall=None, motor=None, record_gait=False,
-                     correlation=None, record_correlation=False):
+                     correlation=None, record_correlation=False, spectrum=None, record_spectrum=False):
     """The reference's robustness grid in one pool: len(mus) x len(delays) x len(cmds) Manual-mode envs (condition index = (i_mu * len(delays) +
     i_delay) * len(cmds) + i_cmd), `warm_steps` control steps on friction mu_warm, then `steps` on the condition's own friction over which the
     statistics are taken.  env_cfg: the `environment:` mapping of a config.  persistent: PolicyEvaluator.run's keyword (same statistics bit for bit
@@ -2117,6 +2373,14 @@ def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=100
     "lstm") -- correlation_row; the rows of the first 8 conditions also carry `corr` float64 [cx, cy], the matrix r, and `corr_moments`, the
     condition's sums.  record_correlation: every row carries `corr_x` [frames, cx], `corr_y` [frames, cy] and `rec_done` [frames], the words
     the analysis saw.  With an MlpPolicy the source "lstm" is refused: the policy has no recurrent state.
+    spectrum: dict(nperseg=256, hop=224, window="tukey", alpha=0.25, detrend=1, band_hz=50.0, sources=("joint", "joint_rate", "action")), every
+    key optional (SPECTRUM_REFERENCE, all of SPECTRUM_SOURCES) -- the reference's `--virba`: the `obs_cond`, `act_applied` and `done` recorders
+    are kept on the device for the measured steps (either form of the loop, both policy kinds; no new recorder), irrl_eval_spectrum runs per
+    source and robot over the frames the row's statistics cover, scaled by the observation's / action's standard deviations (rad, rad/s, rad),
+    at fs = 1 / control_dt, and every row gains vib_peak_hz_<source> and vib_frac_<source> (spectrum_row) and `spectrum` = dict(freqs [K],
+    segments, <source>: psd_sum [12, K]) -- the Welch spectrum is psd_sum / segments; the rows of the first 8 conditions also carry `sxx` =
+    dict(<source>: [12, S_max, K]), the spectrograms.  record_spectrum: every row carries `spec_x` = dict(<source>: [frames, 12] float32) and
+    `rec_done` [frames], the words the analysis saw.
     Without these keywords the rows are what they were, key for key."""
     import torch
     import yaml
@@ -2177,13 +2441,37 @@ def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=100
                     spec=correlation_spec(srcs[0][1], srcs[0][2], srcs[0][3], srcs[1][1], srcs[1][2], srcs[1][3]))
     elif record_correlation:
         raise ValueError("record_correlation needs correlation=dict(x=..., y=...)")
-    if recurrence is None and not record_body and not want_gait and corr is None:
+    vib = None
+    if spectrum is not None:
+        unknown = set(spectrum) - set(SPECTRUM_REFERENCE) - {"sources"}
+        if unknown:
+            raise ValueError("spectrum: unknown keys %s" % sorted(unknown))
+        vib = dict(SPECTRUM_REFERENCE, sources=tuple(SPECTRUM_SOURCES))
+        vib.update(spectrum)
+        vib["sources"] = tuple(vib["sources"])
+        for k in vib["sources"]:
+            if k not in SPECTRUM_SOURCES:
+                raise KeyError("unknown spectrum source %r: choose from %s" % (k, sorted(SPECTRUM_SOURCES)))
+        _, obs_std, _, act_std = obs_normalisation({k: env.cfg_value(k) for k in ("abad", "Vx", "Vy", "Omega")})
+        listed = tuple(range(min(len(grid), SPECTRUM_MAX_MATRICES)))
+        vib["specs"] = {}
+        for k in vib["sources"]:
+            rec_name, c0, cn = SPECTRUM_SOURCES[k]
+            std = obs_std if rec_name == "obs_cond" else act_std
+            vib["specs"][k] = spectrum_spec(RECORDERS[rec_name], c0, cn, vib["nperseg"], vib["hop"], 1.0 / ev._dt, scale=std[c0:c0 + cn],
+                                            detrend=vib["detrend"], matrix_env=listed)
+        vib["tables"] = spectrum_tables(vib["nperseg"], vib["window"], vib["alpha"])
+    elif record_spectrum:
+        raise ValueError("record_spectrum needs spectrum=dict(...)")
+    if recurrence is None and not record_body and not want_gait and corr is None and vib is None:
         ev.run(steps, persistent=persistent)
         extra = lambda i, l: {}
     else:
         wanted = (("body",) if recurrence is not None or record_body else ()) + (("gait", "done") if want_gait else ())
         if corr is not None:
             wanted += tuple(corr["recs"]) + ("done",)
+        if vib is not None:
+            wanted += tuple(SPECTRUM_SOURCES[k][0] for k in vib["sources"]) + ("done",)
         rec = ev.run(steps, record=tuple(dict.fromkeys(wanted)), persistent=persistent)              # (each recorder once, in the order asked for)
         span = steps if levels is None else level_steps               # a row's frames: the run, or its level
         parts = []
@@ -2210,6 +2498,17 @@ def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=100
                 sp = corr["spec"]
                 win = lambda t, a, n: (t if t.dim() == 3 else t.unsqueeze(2))[:, :, a:a + n].cpu().numpy()
                 crec = (win(xr, sp["x_first"], sp["x_count"]), win(yr, sp["y_first"], sp["y_count"]), rec["done"].cpu().numpy())
+        vparts, vrec = [], None
+        if vib is not None:
+            if count > SPECTRUM_MAX_FRAMES:
+                raise ValueError("spectrum: a row covers %d frames, more than %d" % (count, SPECTRUM_MAX_FRAMES))
+            tabs = [torch.from_numpy(t).to(rec["done"].device) for t in vib["tables"]]
+            for l in range(1 if levels is None else levels):
+                vparts.append({k: spectrum_to_numpy(spectrum_device(rec[SPECTRUM_SOURCES[k][0]], rec["done"], vib["specs"][k], tabs[0], tabs[1],
+                                                                    frame_first=first(l), frames=count)) for k in vib["sources"]})
+            if record_spectrum:
+                vrec = ({k: rec[SPECTRUM_SOURCES[k][0]][:, :, SPECTRUM_SOURCES[k][1]:SPECTRUM_SOURCES[k][1] + SPECTRUM_SOURCES[k][2]].cpu().numpy()
+                         for k in vib["sources"]}, rec["done"].cpu().numpy())
         if recurrence is not None:
             shown = list(range(min(len(grid), RECURRENCE_MAX_MATRICES)))
             for l in range(1 if levels is None else levels):
@@ -2239,6 +2538,17 @@ def robustness_sweep(model_or_policy, env_cfg, mus, delays, cmds, warm_steps=100
             if crec is not None:
                 lo = first(l)
                 out["corr_x"], out["corr_y"], out["rec_done"] = crec[0][lo:lo + count, i], crec[1][lo:lo + count, i], crec[2][lo:lo + count, i]
+            if vparts:
+                v = vparts[l]
+                out.update(spectrum_row({k: v[k]["psd_sum"][i] for k in v}, {k: int(v[k]["segments"][i]) for k in v}, 1.0 / ev._dt, vib["sources"],
+                                        vib["band_hz"], nperseg=vib["nperseg"]))
+                out["spectrum"] = dict({k: v[k]["psd_sum"][i] for k in v}, freqs=spectrum_frequencies(vib["nperseg"], 1.0 / ev._dt),
+                                       segments=int(v[vib["sources"][0]]["segments"][i]))
+                if i < SPECTRUM_MAX_MATRICES and v[vib["sources"][0]]["sxx"] is not None:
+                    out["sxx"] = {k: v[k]["sxx"][i] for k in v}
+            if vrec is not None:
+                lo = first(l)
+                out["spec_x"], out["rec_done"] = {k: a[lo:lo + count, i] for k, a in vrec[0].items()}, vrec[1][lo:lo + count, i]
             if grec is not None:
                 out["rec_gait"], out["rec_done"] = grec[0][first(l):first(l) + count, i], grec[1][first(l):first(l) + count, i]
             if parts:
@@ -2423,14 +2733,21 @@ FOOTFALL_TABLE_KEYS = ("stride_hz_db", "duty_db", "gait", "sat_max")
 CORRELATION_TABLE_KEYS = ("corr_max", "corr_leg", "corr_unit")
 
 
-def sweep_table(rows, gait=False, recurrence=False, footfall=False, correlation=False):
+def spectrum_table_keys(sources=None):
+    """the columns sweep_table(spectrum=...) adds: vib_peak_hz_<source>, vib_frac_<source> per source (None: all of SPECTRUM_SOURCES)"""
+    return tuple(k + name for name in (tuple(SPECTRUM_SOURCES) if sources is None else sources) for k in ("vib_peak_hz_", "vib_frac_"))
+
+
+def sweep_table(rows, gait=False, recurrence=False, footfall=False, correlation=False, spectrum=False):
     """one line per row of a robustness_sweep; gait (rows of a sweep with gait=True): the cost of transport, the mean mechanical power, the four
     duty factors, `stride_hz` (mean over the legs of gait_from_sums' stride_hz<l>: the RAW contact flags' touchdown rate, several times the
     stride frequency because the flag chatters while a foot is down -- the debounced one is stride_hz_db) and the flight fraction too; footfall
     (rows of a sweep with a footfall spec): stride_hz_db and duty_db, the debounced stride frequency and duty factor (footfall_row, mean over
     the legs), the gait's name and, with a motor spec too, sat_max, the largest saturated fraction of a joint; recurrence (rows of a sweep with a recurrence spec): the
     recurrence rate, the determinism, the longest diagonal line and the stride period too; correlation (rows of a sweep with correlation=...):
-    corr_max, the largest |r| of a pair, with corr_leg and corr_unit, the x and the y column it belongs to"""
+    corr_max, the largest |r| of a pair, with corr_leg and corr_unit, the x and the y column it belongs to; spectrum (True, or the tuple of
+    sources; rows of a sweep with spectrum=...): per source vib_peak_hz_<source>, the frequency of the Welch spectrum's largest bin without
+    bin 0, and vib_frac_<source>, the fraction of its power above the band (spectrum_row)"""
     keys = ("vx_body_mean", "vx_body_std", "z_mean", "z_std", "roll_std", "pitch_mean", "pitch_std", "yaw_rate_mean")
     staircase = bool(rows) and "level" in rows[0]              # one row per (condition, level): the level and its commanded v_x as well
     lead = ("mu", "delay", "cmd") + (("level", "cmd_level") if staircase else ()) + ("falls",)
@@ -2444,6 +2761,9 @@ def sweep_table(rows, gait=False, recurrence=False, footfall=False, correlation=
         out[0] += " " + " ".join("%-12s" % k for k in FOOTFALL_TABLE_KEYS)
     if correlation:
         out[0] += " " + " ".join("%-12s" % k for k in CORRELATION_TABLE_KEYS)
+    vkeys = spectrum_table_keys(None if spectrum is True else spectrum) if spectrum else ()
+    if spectrum:
+        out[0] += " " + " ".join("%-12s" % k for k in vkeys)
     for r in rows:
         lvl = "%-5d %-9g " % (r["level"], r["cmd_level"]) if staircase else ""
         out.append("%-6g %-5d %-5g %s%-5d " % (r["mu"], r["delay"], r["cmd"], lvl, r["falls"]) + " ".join("%+12.4f" % r[k] for k in keys))
@@ -2458,4 +2778,6 @@ def sweep_table(rows, gait=False, recurrence=False, footfall=False, correlation=
         if correlation:
             label = lambda v: "-" if v is None else v if isinstance(v, str) else ":".join(str(p) for p in v)
             out[-1] += " %+12.4f %-12s %-12s" % (r["corr_max"], label(r["corr_leg"]), label(r["corr_unit"]))
+        if spectrum:
+            out[-1] += " " + " ".join("%+*.4f" % (max(12, len(k)), r[k]) for k in vkeys)
     return "\n".join(out)

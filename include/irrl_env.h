@@ -872,6 +872,64 @@ int irrl_eval_correlation(const float *x, const float *y, const uint8_t *rec_don
                           int frame_first, int frame_every, int frames, const irrl_eval_corr_spec *spec, int64_t *count, double *sx, double *sy,
                           double *sxy, float *range_x, float *range_y, double *work, void *hip_stream);
 
+/* SPECTROGRAM AND WELCH SPECTRUM OF RECORDER COLUMNS: the reference's `--virba`, its "time-frequency spectrum analysis of output"
+ * (run_bp_v5.py:1090-1117): scipy.signal.spectrogram(column, 1 / control_dt) of the joint angles, joint rates and actions -- whether a policy
+ * chatters, at which frequency, and where delay and the low-pass filters move that energy.  x is device f32 [rows, num_envs, x_dim], of which
+ * the columns x_first .. x_first + x_count are analysed.  Frames and T_e are irrl_eval_correlation's: analysed frame i is recorder row
+ * irrl_eval_recurrence_row(frame_first, frame_every, i), T_e = the first analysed frame whose rec_done word is non-zero (rec_done NULL or no such
+ * word: T_e = frames); env index = condition * robots + robot.
+ * Segment s of robot e covers the frames s * hop .. s * hop + nperseg - 1 and exists iff it lies wholly inside i < T_e:
+ * S_e = T_e >= nperseg ? (T_e - nperseg) / hop + 1 : 0 -- a robot that terminates early gives fewer segments, the reset row enters none.
+ * THE ONE ORDER (csrc/eval_elements.hpp irrl_eval_spectrum_*), all in f64, per segment and column c:
+ *   v_n = (double)x_n * scale[c];  detrend == 1: m = (((0.0 + v_0) + v_1) + ...) / nperseg, v_n -= m (detrend == 0: nothing is subtracted);
+ *   a_n = v_n * window[n];  Re_k = sum_n a_n * tw[(k n) mod nperseg].cos,  Im_k = -sum_n a_n * tw[(k n) mod nperseg].sin, n ascending from +0.0,
+ *   k = 0 .. K - 1, K = nperseg / 2 + 1;  P_k = g_k * density * (Re_k^2 + Im_k^2), density = 1 / (fs * sum_n window[n]^2), g_k = 2 except g_0 = 1
+ *   and, with an even nperseg, g_{K-1} = 1.
+ * This is scipy.signal.spectrogram(mode='psd', scaling='density', return_onesided=True, nfft=nperseg, noverlap=nperseg - hop); nperseg = 256,
+ * hop = 224, detrend = 1 and the Tukey(0.25) window are the reference's bare call.  The DFT is direct (nperseg need not be a power of two): a
+ * length-n dot product errs by at most n 2^-53 sum |a_n|, whatever the order and whether fused, which is what the tests' bound rests on.
+ * Tables, both device f64, owned by the caller: window [nperseg]; tw [nperseg, 2] = cos, sin of 2 pi j / nperseg.  irrl_eval_spectrum_tables
+ * fills HOST copies without touching the GPU, so that device, host program, numpy twin and tests share the same table bits: window_kind
+ * 0 boxcar (ones), 1 Hann, periodic (scipy get_window('hann', n)): 0.5 - 0.5 cos(2 pi n / nperseg), 2 Tukey(alpha), periodic (scipy
+ * get_window(('tukey', alpha), n)): with M = nperseg + 1 and width = floor(alpha (M - 1) / 2) the samples n <= width are
+ * 0.5 (1 + cos(pi (-1 + 2 n / alpha / (M - 1)))), the samples n >= M - width - 1 are 0.5 (1 + cos(pi (-2 / alpha + 1 + 2 n / alpha / (M - 1)))), the
+ * rest 1, the last of the M dropped; alpha <= 0 is the boxcar, alpha >= 1 Hann.  -> 0, or non-zero with "irrl_eval_spectrum_tables: " in front of
+ * the text for a NULL table, nperseg outside 8 .. IRRL_EVAL_SPECTRUM_MAX_NPERSEG, a window_kind outside 0 .. 2 or an alpha that is not finite.
+ * Outputs, K = nperseg / 2 + 1:
+ *   segments[g] i64             the sum of S_e over the condition's robots
+ *   psd_sum[g, cx, K] f64       the sum of P_k over those segments: per robot in ascending segment order from +0.0, then the robots' partials in
+ *                               ascending robot order from +0.0.  The Welch spectrum is psd_sum / segments (sums, not means, like the moments)
+ *   sxx[m, cx, S_max, K] f64    (NULL or matrix_count = 0: off) S_max = (frames - nperseg) / hop + 1: the P_k of every segment of robot
+ *                               matrix_env[m] -- the reference's pcolormesh --, segments >= S_e written as 0; a robot may be listed more than once
+ * work: device f64 [irrl_eval_spectrum_work(num_envs, spec)] = num_envs * (cx K + 1) doubles: the robots' partials [num_envs, cx, K], then S_e as
+ * int64 [num_envs]; needed with robots > 1, may be NULL with robots == 1 (the first kernel then writes the outputs itself).
+ * irrl_eval_spectrum_work needs no GPU; 0 for a NULL or refused spec or num_envs < 1.
+ * No atomics on any output, every output word has one writer, the same bits from run to run.  A non-finite sample poisons the bins of its own
+ * column in its own segment(s) and the psd_sum of its condition, and nothing else.  Stateless and stream-ordered, no env handle.
+ * frames < nperseg is accepted: nothing is launched, segments and psd_sum are set to zero (device memory by a memset on the stream; memory HIP
+ * does not know as a device's is written by the host), no error is set.
+ * Refused before any HIP call with "irrl_eval_spectrum: " in front of the text: NULL x, spec, window, tw, segments or psd_sum; x_dim < 1, a window
+ * outside its row width; x_count outside 1 .. IRRL_EVAL_SPECTRUM_MAX_X; nperseg outside 8 .. IRRL_EVAL_SPECTRUM_MAX_NPERSEG; hop outside
+ * 1 .. nperseg; detrend outside 0 .. 1; fs or a used scale entry that is not finite or <= 0; matrix_count outside 0 ..
+ * IRRL_EVAL_SPECTRUM_MAX_MATRICES; matrix_count > 0 with a NULL sxx; a matrix_env outside 0 .. num_envs - 1; num_envs < 1, conditions or robots
+ * < 1, conditions * robots != num_envs; frames outside 1 .. IRRL_EVAL_SPECTRUM_MAX_FRAMES; frame_first < 0, frame_every < 1, frame_first +
+ * (frames - 1) * frame_every >= rows; robots > 1 with work NULL. */
+#define IRRL_EVAL_SPECTRUM_MAX_FRAMES 16384
+#define IRRL_EVAL_SPECTRUM_MAX_X 64
+#define IRRL_EVAL_SPECTRUM_MAX_NPERSEG 1024
+#define IRRL_EVAL_SPECTRUM_MAX_MATRICES 8
+typedef struct irrl_eval_spectrum_spec {
+  int x_dim, x_first, x_count, nperseg, hop, detrend, matrix_count;
+  int matrix_env[8];
+  double fs;
+  double scale[64];
+} irrl_eval_spectrum_spec;
+int irrl_eval_spectrum_tables(int nperseg, int window_kind, double alpha, double *window, double *tw);
+size_t irrl_eval_spectrum_work(int num_envs, const irrl_eval_spectrum_spec *spec);
+int irrl_eval_spectrum(const float *x, const uint8_t *rec_done, int rows, int num_envs, int conditions, int robots, int frame_first,
+                       int frame_every, int frames, const irrl_eval_spectrum_spec *spec, const double *window, const double *tw,
+                       int64_t *segments, double *psd_sum, double *sxx, double *work, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

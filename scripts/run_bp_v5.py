@@ -23,6 +23,10 @@ reference's own (run_bp_v5.py:8-13), resolved by the compat packages at the repo
     python scripts/run_bp_v5.py --test --sweep --model data/..._final.pkl --sweep_cmd 2,5 --corr [--corr_x contact --corr_y lstm] --out sweep.json
                                                                                            # + the largest correlation of a foot-contact flag with
                                                                                            # an LSTM unit, its leg and unit; the matrices to --out
+    python scripts/run_bp_v5.py --test --sweep --model data/..._final.pkl --sweep_cmd 2,5 --vibration [--vib_nperseg 256 --vib_hop 224 --vib_window tukey \
+        --vib_band 50] --out sweep.json                                                    # + the Welch spectrum's peak frequency and the share of
+                                                                                           # power above the band for joint angles, joint rates and
+                                                                                           # actions; spectra and spectrograms to --out
     python scripts/run_bp_v5.py --test --sweep --step --gait --model data/..._final.pkl --persistent on   # cost of transport, duty factors and
                                                                                            # touchdown rate per (friction, command level)
 
@@ -134,6 +138,14 @@ def parse_args(argv):
                         "The measured steps run in the five-launch form (the LSTM state's recorder is steps x robots x 4 hid x 4 B)")
     p.add_argument("--corr_x", type=str, default="contact", help="--corr: the x source, one of contact, torque, joint_rate, body, obs, action, lstm, value")
     p.add_argument("--corr_y", type=str, default="lstm", help="--corr: the y source (an MlpPolicy checkpoint has no recurrent state: choose another than lstm)")
+    p.add_argument("--vibration", dest="flag_vibration", action="store_true", default=False,
+                   help="--sweep: the reference's --virba -- scipy.signal.spectrogram of the joint angles, joint rates and applied actions per robot on the "
+                        "device over the measured steps (evaluate.SPECTRUM_SOURCES, in rad, rad/s, rad): the table gains vib_peak_hz and vib_frac per "
+                        "source; --out also gets the Welch spectra of all conditions and the spectrograms (`sxx`) of the first 8")
+    p.add_argument("--vib_nperseg", type=int, default=256, help="--vibration: frames per segment, 8 .. 1024 (scipy's default 256)")
+    p.add_argument("--vib_hop", type=int, default=224, help="--vibration: frames between the starts of two segments (scipy's default nperseg - nperseg // 8)")
+    p.add_argument("--vib_window", choices=["boxcar", "hann", "tukey"], default="tukey", help="--vibration: the window (tukey: alpha 0.25, scipy's default)")
+    p.add_argument("--vib_band", type=float, default=50.0, help="--vibration: vib_frac is the share of power above this frequency [Hz] (the reference's set_ylim)")
     p.add_argument("--recurrence_frames", type=int, default=None, help="--recurrence: the last so many frames of the run are analysed (default: min(steps, 800))")
     p.add_argument("--recurrence_radius", type=int, default=None, help="--recurrence: the recurrence radius in levels of 0.001 (default 10)")
     return p.parse_args(argv)
@@ -171,6 +183,13 @@ def correlation_keywords(args):
     if args.persistent == "on":
         raise SystemExit("--corr records inside the policy, which only the five-launch form of the loop can: --persistent auto or off")
     return dict(correlation=dict(x=args.corr_x, y=args.corr_y))
+
+
+def vibration_keywords(args):
+    """--vibration [--vib_nperseg P --vib_hop H --vib_window NAME --vib_band HZ] -> the keywords of robustness_sweep"""
+    if not args.flag_vibration:
+        return {}
+    return dict(spectrum=dict(nperseg=args.vib_nperseg, hop=args.vib_hop, window=args.vib_window, band_hz=args.vib_band))
 
 
 def plain(v):
@@ -266,14 +285,15 @@ def run_sweep(args, cfg):
                     act_hz=none_if_off(args.act_filter_freq), persistent=PERSISTENT_DEFAULT if args.persistent is None else args.persistent,
                     levels=4 if args.flag_step else None, level_steps=args.step_steps if args.flag_step else None,
                     heading=heading_hold(n) if args.flag_dir_fd else None, **gait, **recurrence_keywords(args),
-                    **footfall_keywords(args, cfg["environment"]), **correlation_keywords(args))
+                    **footfall_keywords(args, cfg["environment"]), **correlation_keywords(args), **vibration_keywords(args))
     try:
         rows = robustness_sweep(args.trained_model, cfg["environment"], args.sweep_mu, args.sweep_delay, args.sweep_cmd, **keywords)
     except ValueError as e:
         if args.flag_corr and "no recurrent state" in str(e):      # an MlpPolicy checkpoint with --corr_y lstm (or --corr_x lstm)
             raise SystemExit("--corr: %s" % e)
         raise
-    print(sweep_table(rows, gait=args.flag_gait, recurrence=args.flag_recurrence, footfall=args.flag_footfall, correlation=args.flag_corr))
+    print(sweep_table(rows, gait=args.flag_gait, recurrence=args.flag_recurrence, footfall=args.flag_footfall, correlation=args.flag_corr,
+                      spectrum=args.flag_vibration))
     if args.out:
         with open(args.out, "w") as f:                                 # (--recurrence: the level matrices of the first 8 conditions as nested lists)
             json.dump([{k: plain(v) for k, v in r.items()} for r in rows], f, indent=1)   # (--footfall / --motor: the patterns and the maps too)
