@@ -8,6 +8,9 @@ Tolerances (fp32 kernels vs f64 oracle; the north-star asks for "a stated fp32 t
       velocities 5e-3 (joint rates reach 30 rad/s; (q_ref - q_ref_last)/0.002 amplifies 1 ulp 500x)
   free-running: 1 substep 2e-5 / 2e-3, 8 substeps 5e-5 / 5e-3, 400 substeps 5e-3 / 0.25 (pos / vel)
   -- legged contact dynamics amplify rounding, so the bound grows with the horizon.
+  dynamics probe (check_probe): max |dM^-1| / max |M^-1| < 2e-5 and |db| < 5e-3 (check_probe_max_norm: a max-norm, 20-400x looser than
+      f32 rounding), and then every entry of M^-1 and of the bias, scaled by the diagonal of M^-1, within 8x the f32 oracle's own
+      error: those bounds live in dynamics_parity_lib.BOUND, per state family (check_probe uses the `moving` family's row)
 Discrete outcomes (done flags, contact sets, RNG draws) must match exactly except where a threshold sits
 within rounding distance, which the fixed seeds below avoid.
 """
@@ -90,12 +93,24 @@ def check_init(orc, cand):
     np.testing.assert_allclose(cand.observe(), orc.observe(), atol=1e-4)
 
 
-def check_probe(orc, cand):
+def check_probe_max_norm(orc, cand):
     minv_o, nl_o = orc.inverse_mass_matrix(), orc.nonlinear()
     minv_c, nl_c = cand.probe()
     scale = np.abs(minv_o).max()
     assert np.abs(minv_c - minv_o).max() / scale < 2e-5
     assert np.abs(nl_c - nl_o).max() < 5e-3  # entries up to ~90 N
+
+
+def check_probe(orc, cand):
+    """The max-norm check on the pools as they come, then the entry-wise one (dynamics_parity_lib.check_probe_entrywise at the `moving`
+    family's bounds).  The entry-wise bounds are at rounding level, so that check is made from ONE identical state: callers that come
+    here behind a step of both pools are a step's rounding apart, and both pools are first set to the oracle's f32-rounded state."""
+    import dynamics_parity_lib as DL
+    check_probe_max_norm(orc, cand)
+    st = f32_round_state(orc.get_state())
+    orc.set_state(st)
+    cand.set_state(st)
+    DL.check_probe_entrywise(orc, cand, "moving", label="check_probe")
 
 
 def check_teacher_forced(orc, cand, steps, seed=0, action_scale=0.5, force_terminal_every=0, max_factor=10.0, perturb=None, cap_factor=None,
