@@ -333,6 +333,13 @@ class MlpPolicy(ActorCriticPolicy):
 
     @torch.no_grad()
     def value(self, obs, states=None, masks=None):
+        # the bootstrap value of a rollout.  On the device the GEMM library picks its kernel -- and with it the order of the sums -- by the row
+        # count: V of the same robot differed by an ulp or two between a pool of 1, 6 or 7 robots and a pool of 16, and the returns with it.  A
+        # pool of N robots is evaluated as the front of the next multiple of 16 (as lstm_fused.lstm_sequence pads the recurrent policy's pool),
+        # so its returns are the bits those robots have in a full pool; a multiple of 16 goes through as it did.
+        pad = (-obs.shape[0]) % 16 if (obs.is_cuda and obs.dim() == 2) else 0
+        if pad:
+            return self._run(torch.cat([obs, obs.new_zeros(pad, obs.shape[1])], 0))[1][:obs.shape[0]]
         return self._run(obs)[1]
 
     def evaluate_raw(self, obs, states=None, masks=None):

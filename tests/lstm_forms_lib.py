@@ -80,6 +80,17 @@ F_LSTM_CASES = ([(48, ob, n) for ob in (33, 34, 36, 1, 20, 32, 37, 48) for n in 
                 + [(h, ob, 7) for h in (32, 64) for ob in (20, 36)])
 F_MLP_CASES = [(ob, n) for ob in (1, 33, 36, 37, 64) for n in (5, 40)]
 
+# ---- G: policy step at other action widths, ob_dim 35: (hid, act, N) / (act, N) ----
+# The kernels take act_dim at run time (policy_heads: thread (env, action) + 16 value threads; policy_heads_wave: lane (env, action) + 4 value
+# lanes; the sampler's Philox block is action index >> 2, so slots 12 .. 15 are the fourth block, purpose word 0x53).  The entry points accept
+# act_dim <= 16 with 16 act + 16 <= threads = 8 hid (LSTM: (32, 15) meets it with equality, (32, 16) is refused) and act_dim <= 15 with
+# 4 act + 4 <= 64 (MLP: 15 fills the wave, 16 is refused).
+G_OB = 35
+G_LSTM_CASES = [(h, a, n) for (h, a) in ((48, 1), (48, 5), (48, 16), (64, 16), (32, 15)) for n in (7, 40)]
+G_MLP_CASES = [(a, n) for a in (1, 5, 15) for n in (5, 40)]
+G_LSTM_REFUSED, G_MLP_REFUSED = (32, 16), 16
+G_RNG_STEP, G_RNG_ENV0, G_RNG_SEED = (5 << 32) + 42, 1000, 1234567      # the sampler launch: step with a non-zero high word, a global id of env 0
+
 # tall GEMMs: (K, m, n)
 TALL_CASES = [(K, m, n) for (m, n) in ((48, 12), (64, 256)) for K in (16384, 16384 + 16, 4096)]
 
@@ -319,10 +330,11 @@ def eager_policy(pol, obs, st, masks, act):
 
 
 # ---- policy steps ----
-def make_lstm_step_inputs(fc, device="cpu"):
+def make_lstm_step_inputs(fc, device="cpu", act=12):
+    """act: the action width (12: the F cases and their seeds; another width draws from a seed of its own)"""
     hid, ob, N = fc
-    torch.manual_seed(seed_of(("lstm",) + tuple(fc)))
-    pol = CustomLSTMPolicy(ob_dim=ob, n_lstm=(hid, hid))
+    torch.manual_seed(seed_of(("lstm",) + tuple(fc) + (() if act == 12 else ("act", act))))
+    pol = CustomLSTMPolicy(ob_dim=ob, act_dim=act, n_lstm=(hid, hid))
     with torch.no_grad():
         for p in pol.parameters():
             p.add_(torch.randn_like(p) * 0.05)
@@ -330,7 +342,7 @@ def make_lstm_step_inputs(fc, device="cpu"):
     st = torch.randn(N, 8 * hid) * 0.5
     dones = torch.rand(N) < 0.2
     dones[0], dones[N - 1] = True, False       # both kinds of rows at every N
-    noise = torch.randn(N, 12)
+    noise = torch.randn(N, act)
     dev = torch.device(device)
     return pol.to(dev), obs.to(dev), st.to(dev), dones.to(dev), noise.to(dev)
 
@@ -349,17 +361,17 @@ def lstm_step_reference(pol, obs, st, dones, noise, dtype=torch.float64):
         SBLstm.use_fused = True
 
 
-def make_mlp_step_inputs(fc, device="cpu"):
+def make_mlp_step_inputs(fc, device="cpu", act=12):
     ob, N = fc
-    torch.manual_seed(seed_of(("mlp",) + tuple(fc)))
-    pol = MlpPolicy(ob_dim=ob)
+    torch.manual_seed(seed_of(("mlp",) + tuple(fc) + (() if act == 12 else ("act", act))))
+    pol = MlpPolicy(ob_dim=ob, act_dim=act)
     with torch.no_grad():
         for p in pol.parameters():
             p.add_(torch.randn_like(p) * 0.05)
     obs = torch.randn(N, ob)
     dones = torch.rand(N) < 0.2
     dones[0], dones[N - 1] = True, False       # both kinds of rows at every N
-    noise = torch.randn(N, 12)
+    noise = torch.randn(N, act)
     dev = torch.device(device)
     return pol.to(dev), obs.to(dev), dones.to(dev), noise.to(dev)
 

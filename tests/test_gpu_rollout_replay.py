@@ -1,6 +1,7 @@
 """The seam between a device rollout and the update, on an MI355X: a real rollout of ppo2.Runner on the HIP engine, then everything it recorded
 recomputed in float64 from the recorded observations alone (tests/rollout_replay_lib.py; tests/test_rollout_replay_reference.py checks that
-library against the eager runner on the CPU oracle).
+library against the eager runner on the CPU oracle).  The checks themselves are written once, in tests/rollout_checks_lib.py, for this module and
+tests/test_gpu_rollout_ragged.py.
 
 Pool: default_cfg.yaml, 40 robots (two full 16-robot workgroups and a ragged one), EnvIdOffset 1000, 24 steps, two consecutive run() calls per
 case -- the second starts at rng_base 24 with the carried LSTM state and done flags.  Chosen robots are thrown over the 0.65 m termination
@@ -37,19 +38,16 @@ None of these bounds was fitted to a GPU run.  Measured on an MI355X, worst of t
   lr-0 update, MlpPolicy: approxkl 5.3e-13 (f32), 3.0e-11 (bf16x3), the same with and without records and for 1 and 4 minibatches; |pg| <= 6.3e-08;
   vf and entropy equal float64 to the 7 digits printed, clipfrac 0, in all 11 update cases.
 """
-import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-import lstm_forms_lib as FL
 import ppo_loss_lib as PL
+import rollout_checks_lib as K
 import rollout_replay_lib as R
 from conftest import load_env_cfg
 
-CLIPRANGE = 0.2
-SAMPLER_TOL = 2e-3          # test_fused_policy_step_kernel_noise_is_the_counter_rng
 # (policy, mode, logstd range)
 CASES = [("lstm", "default", None), ("lstm", "stepwise", (-1.0, 0.5)), ("mlp", "default", (-1.0, 0.5)), ("mlp", "stepwise", None)]
 _cache = {}
@@ -88,116 +86,24 @@ def _case(kind, mode, logstd_range):
     return _cache[key]
 
 
-def _hold(what, errs, bounds, fallback):
-    """every error within its bound; one that is not, within 4 x the error of the float32 eager replay on the same batch (computed only then)"""
-    over = {k: e for k, e in errs.items() if not e <= bounds[k]}
-    if over:
-        fb = fallback()
-        print("\n[rollout replay %s] over its bound: %s; float32 eager replay: %s" % (what, FL.fmt(over), FL.fmt({k: fb[k] for k in over})))
-        for k, e in over.items():
-            assert e <= 4.0 * fb[k], (what, k, e, bounds[k], fb[k])
-
-
-def _f32_replay_errors(pol, batch, last, rep):
-    """the errors of `replay_errors` / `returns_errors` for the float32 eager replay in place of the recorded numbers"""
-    r32 = R.replay(pol, batch, last, dtype=torch.float32)
-    fake_batch = dict(batch, values=r32["value"], neglogpacs=r32["neglogp"])
-    fake_last = dict(last, result=r32["last_value"], states=r32["state"])
-    return R.replay_errors(pol, fake_batch, fake_last, rep)
-
-
 @pytest.mark.parametrize("kind,mode,logstd_range", CASES, ids=["%s-%s" % c[:2] for c in CASES])
 def test_device_rollout_is_what_a_float64_replay_of_its_observations_gives(kind, mode, logstd_range):
     model, runner, rollouts = _case(kind, mode, logstd_range)
-    pol, plan, T, N = model.policy, R.PLAN, R.T_STEPS, R.N_ENVS
-    for r, (batch, last, rng_base) in enumerate(rollouts):
-        what = (kind, mode, r)
-        # 1. conditions: exactly the designed episode ends, and they are the ones this test is about
-        ends = R.realised_ends(batch, last)
-        assert ends == {i: [k] for i, k in plan.items()}, (what, ends)
-        rows = {k for ks in ends.values() for k in ks}
-        assert len(rows) >= 4 and {1, T - 1, T} <= rows and any(i >= 32 for i in ends) and len({i // 16 for i in ends}) == 3
-        want_last = torch.tensor([plan.get(i) == T for i in range(N)], device=last["dones"].device)
-        assert torch.equal(last["dones"].bool(), want_last) and bool(want_last.any())
-        if r:
-            assert torch.equal(batch["masks"][0], rollouts[r - 1][1]["dones"].to(batch["masks"].dtype)) and bool(batch["masks"][0].any())
-        else:
-            assert not batch["masks"][0].any()
-        if pol.recurrent:
-            assert torch.equal(batch["states"], rollouts[r - 1][1]["states"]) if r else not batch["states"].any()
-        rep = R.replay(pol, batch, last)
-        if logstd_range is not None:
-            assert float(rep["logstd"].min()) == logstd_range[0] and float(rep["logstd"].max()) == logstd_range[1]
-        # 2. the sampler: every row, env and slot
-        s_err = R.sampler_error(model, batch, rep, rng_base)
-        # 3. + 4. old neglogp / values, carried state by halves, bootstrap
-        errs = R.replay_errors(pol, batch, last, rep)
-        # 5. returns
-        g_errs = R.returns_errors(batch, last, rep)
-        # 6. power
-        power = R.power_errors(pol, batch, last, rep)
-        print("\n[rollout replay %s-%s rollout %d] sampler %.2e  %s  %s  masks one row early: values (least / largest over the ended robots) %s, returns (least) %.1e"
-              % (kind, mode, r, s_err, FL.fmt(errs), FL.fmt(g_errs),
-                 "%.1e / %.1e" % (min(p[0] for p in power.values()), max(p[0] for p in power.values())) if pol.recurrent else "n/a",
-                 min(p[1] for p in power.values())))
-        assert s_err <= SAMPLER_TOL, (what, s_err)
-        assert pol.recurrent == ("state_v" in errs)
-        _hold(what, errs, R.REPLAY_TOL, lambda: _f32_replay_errors(pol, batch, last, rep))
-        assert g_errs["returns"] <= R.RETURNS_TOL and g_errs["advantages"] <= R.RETURNS_TOL, (what, g_errs)
-        assert set(power) == set(plan)
-        for i, (_, r_err) in power.items():
-            assert r_err >= R.POWER * R.RETURNS_TOL, (what, i, r_err)
-        # (the values' error is, as in 3., the largest over the tensor -- here the ended robots' columns: how far ONE robot's value moves when its
-        # state is cleared a row early is the policy's business, 1.3e-03 .. 3.3e-02 in these cases)
-        assert not pol.recurrent or max(p[0] for p in power.values()) >= R.POWER * R.REPLAY_TOL["value"], (what, power)
-
-
-def _zero_lr_update(model, batch, last, rep, tol, d_new=None):
-    """update(batch, 0.0, cliprange) on the recorded batch -> printed line; asserts what the module docstring says.  d_new: the measured absolute
-    error of the device's new neglogp (None: tol (1 + max |neglogp64|))"""
-    pol = model.policy
-    before = [p.detach().clone() for p in pol.parameters()]
-    shuffles = model._shuffles
-    want = R.expected_stats(model, batch, rep, CLIPRANGE, shuffles).numpy()
-    got = model.update(batch, 0.0, CLIPRANGE).double().cpu().numpy()
-    torch.cuda.synchronize()
-    for a, b in zip(before, pol.parameters()):
-        assert torch.equal(a, b)
-    nlp_scale = 1.0 + float(rep["neglogp"].abs().max())
-    d_old = float((batch["neglogpacs"].double().cpu() - rep["neglogp"]).abs().max())
-    d_new = tol * nlp_scale if d_new is None else d_new
-    line = "pg %.2e (want %.2e) vf %.7g (%.7g) entropy %.7g (%.7g) approxkl %.2e (bound %.2e) clipfrac %g" % (
-        got[0], want[0], got[1], want[1], got[2], want[2], got[3], 0.5 * (d_old + d_new) ** 2, got[4])
-    print(line)
-    assert got[4] == 0.0 and want[4] == 0.0, line
-    np.testing.assert_allclose(got[:3], want[:3], rtol=10 * tol, atol=tol, err_msg=line)
-    assert got[3] <= 0.5 * (d_old + d_new) ** 2, line
-    return line
+    plan, T = R.PLAN, R.T_STEPS
+    # the designed ends are the ones this test is about (rollout_checks_lib.check_replay asserts that they are exactly the realised ones)
+    rows = set(plan.values())
+    assert len(rows) >= 4 and {1, T - 1, T} <= rows and any(i >= 32 for i in plan) and len({i // 16 for i in plan}) == 3
+    assert rollouts[0][0]["masks"].shape[1] == R.N_ENVS
+    K.check_replay(model, rollouts, plan, (kind, mode), logstd_range)
 
 
 @pytest.mark.parametrize("prec", ["f32", "bf16x3", "bf16x6"])
 def test_zero_learning_rate_update_of_the_lstm_policy_sees_ratio_one(prec, monkeypatch):
     from high_speed_quadrupedal_locomotion_by_irrl_amd import lstm_fused
     model, runner, rollouts = _case(*CASES[0])
-    pol = model.policy
     batch, last, _ = rollouts[1]
     monkeypatch.setattr(lstm_fused, "PRECISION", prec)
-    assert model.nminibatches == 1 and model.fused_loss and model.fused_heads and pol.fused_heads_supported(batch["obs"])
-    rep = R.replay(pol, batch, last)
-    # per sample: what the update's forward pass gives on the device for the recorded batch
-    nlp, val, _ = pol.evaluate(batch["obs"], batch["states"], batch["masks"], batch["actions"])
-    errs = {"neglogp": FL.rel_err(nlp.detach(), rep["neglogp"]), "value": FL.rel_err(val.detach(), rep["value"])}
-    print("\n[lr-0 update, lstm, %s] evaluate on the device against float64: %s" % (prec, FL.fmt(errs)))
-
-    def fallback():
-        r32 = R.replay(pol, batch, last, dtype=torch.float32)
-        return {"neglogp": FL.rel_err(r32["neglogp"], rep["neglogp"]), "value": FL.rel_err(r32["value"], rep["value"])}
-    _hold(("evaluate", prec), errs, {k: FL.BOUNDS[prec] for k in errs}, fallback)
-    d_new = float((nlp.detach().double().cpu() - rep["neglogp"]).abs().max())
-    # (hence |exp(old - new) - 1| of every sample within expm1 of the two measured errors' sum)
-    ratio = torch.exp(batch["neglogpacs"].double().cpu() - nlp.detach().double().cpu())
-    print("max |ratio - 1| %.2e" % float((ratio - 1.0).abs().max()), end="  ")
-    _zero_lr_update(model, batch, last, rep, FL.BOUNDS[prec], d_new=d_new)
+    K.lstm_zero_lr_check(model, batch, last, prec)
 
 
 @pytest.mark.parametrize("nminibatches", [1, 4])
@@ -213,5 +119,5 @@ def test_zero_learning_rate_update_of_the_mlp_policy_sees_ratio_one(prec, record
     rep = R.replay(model.policy, batch, last)
     shuffles = model._shuffles
     print("\n[lr-0 update, mlp, %s, records %s, %d minibatches]" % (prec, records, nminibatches), end=" ")
-    _zero_lr_update(model, batch, last, rep, PL.BOUNDS[prec])
+    K.zero_lr_update(model, batch, last, rep, PL.BOUNDS[prec])
     assert model._shuffles - shuffles == model.noptepochs

@@ -10,6 +10,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from conftest import load_env_cfg
+from rollout_checks_lib import assert_actor_only_equals as _assert_actor_only_equals
 
 CONTACT_KEYS = ("ContactSolver", "ContactExit", "ContactTolerance", "ContactIterations")
 LAYOUTS = {"l16": ("16", "1", "_l16"), "l4": ("4", "1", "_l4"), "l4w2": ("4", "2", "_l4w2")}    # IRRL_LANES_PER_ROBOT, IRRL_L4_WAVES, kernel suffix
@@ -119,19 +120,6 @@ def _three_rollouts(runner, env):
     b2 = {k: v.clone() for k, v in runner.run().items() if torch.is_tensor(v)}
     b3 = {k: v.clone() for k, v in runner.run().items() if torch.is_tensor(v)}
     return b1, b2, b3
-
-
-def _assert_actor_only_equals(got, want, tag):
-    """the comparisons of test_graph_capture_warmup_leaves_no_trace_and_setters_invalidate_the_graph for the actor-only rollout: the actor side
-    bit for bit; values, returns and the critic's half of the carried state at that test's 2e-5 of their scale (the sequence kernels' error)"""
-    for k in ("obs", "actions", "true_reward", "masks", "neglogpacs"):
-        assert torch.equal(got[k], want[k]), (tag, k)
-    sa, se = got["states"], want["states"]
-    assert torch.equal(sa[:, :192], se[:, :192]), tag
-    assert float((sa[:, 192:] - se[:, 192:]).abs().max()) < 2e-5 * (1.0 + float(se[:, 192:].abs().max())), tag
-    for k in ("values", "returns"):
-        a, b = got[k], want[k]
-        assert float((a - b).abs().max()) < 2e-5 * (1.0 + float(b.abs().max())), (tag, k, float((a - b).abs().max()))
 
 
 @pytest.mark.parametrize("kind,modes", [("no_contact_keys", ("direct", "one_launch", "persistent", "persistent_actor", "persistent_actor_wg")),

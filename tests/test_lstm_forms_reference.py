@@ -65,6 +65,70 @@ def test_eager_f32_mlp_step_stays_under_a_quarter_of_the_kernel_bound(fc):
         assert e <= 0.25 * L.STEP_TOL[name], (fc, name, e)
 
 
+@pytest.mark.parametrize("gc", L.G_LSTM_CASES, ids=L.case_id)
+def test_lstm_step_reference_at_other_action_widths(gc):
+    """group G: the float64 step reference returns tensors of the asked width, the eager f32 step stays under a quarter of the kernel bound, and
+    the width-12 draw is the F cases' draw (the action width enters the seed only when it is not 12)"""
+    hid, A, N = gc
+    pol, obs, st, dones, noise = L.make_lstm_step_inputs((hid, L.G_OB, N), act=A)
+    assert pol.act_dim == A and noise.shape == (N, A) and obs.shape == (N, L.G_OB) and pol.logstd.shape == (1, A)
+    ref = dict(zip(("action", "value", "state", "neglogp"), L.lstm_step_reference(pol, obs, st, dones, noise)))
+    assert ref["action"].shape == (N, A) and ref["value"].shape == (N,) and ref["state"].shape == (N, 8 * hid) and ref["neglogp"].shape == (N,)
+    assert all(v.dtype == torch.float64 and torch.isfinite(v).all() for v in ref.values())
+    out = dict(zip(("action", "value", "state", "neglogp"), L.lstm_step_reference(pol, obs, st, dones, noise, dtype=torch.float32)))
+    for name, e in L.step_errors(out, ref).items():
+        assert e <= 0.25 * L.STEP_TOL[name], (gc, name, e)
+    assert 0 < int(dones.sum()) < N
+    assert (16 * A + 16 <= 8 * hid) and A <= 16
+
+
+@pytest.mark.parametrize("gc", L.G_MLP_CASES, ids=L.case_id)
+def test_mlp_step_reference_at_other_action_widths(gc):
+    A, N = gc
+    pol, obs, dones, noise = L.make_mlp_step_inputs((L.G_OB, N), act=A)
+    assert pol.act_dim == A and noise.shape == (N, A) and pol.logstd.shape == (1, A)
+    ref = dict(zip(("action", "value", "neglogp"), L.mlp_step_reference(pol, obs, noise)))
+    assert ref["action"].shape == (N, A) and ref["value"].shape == (N,) and ref["neglogp"].shape == (N,)
+    out = dict(zip(("action", "value", "neglogp"), L.mlp_step_reference(pol, obs, noise, dtype=torch.float32)))
+    for name, e in L.step_errors(out, ref).items():
+        assert e <= 0.25 * L.STEP_TOL[name], (gc, name, e)
+    assert 4 * A + 4 <= 64
+
+
+def test_action_width_twelve_keeps_the_draws_of_the_observation_width_cases():
+    a = L.make_lstm_step_inputs(L.F_LSTM_CASES[0])
+    b = L.make_lstm_step_inputs(L.F_LSTM_CASES[0], act=12)
+    assert all(torch.equal(x, y) for x, y in zip(a[1:], b[1:])) and all(torch.equal(x, y) for x, y in zip(a[0].parameters(), b[0].parameters()))
+    c = L.make_lstm_step_inputs(L.F_LSTM_CASES[0], act=5)
+    assert not torch.equal(a[1], c[1])
+    a, b = L.make_mlp_step_inputs(L.F_MLP_CASES[0]), L.make_mlp_step_inputs(L.F_MLP_CASES[0], act=12)
+    assert all(torch.equal(x, y) for x, y in zip(a[1:], b[1:]))
+    assert L.G_LSTM_REFUSED == (32, 16) and 16 * 16 + 16 > 8 * 32 and 16 * 15 + 16 == 8 * 32 and 4 * 15 + 4 == 64 and L.G_MLP_REFUSED == 16
+
+
+@pytest.mark.parametrize("act", [1, 5, 15, 16])
+def test_sampler_reference_at_other_action_widths_is_the_oracle_generator(act):
+    """rollout_replay_lib.sampler_reference(..., act_dim): slot a comes from Philox block a >> 2 (purpose word 0x50 + block, up to 0x53 for slots
+    12 .. 15) of the oracle's independent C statement of the generator, through Box-Muller on (u0, u1) and (u2, u3)"""
+    import oracle as O
+    import rollout_replay_lib as R
+    seed, step = L.G_RNG_SEED, L.G_RNG_STEP + 3
+    envs = np.array([0, 6, 39]) + L.G_RNG_ENV0
+    z = R.sampler_reference(seed, envs, step, act)
+    assert z.shape == (3, act)
+    for i, env in enumerate(envs):
+        want = []
+        for q in range((act + 3) // 4):
+            u = O.rng_u01(seed, int(env), step >> 32, step & 0xFFFFFFFF, 0x50 + q)
+            for a, b in ((u[0], u[1]), (u[2], u[3])):
+                r = np.sqrt(-2.0 * np.log(1.0 - a))
+                want += [r * np.cos(2 * np.pi * b), r * np.sin(2 * np.pi * b)]
+        assert (act + 3) // 4 - 1 == (act - 1) >> 2 <= 3
+        assert np.abs(z[i] - np.array(want[:act])).max() < 1e-12, (env, act)
+    # a narrower policy draws the front of a wider one's noise
+    assert np.array_equal(z, R.sampler_reference(seed, envs, step, 16)[:, :act])
+
+
 @pytest.mark.parametrize("case", [L.A_CASES[1], L.D_CASES[1]], ids=L.case_id)
 def test_float64_eager_forward_equals_an_independent_numpy_recurrence(case):
     """pins the reference itself: (9, 40, 35, 48) with random episode starts, and (9, 16, 35, 48) with a start at t = 0 only"""
@@ -136,6 +200,9 @@ def test_policy_step_entry_points_refuse_unsupported_widths_before_any_launch():
     assert mlp_rc(L.MLP_STEP_MAX_OB + 1) == 1 and mlp_rc(0) == 1 and mlp_rc(-3) == 1 and mlp_rc(1 << 20) == 1
     assert mlp_rc(35, hid=48) == 1 and mlp_rc(35, act=16) == 1 and mlp_rc(35, n=0) == 1
     assert lstm_rc(0) == 1 and lstm_rc(-1) == 1 and lstm_rc(35, hid=40) == 1 and lstm_rc(35, hid=16) == 1 and lstm_rc(35, act=17) == 1 and lstm_rc(35, n=0) == 1
+
+    # the thread budgets: 16 act + 16 <= 8 hid (LSTM), act <= 15 (MLP: 4 act + 4 <= 64)
+    assert lstm_rc(35, hid=L.G_LSTM_REFUSED[0], act=L.G_LSTM_REFUSED[1]) == 1 and mlp_rc(35, act=L.G_MLP_REFUSED) == 1
 
     def fake_obs(ob):
         return SimpleNamespace(is_cuda=True, dtype=torch.float32, shape=(5, ob))
